@@ -15,12 +15,19 @@ the 2B [cond;uncond] batch) + VAE decode.  ``--config`` picks the workload by SU
 actually ran.  Weights are random (recipe scaling; no checkpoint exists offline), inputs synthetic and resident in
 HBM before the timed region.  value = images/s over all ranks (weak scaling: fixed images per GPU per step).
 
+A plain run sets up, warms up, times the --steps steps and prints the line.  Everything measured or checked beside
+the headline runs only with --full: the strict-mode leg, the standalone hot-kernel and per-class timings, the CLIP
+text-tower timing, the CPU baseline, the parity re-check against the oracle, and configs[4]'s host-processor check.
+--dump-outputs DIR writes what the last timed step returned (images, final latents, configs[4]'s reward scores) as
+float32 DIR/<name>.npy, rank 0 only, at most 64 MB in all (a fixed seeded sample of the elements beyond that).
+Every weight and input is drawn from a seeded generator, so the same arguments give the same inputs in every run.
+
 Extra objects in the JSON line:
   roofline      whole-UNet-forward MFMA roofline: algorithmic FLOPs of the forwards executed in the
                 timed region (F_full = 1.1477 TFLOP / sample-forward with the fuser,
                 F_off = 0.8141 TFLOP when the sampler's scale-0 skips it) / HIP-event time of those
                 forward launches (graph replays) vs the 2.5 PFLOP/s dense fp16 MFMA peak.
-  cpu_baseline  the fp32 oracle (CPU restatement of the reference UNet, oracle/unet_ref.py) timed on
+  cpu_baseline  (--full) the fp32 oracle (CPU restatement of the reference UNet, oracle/unet_ref.py) timed on
                 this box's host cores on a bounded sample (rank 0, N=1 only).
 """
 from __future__ import annotations
@@ -38,6 +45,7 @@ import numpy as np
 import torch
 
 MFMA_PEAK_TFLOPS = 2500.0
+DUMP_BYTES = 64 << 20
 # SURVEY 8d numbering -> (BASELINE.json configs index, images per GPU, latent side, boxes per image)
 CONFIGS = {2: (1, 4, 64, 8), 3: (2, 2, 96, 16), 4: (3, 8, 64, 8), 5: (4, 16, 64, 8)}
 
@@ -137,7 +145,22 @@ def parse():
     ap.add_argument("--force-dist", action="store_true", help="take the multi-rank code path (process group, bundle broadcast, barriers, max-over-ranks) "
                     "even at WORLD_SIZE=1: runs the RCCL calls on a 1-GPU box")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to smoke-test the path on one GPU)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beside the headline (strict leg, hot kernel and "
+                    "kernel classes, CLIP text tower, CPU baseline, oracle parity, configs[4] host processor); the --no-* flags still apply")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as float32 DIR/<name>.npy (rank 0, <= 64 MB in all)")
     return ap.parse_args()
+
+
+def dump_outputs(path, arrays):
+    """float32 .npy per output; above DUMP_BYTES in all, each output keeps the same share of a fixed seeded sample of its elements"""
+    os.makedirs(path, exist_ok=True)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if total > DUMP_BYTES:
+            idx = np.random.default_rng(0).choice(a.size, a.size * DUMP_BYTES // total, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # descriptive strings of the JSON line that --verbose-json keeps; the default line carries the numbers only (VERDICT r5: the ~5 KB line lost its
@@ -215,12 +238,14 @@ def main():
     packed_strict = None
     if rank == 0:
         sd = random_state_dict(cfg, dev, seed=0)
-        fc = {"weight": torch.randn(cfg.model_channels, cfg.in_channels, 3, 3, device=dev) * 0.16,
+        gfc = torch.Generator(device=dev)
+        gfc.manual_seed(2)                         # seeded like the UNet (0) and VAE (1) weights: the same SD first conv in every run
+        fc = {"weight": torch.randn(cfg.model_channels, cfg.in_channels, 3, 3, device=dev, generator=gfc) * 0.16,
               "bias": torch.zeros(cfg.model_channels, device=dev)}
         packed = pack_state_dict(sd, cfg, dev, fc)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sd_cpu_sample = {k: v.cpu() for k, v in sd.items()}
-        want_strict = world == 1 and not args.no_strict and not args.tiny and cnum == 2 and not overridden
+        want_strict = args.full and world == 1 and not args.no_strict and not args.tiny and cnum == 2 and not overridden
         packed_strict = None
         if want_strict:
             # the same weights in the split layout ([Whi | Wlo] for every matrix): the strict-mode engine of the second leg
@@ -287,8 +312,8 @@ def main():
     # GPU (preprocess.py: Pillow's fixed-point algorithm bit for bit; the 16 ground-truth images arrive as host uint8 480 x 640 arrays,
     # like dataset images, and take the same kernels after one upload) -> CLIP ViT-L/14 vision tower (HIP) on the 16 predictions and the
     # 16 ground-truth images, text tower (HIP) on the 16 captions -> similarities + AestheticMLP (gl_reward_score).  Random-init towers
-    # of the ViT-L/14 architecture.  The first step also runs the reference's host path (HF processor on the CPU) once: the GPU
-    # pixel_values must equal it bitwise, and its time is reported beside the GPU one.
+    # of the ViT-L/14 architecture.  With --full, the reference's host path (HF processor on the CPU) runs once after the timed steps:
+    # the GPU pixel_values must equal it bitwise, and its time is reported beside the GPU one.
     scorer, score_events, score_in = None, [], None
     reward_stage_ms = {"processor_cpu": [], "preprocess_equal": []}
     if cnum == 5 and not args.tiny:
@@ -301,11 +326,13 @@ def main():
             aes_sd[f"layers.{li}.weight"] = (torch.rand(n_, k_, device=dev, generator=gsc) * 2 - 1) * (3.0 / k_) ** 0.5
             aes_sd[f"layers.{li}.bias"] = (torch.rand(n_, device=dev, generator=gsc) * 2 - 1) * 0.1
         scorer = RewardModel(random_clip_vit_l14_state_dict(dev, gsc), aes_sd, dev)
-        try:
-            from transformers import CLIPImageProcessor
-            processor = CLIPImageProcessor()
-        except Exception as e:                                   # pragma: no cover
-            raise SystemExit(f"--config 5 needs transformers' CLIPImageProcessor for the host-side preprocessing step: {e}")
+        processor = None
+        if args.full:
+            try:
+                from transformers import CLIPImageProcessor
+                processor = CLIPImageProcessor()
+            except Exception as e:                                   # pragma: no cover
+                raise SystemExit(f"--config 5 --full needs transformers' CLIPImageProcessor for the host-side preprocessing check: {e}")
         import numpy as _np
         gt_u8 = _np.random.default_rng(7 + rank).integers(0, 256, (B, 480, 640, 3), dtype=_np.uint8)       # ground-truth images (host, dataset-like)
         cap_ids = torch.randint(1, 49406, (B, 77), device=dev, generator=gsc)
@@ -316,10 +343,13 @@ def main():
             cap_ids[b_, L_ + 1:] = 49407
         score_in = (cap_ids, gt_u8, processor)
 
+    last = {}                                      # what the latest step returned to its caller (--dump-outputs)
+
     def one_step():
         model.first_conv_type = "GLIGEN"
         lat = denoise(all_models, inp["context"], inp["uc"], inp["relations"], batch, inp["x"], [0.3, 0.0, 0.7], 7.5,
                       steps=args.plms_steps)
+        last["latents"] = lat
         if vae is None:
             return lat
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -327,6 +357,7 @@ def main():
         img = vae.decode(lat)                      # fp32 [B, 3, 512, 512], what interface.py:541 hands to the PIL loop
         e1.record()
         vae_events.append((e0, e1))
+        last["images"] = img
         if scorer is not None:
             cap_ids, gt_u8, processor = score_in
             sp, s0, s1, s2 = (torch.cuda.Event(enable_timing=True) for _ in range(4))
@@ -342,6 +373,7 @@ def main():
             s2.record()
             score_events.append((sp, s0, s1, s2))
             assert sc["reward"].shape == (B,) and bool(torch.isfinite(sc["reward"]).all())
+            last.update(sc)
         return img
 
     def sync():
@@ -362,7 +394,7 @@ def main():
     sync()
     elapsed = time.time() - t1
     assert torch.isfinite(out).all(), "non-finite latents"
-    if scorer is not None:
+    if scorer is not None and args.full:
         # outside the timed region: the reference's host path (HF processor on the CPU) once on the last batch -- the GPU
         # pixel_values must equal it bitwise; its time is reported beside the GPU preprocessing time
         cap_ids, gt_u8, processor = score_in
@@ -378,6 +410,8 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     # ---- STRICT mode leg (second engine on the split weight layout, gl_set_handle_option 50; outside the headline's timed region): the same
     # denoise + decode on split-fp16 operands everywhere -- the mode whose output is within north_star's rtol 1e-3 / atol 1e-4 of the fp32
@@ -466,7 +500,7 @@ def main():
     # ---- the single hottest kernel shape, timed standalone with HIP events on the launch stream: the implicit-GEMM
     # 3x3 conv 320 -> 320 at the 64x64 level of the 2B batch (gemm8_kernel<256,160,true>, 7 launches per forward; that instantiation is
     # the top line of profiles/r3_kernel_stats.csv, where its average covers all conv shapes incl. the split-K ones)
-    if rank == 0 and side == 64 and not args.tiny and not args.no_hot_kernel:
+    if args.full and rank == 0 and side == 64 and not args.tiny and not args.no_hot_kernel:
         from layoutllm_t2i_amd import ops as _o
         Bn = 2 * B
         xa = torch.randn(Bn * side * side, 320, device=dev).to(torch.float16)
@@ -520,8 +554,8 @@ def main():
                              round(sum(a.elapsed_time(b) for a, b, c, d in score_events) / len(score_events), 3),
                              "clip_towers(text 16 + vision 2x16, HIP)": round(sum(b.elapsed_time(c) for a, b, c, d in score_events) / len(score_events), 3),
                              "similarities+aesthetic (gl_reward_score)": round(sum(c.elapsed_time(d) for a, b, c, d in score_events) / len(score_events), 3),
-                             "reference host path of the preprocessing (HF CLIP processor, PIL, CPU; once, outside the timed region)": round(reward_stage_ms["processor_cpu"][-1], 1),
-                             "gpu_pixel_values_equal_host_processor_bitwise": reward_stage_ms["preprocess_equal"][-1]}
+                             **({"reference host path of the preprocessing (HF CLIP processor, PIL, CPU; once, outside the timed region)": round(reward_stage_ms["processor_cpu"][-1], 1),
+                                 "gpu_pixel_values_equal_host_processor_bitwise": reward_stage_ms["preprocess_equal"][-1]} if reward_stage_ms["processor_cpu"] else {})}
                             if score_events else None),
         "reward_score_note": ("Reward_Model.forward's GPU part on the decoded images: uint8 + CLIP feature-extractor preprocessing (HIP) -> CLIP "
                               "ViT-L/14 towers (random-init, HIP) on 16 predictions + 16 ground-truth images + 16 captions -> similarities + "
@@ -529,7 +563,7 @@ def main():
         "roofline": roofline,
         "setup_s": round(setup_s, 1),
     }
-    if not args.tiny:
+    if args.full and not args.tiny:
         result["conditioning_encode"] = conditioning_encode_ms(dev, B, args.boxes, rank)
     if bcast_ms is not None:
         result["weight_broadcast_ms"] = round(bcast_ms, 1)

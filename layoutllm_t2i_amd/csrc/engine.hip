@@ -1380,7 +1380,7 @@ extern "C" int gl_plms_step(gl_engine* e, const gl_plms_step_args* a, void* stre
 
 extern "C" int gl_set_handle_option(gl_engine* e, int key, int value) {
     gl_opts probe{};
-    if (!e || key < 0 || key >= GL_OPT_MAX || !gl_opts_store(probe, key, value)) return GL_ERR_BAD_ARG;
+    if (!e || key < 0 || key >= GL_OPT_MAX || !gl_opts_put(probe, key, value)) return GL_ERR_BAD_ARG;
     e->ovr.mask |= (uint64_t)1 << key;
     e->ovr.v[key] = value;
     ++e->ovr.epoch;

@@ -316,7 +316,7 @@ gl_opts g_gl_opts = make_default_opts();
 thread_local const gl_opts* tl_gl_opts = nullptr;
 int g_gl_option_epoch = 0;
 
-bool gl_opts_store(gl_opts& t, int key, int value) {
+bool gl_opts_put(gl_opts& t, int key, int value) {
     switch (key) {
         case 2: case 3: case 4: case 6: case 7: case 8: case 10: case 13: case 17: case 20: case 21: case 23: case 24: case 25:
         case 27: case 29: case 30: case 31: case 32: case 33: case 35: case 37: case 38: case 41: case 42: case 43: case 44: case 45: case 46: case 47: case 50: case 51: case 52: case 53:
@@ -333,7 +333,7 @@ bool gl_opts_store(gl_opts& t, int key, int value) {
 }
 
 extern "C" int gl_set_option(int key, int value) {
-    if (key < 0 || key >= GL_OPT_MAX || !gl_opts_store(g_gl_opts, key, value)) return GL_ERR_BAD_ARG;
+    if (key < 0 || key >= GL_OPT_MAX || !gl_opts_put(g_gl_opts, key, value)) return GL_ERR_BAD_ARG;
     ++g_gl_option_epoch;
     return 0;
 }

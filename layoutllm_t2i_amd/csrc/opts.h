@@ -31,7 +31,7 @@ static inline int gl_opt(int key) {
 }
 
 // normalises (key, value) exactly like the process-level setter and stores it into `t`; false for an unknown key
-bool gl_opts_store(gl_opts& t, int key, int value);
+bool gl_opts_put(gl_opts& t, int key, int value);
 
 // RAII: a handle's entry point installs [defaults + its overrides] for the duration of the call
 struct gl_opts_scope {
@@ -40,7 +40,7 @@ struct gl_opts_scope {
     explicit gl_opts_scope(const gl_opt_overrides& o) : prev(tl_gl_opts) {
         eff = g_gl_opts;
         for (int k = 0; k < GL_OPT_MAX; ++k)
-            if ((o.mask >> k) & 1u) gl_opts_store(eff, k, o.v[k]);
+            if ((o.mask >> k) & 1u) gl_opts_put(eff, k, o.v[k]);
         tl_gl_opts = &eff;
     }
     ~gl_opts_scope() { tl_gl_opts = prev; }

@@ -389,7 +389,7 @@ extern "C" int gl_vae_decode(gl_vae* v, const float* z, int32_t B, int32_t side,
 
 extern "C" int gl_vae_set_option(gl_vae* v, int key, int value) {
     gl_opts probe{};
-    if (!v || key < 0 || key >= GL_OPT_MAX || !gl_opts_store(probe, key, value)) return GL_ERR_BAD_ARG;
+    if (!v || key < 0 || key >= GL_OPT_MAX || !gl_opts_put(probe, key, value)) return GL_ERR_BAD_ARG;
     v->ovr.mask |= (uint64_t)1 << key;
     v->ovr.v[key] = value;
     ++v->ovr.epoch;

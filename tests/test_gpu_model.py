@@ -343,7 +343,7 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--backend", "gloo", "--plms-steps", "5", "--no-cpu-baseline"]
+           "--backend", "gloo", "--plms-steps", "5", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -7,10 +7,10 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out
 mkdir -p $O
 (python -m pytest tests -m gpu -q 2>&1 | tail -4) > $O/${T}_final_gpu_tests.log 2>&1
-python bench.py > $O/${T}_final_bench.json 2> $O/${T}_final_bench.err
-python bench.py --config 3 --steps 2 --no-cpu-baseline > $O/${T}_final_bench_c3.json 2> $O/${T}_final_bench_c3.err
-python bench.py --config 5 --steps 2 --no-cpu-baseline > $O/${T}_final_bench_c5.json 2> $O/${T}_final_bench_c5.err
-python bench.py --strict-main --steps 2 --no-cpu-baseline > $O/${T}_final_bench_strict_main.json 2> $O/${T}_final_bench_strict_main.err
+python bench.py --full > $O/${T}_final_bench.json 2> $O/${T}_final_bench.err
+python bench.py --full --config 3 --steps 2 --no-cpu-baseline > $O/${T}_final_bench_c3.json 2> $O/${T}_final_bench_c3.err
+python bench.py --full --config 5 --steps 2 --no-cpu-baseline > $O/${T}_final_bench_c5.json 2> $O/${T}_final_bench_c5.err
+python bench.py --full --strict-main --steps 2 --no-cpu-baseline > $O/${T}_final_bench_strict_main.json 2> $O/${T}_final_bench_strict_main.err
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/${T}_final_smoke.log 2>&1
 bash tools/profile_round.sh $T > $O/${T}_final_profile.log 2>&1
 bash tools/profile_round.sh $T strict > $O/${T}_final_profile_strict.log 2>&1
