@@ -323,6 +323,20 @@ int gl_latent_affine_pack(const float* z, const float* w, const float* bias, flo
                           int32_t hw, int32_t Cpad, void* out, void* stream);
 int gl_softmax_rows(void* x, int32_t rows, int32_t n, int32_t ld, float scale, void* stream);
 
+/*
+ * VAE encode stage and masked PLMS sampling (GLIGEN inpainting: AutoencoderKL.encode autoencoder.py:34-38, plms.py:95-99).
+ *   gl_vae_posterior : h fp32 NCHW [B, Cin, hw] (Encoder.conv_out) -> quant_conv 1x1 in fp32 (w fp32 [2E, Cin], bias [2E]) -> mean, logvar =
+ *                      the two halves, logvar clamped to [-30, 20], z = (mean + exp(logvar / 2) * noise) * scale (distributions.py:24-36),
+ *                      z fp32 NCHW [B, E, hw]; mean (optional, may be NULL) receives the posterior mean.
+ *   gl_latent_blend  : in place on x fp32 [B, C, hw]: x = (a * x0 + s * noise) * m + (1 - m) * x (q_sample, ldm.py:19-22, then the blend),
+ *                      in torch's operation order with FP contraction off (bit-identical to the torch expression).  x0 and noise have
+ *                      x0_batch (1 or B) samples of [C, hw], the mask mask_batch (1 or B) samples of [1, hw].
+ */
+int gl_vae_posterior(const float* h, const float* w, const float* bias, const float* noise, float scale, int32_t B, int32_t Cin,
+                     int32_t E, int32_t hw, float* z, float* mean, void* stream);
+int gl_latent_blend(float* x, const float* x0, const float* noise, const float* mask, float a, float s, int32_t B, int32_t C,
+                    int32_t hw, int32_t x0_batch, int32_t mask_batch, void* stream);
+
 /* =====================================================================================================
  * Forward-level API ("what a C-ABI replacement must export underneath"): one handle per device per
  * thread owns the block plan, the packed weights' layout, the activation pool, the hoisted conditioning and the
@@ -422,6 +436,10 @@ int gl_sizeof_reward_args(void);
 
 int gl_gemm(const gl_gemm_args* a, void* stream);
 int gl_conv3x3(const gl_conv_args* a, void* stream);
+/* The VAE encoder's Downsample (model.py:60-79): F.pad(x, (0, 1, 0, 1)) then a 3x3 conv with stride 2 and pad 0, i.e. output (oy, ox)
+ * reads input rows 2oy .. 2oy+2 and columns 2ox .. 2ox+2 with zeros at row Hin / column Win.  Needs stride == 2, upsample2x == 0,
+ * in_split == 0 and Hout = Hin / 2, Wout = Win / 2 (GL_ERR_BAD_ARG otherwise); dispatched like gl_conv3x3. */
+int gl_conv3x3_pad01(const gl_conv_args* a, void* stream);
 int gl_attention(const gl_attn_args* a, void* stream);
 
 /*
@@ -455,6 +473,18 @@ int gl_vae_decode(gl_vae* v, const float* z, int32_t B, int32_t side, float* out
 int gl_vae_num_launches(const gl_vae* v);
 int64_t gl_vae_pool_bytes(const gl_vae* v);
 int gl_sizeof_vae_config(void);
+/*
+ * VAE encode stage on the same handle type: AutoencoderKL.encode (autoencoder.py:34-38) = Encoder.forward (model.py:368-459, no
+ * down-level attention), quant_conv and DiagonalGaussianDistribution.sample() * scale_factor.  gl_vae_encoder_create builds an
+ * ENCODER handle (plan and flat weight table need no GPU; encoder.* / quant_conv.* in the decoder's packed forms, image channels =
+ * out_ch, the 3x3 conv_in input zero-padded to 64 channels, quant_conv fp32).  gl_vae_encode maps x fp32 [B, out_ch, side, side]
+ * -> z fp32 [B, embed_dim, side / f, side / f], f = 2^(n_mult-1), with the caller's posterior noise fp32 [B, embed_dim, side / f,
+ * side / f]; side must be a multiple of f below 1024 (GL_ERR_BAD_ARG otherwise), one hipGraph per (B, side).  The
+ * weight-table / load / option / launch-count / pool / destroy entries above apply unchanged; gl_vae_decode on an encoder handle and
+ * gl_vae_encode on a decoder handle return GL_ERR_BAD_ARG.
+ */
+int gl_vae_encoder_create(const gl_vae_config* cfg, gl_vae** out);
+int gl_vae_encode(gl_vae* v, const float* x, int32_t B, int32_t side, const float* noise, float* z, int32_t use_graph, void* stream);
 
 /*
  * CLIP towers of the reward stage: transformers.CLIPModel.get_image_features / get_text_features as the

@@ -211,6 +211,11 @@ PROTOTYPES = {
     "gl_vae_num_launches": (i32, [vp]),
     "gl_vae_pool_bytes": (i64, [vp]),
     "gl_sizeof_vae_config": (i32, []),
+    "gl_vae_encoder_create": (i32, [C.POINTER(VaeConfigC), C.POINTER(vp)]),
+    "gl_vae_encode": (i32, [vp, fp, i32, i32, fp, fp, i32, vp]),
+    "gl_conv3x3_pad01": (i32, [C.POINTER(ConvArgs), vp]),
+    "gl_vae_posterior": (i32, [fp, fp, fp, fp, f32, i32, i32, i32, i32, fp, fp, vp]),
+    "gl_latent_blend": (i32, [fp, fp, fp, fp, f32, f32, i32, i32, i32, i32, i32, vp]),
     "gl_clip_patchify": (i32, [fp, i32, i32, i32, i32, vp, vp]),
     "gl_clip_assemble": (i32, [vp, i32, fp, fp, i32, i32, i32, fp, fp, f32, fp, vp]),
     "gl_clip_embed_tokens": (i32, [vp, fp, fp, i32, i32, i32, i32, fp, vp]),
@@ -296,15 +301,18 @@ def create_engine(cfg) -> int:
     return h.value
 
 
-def create_vae(cfg) -> int:
-    """gl_vae_create from an arch.VAEConfig: returns the opaque handle.  Needs no GPU."""
+def create_vae(cfg, encoder: bool = False) -> int:
+    """gl_vae_create (``encoder``: gl_vae_encoder_create) from an arch.VAEConfig: returns the opaque handle.  Needs no GPU."""
     cc = VaeConfigC()
     cc.ch, cc.n_mult, cc.num_res_blocks, cc.z_channels, cc.out_ch = cfg.ch, len(cfg.ch_mult), cfg.num_res_blocks, cfg.z_channels, cfg.out_ch
     for i, m in enumerate(cfg.ch_mult):
         cc.ch_mult[i] = int(m)
     cc.embed_dim, cc.scale_factor = cfg.embed_dim, float(cfg.scale_factor)
     h = vp()
-    check(lib().gl_vae_create(C.byref(cc), C.byref(h)), "gl_vae_create")
+    if encoder:
+        check(lib().gl_vae_encoder_create(C.byref(cc), C.byref(h)), "gl_vae_encoder_create")
+    else:
+        check(lib().gl_vae_create(C.byref(cc), C.byref(h)), "gl_vae_create")
     return h.value
 
 

@@ -336,3 +336,37 @@ def vae_decoder_param_shapes(cfg: VAEConfig) -> Dict[str, Tuple[int, ...]]:
     out.update(norm_params("decoder.norm_out", block_in))
     out.update(conv_params("decoder.conv_out", block_in, cfg.out_ch))
     return out
+
+
+def vae_encoder_param_shapes(cfg: VAEConfig) -> Dict[str, Tuple[int, ...]]:
+    """state_dict name -> shape of everything AutoencoderKL.encode touches (autoencoder.py:34-38, Encoder model.py:368-459 with
+    in_channels = out_ch, double_z and no down-level attention), in the reference's naming (encoder.*, quant_conv.*)."""
+    out: Dict[str, Tuple[int, ...]] = {}
+    out.update(conv_params("encoder.conv_in", cfg.out_ch, cfg.ch))
+    nres = len(cfg.ch_mult)
+    in_ch_mult = (1,) + tuple(cfg.ch_mult)
+    block_in = cfg.ch
+
+    def resnet(p, cin, cout):
+        out.update(norm_params(p + ".norm1", cin))
+        out.update(conv_params(p + ".conv1", cin, cout))
+        out.update(norm_params(p + ".norm2", cout))
+        out.update(conv_params(p + ".conv2", cout, cout))
+        if cin != cout:
+            out.update(conv_params(p + ".nin_shortcut", cin, cout, 1))
+    for lvl in range(nres):
+        block_in, block_out = cfg.ch * in_ch_mult[lvl], cfg.ch * cfg.ch_mult[lvl]
+        for i in range(cfg.num_res_blocks):
+            resnet(f"encoder.down.{lvl}.block.{i}", block_in, block_out)
+            block_in = block_out
+        if lvl != nres - 1:
+            out.update(conv_params(f"encoder.down.{lvl}.downsample.conv", block_in, block_in))
+    resnet("encoder.mid.block_1", block_in, block_in)
+    out.update(norm_params("encoder.mid.attn_1.norm", block_in))
+    for n in ("q", "k", "v", "proj_out"):
+        out.update(conv_params(f"encoder.mid.attn_1.{n}", block_in, block_in, 1))
+    resnet("encoder.mid.block_2", block_in, block_in)
+    out.update(norm_params("encoder.norm_out", block_in))
+    out.update(conv_params("encoder.conv_out", block_in, 2 * cfg.z_channels))
+    out.update(conv_params("quant_conv", 2 * cfg.z_channels, 2 * cfg.embed_dim, 1))
+    return out

@@ -181,7 +181,9 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
                 // Nearest-2x-upsampled input (openaimodel.py:82-84): the conv runs on the UPSAMPLED grid (bounds Hout x Wout), source pixel
                 // ((oy + dy) >> 1, (ox + dx) >> 1); relative to the centre's source pixel (oy >> 1, ox >> 1) that is a shift of
                 // ((dy + (oy & 1)) >> 1, (dx + (ox & 1)) >> 1) pixels -- per lane, from the two parity bits kept in cmask bits 9 / 10.
-                const int iy = cg.ups ? oy : oy * cg.stride, ix = cg.ups ? ox : ox * cg.stride;
+                // cg.shift: gl_conv3x3_pad01's tap window (one pixel down / right); it needs in_split == 0, so never the three-pass loop
+                const int sh = S3 ? 0 : cg.shift;
+                const int iy = cg.ups ? oy : oy * cg.stride + sh, ix = cg.ups ? ox : ox * cg.stride + sh;
                 const int hlim = cg.ups ? cg.Hout : cg.Hin, wlim = cg.ups ? cg.Wout : cg.Win;
                 const unsigned rb = (iy >= 1 ? 1u : 0u) | 2u | (iy + 1 < hlim ? 4u : 0u);
                 const unsigned cb = (ix >= 1 ? 1u : 0u) | 2u | (ix + 1 < wlim ? 4u : 0u);

@@ -167,11 +167,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * WK, (min_waves<BM, BN, BKT
                     unsigned mk = 0u;
 #pragma unroll
                     for (int t = 0; t < 9; ++t) {
-                        const int iy = oy * cg.stride + t / 3 - 1, ix = ox * cg.stride + t % 3 - 1;
+                        const int iy = oy * cg.stride + cg.shift + t / 3 - 1, ix = ox * cg.stride + cg.shift + t % 3 - 1;
                         if (iy >= 0 && iy < cg.Hin && ix >= 0 && ix < cg.Win) mk |= 1u << t;
                     }
                     cmask[i] = mk;
-                    aptr[i] = cg.in + ((size_t)(b * cg.Hin + oy * cg.stride) * cg.Win + ox * cg.stride) * cg.Cin + gc;
+                    aptr[i] = cg.in + ((size_t)(b * cg.Hin + oy * cg.stride + cg.shift) * cg.Win + ox * cg.stride + cg.shift) * cg.Cin + gc;
                 }
             }
         } else {
@@ -905,7 +905,8 @@ extern "C" int gl_gemm(const gl_gemm_args* a, void* stream) {
     return dispatch<false>(g, cg, (hipStream_t)stream);
 }
 
-extern "C" int gl_conv3x3(const gl_conv_args* a, void* stream) {
+namespace {
+int conv3x3_entry(const gl_conv_args* a, int shift, void* stream) {
     if (!a || !a->in || !a->g.w || !a->g.out) return GL_ERR_BAD_ARG;
     if ((a->Cin % 64) != 0) return GL_ERR_BAD_ARG;
     if (a->stride != 1 && a->stride != 2) return GL_ERR_BAD_ARG;
@@ -922,8 +923,19 @@ extern "C" int gl_conv3x3(const gl_conv_args* a, void* stream) {
     g.ldw = 9 * a->Cin * (a->w_split ? 2 : 1);
     g.kwrap = a->in_split ? 9 * a->Cin : 0;
     ConvGeom cg{reinterpret_cast<const half_t*>(a->in), a->B, a->Hin, a->Win, a->Cin * (a->in_split ? 2 : 1), a->Hout, a->Wout, a->stride,
-                a->upsample2x, nullptr, a->in_split == 3 ? 2 * (a->Cin >> 6) : 0};
+                a->upsample2x, nullptr, a->in_split == 3 ? 2 * (a->Cin >> 6) : 0, shift};
     return dispatch<true>(g, cg, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int gl_conv3x3(const gl_conv_args* a, void* stream) { return conv3x3_entry(a, 0, stream); }
+
+// VAE encoder Downsample (model.py:60-79): F.pad(x, (0, 1, 0, 1)) then a stride-2 pad-0 3x3 conv = the stride-2 conv with its tap
+// window moved one pixel down and right; the padded row / column (index Hin / Win) is zero through the same validity masks
+extern "C" int gl_conv3x3_pad01(const gl_conv_args* a, void* stream) {
+    if (!a || a->stride != 2 || a->upsample2x != 0 || a->in_split != 0) return GL_ERR_BAD_ARG;
+    if (a->Hout != a->Hin / 2 || a->Wout != a->Win / 2 || a->Hout <= 0 || a->Wout <= 0) return GL_ERR_BAD_ARG;
+    return conv3x3_entry(a, 1, stream);
 }
 
 template <int BM, int BN, int WM, int WN, bool CONV, int BKT, int WK = 1>

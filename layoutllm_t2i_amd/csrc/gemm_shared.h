@@ -15,6 +15,8 @@ struct ConvGeom {
     int cwrap;                 // split-fp16 input with a third pass (gl_conv_args.in_split == 3): channel blocks >= cwrap read the input's block
                                // (cblk - cwrap), i.e. the K walk [hi | lo | hi] over pixel rows that hold [hi | lo]; 0 = no wrap.  Cin above is the
                                // pixel ROW STRIDE in channels (2 x the conv's channels for a split input); the channel blocks walked are K / 576
+    int shift;                 // tap-window centre offset in input pixels (both axes): 0 = pad 1 (input (oy*s + ky - 1, ox*s + kx - 1));
+                               // 1 = the VAE encoder's Downsample, F.pad(x, (0, 1, 0, 1)) + pad-0 conv (input (oy*s + ky, ox*s + kx))
 };
 
 namespace {

@@ -103,7 +103,70 @@ __global__ void plms_update_kernel(const float* x, const float* e, const float* 
         x_prev[i] = sqrt_aprev * pred_x0 + dir_xt;
     }
 }
+
+// Masked PLMS step (plms.py:95-99 with ldm.py:19-22): x = (a * x0 + s * noise) * m + (1 - m) * x, in place, in torch's operation order
+// (q_sample's two products and their sum, then img_orig * mask, (1 - mask) * img and the sum).  x0 / noise have batch 1 or B (nb0), the
+// mask [1|B, 1, hw] (nbm).  VEC = 4: hw % 4 == 0, one float4 of one (b, c) row per thread.
+template <int VEC>
+__global__ __launch_bounds__(256) void latent_blend_kernel(float* x, const float* __restrict__ x0, const float* __restrict__ noise,
+                                                           const float* __restrict__ m, float a, float s, int B, int C, int hw, int nb0,
+                                                           int nbm) {
+    const size_t nvec = (size_t)B * C * hw / VEC;
+    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = v * VEC;
+        const int p = (int)(i % hw);
+        const size_t bc = i / hw;
+        const int c = (int)(bc % C), b = (int)(bc / C);
+        const size_t i0 = ((size_t)(nb0 == 1 ? 0 : b) * C + c) * hw + p;
+        const size_t im = (size_t)(nbm == 1 ? 0 : b) * hw + p;
+        float xv[VEC], x0v[VEC], nv[VEC], mv[VEC];
+        if constexpr (VEC == 4) {
+            const float4 t = *reinterpret_cast<const float4*>(x + i), t0 = *reinterpret_cast<const float4*>(x0 + i0),
+                         tn = *reinterpret_cast<const float4*>(noise + i0), tm = *reinterpret_cast<const float4*>(m + im);
+            xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
+            x0v[0] = t0.x; x0v[1] = t0.y; x0v[2] = t0.z; x0v[3] = t0.w;
+            nv[0] = tn.x; nv[1] = tn.y; nv[2] = tn.z; nv[3] = tn.w;
+            mv[0] = tm.x; mv[1] = tm.y; mv[2] = tm.z; mv[3] = tm.w;
+        } else {
+            xv[0] = x[i]; x0v[0] = x0[i0]; nv[0] = noise[i0]; mv[0] = m[im];
+        }
+        float o[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            const float q = a * x0v[j] + s * nv[j];
+            o[j] = q * mv[j] + (1.0f - mv[j]) * xv[j];
+        }
+        if constexpr (VEC == 4) *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
+        else x[i] = o[0];
+    }
+}
 #pragma clang fp contract(fast)
+
+// DiagonalGaussianDistribution(quant_conv(h)).sample() * scale_factor (autoencoder.py:34-38, distributions.py:24-36) per pixel:
+// moments = W h + b (fp32 1x1 conv, 2E x Cin), mean / logvar = the two halves, logvar clamped to [-30, 20], std = exp(logvar / 2),
+// z = (mean + std * noise) * scale.  h fp32 NCHW [B, Cin, hw]; z / mean fp32 NCHW [B, E, hw].  One thread per pixel.
+__global__ __launch_bounds__(256) void vae_posterior_kernel(const float* __restrict__ h, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, const float* __restrict__ noise, float scale,
+                                                            int B, int Cin, int E, int hw, float* __restrict__ z, float* __restrict__ mean) {
+    const size_t n = (size_t)B * hw;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int b = (int)(i / hw), p = (int)(i % hw);
+        const float* hp = h + (size_t)b * Cin * hw + p;
+        for (int e = 0; e < E; ++e) {
+            float mu = bias[e], lv = bias[E + e];
+            for (int k = 0; k < Cin; ++k) {
+                const float hv = hp[(size_t)k * hw];
+                mu += w[(size_t)e * Cin + k] * hv;
+                lv += w[(size_t)(E + e) * Cin + k] * hv;
+            }
+            lv = fminf(fmaxf(lv, -30.0f), 20.0f);
+            const float sd = expf(0.5f * lv);
+            const size_t o = ((size_t)b * E + e) * hw + p;
+            z[o] = (mu + sd * noise[o]) * scale;
+            if (mean) mean[o] = mu;
+        }
+    }
+}
 
 // x fp32 [B, C, hw] -> fp16 [reps*B, hw, Cpad].  split: channels [0, C) = hi = fp16(x), [C, 2C) = lo = fp16(x - hi), [2C, 3C) = hi again -- against
 // first-conv weights packed [Whi | Whi | Wlo] (weights.py pack_first_conv) the one conv launch computes xhi.Whi + xlo.Whi + xhi.Wlo in the channel
@@ -267,6 +330,29 @@ extern "C" int gl_pack_latent(const float* x, int32_t B, int32_t C, int32_t hw, 
     if (!x || !out || B <= 0 || C <= 0 || hw <= 0 || Cpad < (split ? 3 * C : C) || reps <= 0) return GL_ERR_BAD_ARG;
     pack_latent_kernel<<<dim3(ew_blocks((size_t)reps * B * hw * Cpad)), dim3(256), 0, (hipStream_t)stream>>>(
         x, B, C, hw, Cpad, reps, split, reinterpret_cast<half_t*>(out));
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_latent_blend(float* x, const float* x0, const float* noise, const float* mask, float a, float s, int32_t B, int32_t C,
+                               int32_t hw, int32_t x0_batch, int32_t mask_batch, void* stream) {
+    if (!x || !x0 || !noise || !mask || B <= 0 || C <= 0 || hw <= 0) return GL_ERR_BAD_ARG;
+    if ((x0_batch != 1 && x0_batch != B) || (mask_batch != 1 && mask_batch != B)) return GL_ERR_BAD_ARG;
+    const size_t n = (size_t)B * C * hw;
+    const bool vec = (hw % 4) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(noise) |
+                                        reinterpret_cast<uintptr_t>(mask)) % 16) == 0;
+    if (vec)
+        latent_blend_kernel<4><<<dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream>>>(x, x0, noise, mask, a, s, B, C, hw, x0_batch, mask_batch);
+    else
+        latent_blend_kernel<1><<<dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream>>>(x, x0, noise, mask, a, s, B, C, hw, x0_batch, mask_batch);
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_vae_posterior(const float* h, const float* w, const float* bias, const float* noise, float scale, int32_t B, int32_t Cin,
+                                int32_t E, int32_t hw, float* z, float* mean, void* stream) {
+    if (!h || !w || !bias || !noise || !z || B <= 0 || Cin <= 0 || E <= 0 || hw <= 0) return GL_ERR_BAD_ARG;
+    vae_posterior_kernel<<<dim3(ew_blocks((size_t)B * hw)), dim3(256), 0, (hipStream_t)stream>>>(h, w, bias, noise, scale, B, Cin, E, hw, z, mean);
     GL_CHECK_LAUNCH();
     return 0;
 }

@@ -9,6 +9,11 @@
 // addresses and one hipGraph per (batch, latent side), captured on an engine-owned stream and replayed on the caller's.
 // No new heavy kernels: every conv / 1x1 conv / GroupNorm goes through gl_conv3x3 / gl_gemm / gl_groupnorm (and therefore
 // through the 8-wave deep-pipelined kernel wherever its dispatch applies).
+//
+// The same handle type also runs the ENCODE stage (gl_vae_encoder_create / gl_vae_encode): AutoencoderKL.encode
+// (autoencoder.py:34-38) = Encoder.forward (model.py:368-459) -> quant_conv -> DiagonalGaussianDistribution.sample() * scale_factor,
+// with the decoder's helpers (resnet, GroupNorm, conv, mid attention, pool, graphs); the two encoder-only pieces are the
+// asymmetrically padded stride-2 Downsample (gl_conv3x3_pad01) and the posterior (gl_vae_posterior).
 #include "common.h"
 #include "gligen_hip.h"
 #include "opts.h"
@@ -44,6 +49,7 @@ struct gl_vae {
     int opt_epoch = 0;
     int ovr_epoch = 0;
     gl_opt_overrides ovr;              // per-handle option overrides (gl_vae_set_option)
+    bool encoder = false;              // gl_vae_encoder_create: encode-stage plan (gl_vae_encode), else decode-stage (gl_vae_decode)
 
     void add(const std::string& n, int dtype, std::initializer_list<int64_t> shp) {
         VW w{};
@@ -126,15 +132,16 @@ int v_gn(VRun& r, const half_t* x, int C, int HW, const std::string& p, bool sil
     return 0;
 }
 
+// down != 0: the encoder's Downsample (F.pad(x, (0, 1, 0, 1)) + stride-2 pad-0 conv, gl_conv3x3_pad01), side -> side / 2
 int v_conv(VRun& r, const half_t* x, int side, int cin, const std::string& p, int cout, int up, int epi, const void* res, void* out,
-           int out_mode = GL_OUT_F16_ROWMAJOR) {
+           int out_mode = GL_OUT_F16_ROWMAJOR, int down = 0) {
     gl_vae* v = r.v;
     gl_conv_args a;
     memset(&a, 0, sizeof(a));
     a.in = x;
     a.B = r.B; a.Hin = side; a.Win = side; a.Cin = cin;
-    a.Hout = up ? 2 * side : side; a.Wout = a.Hout;
-    a.stride = 1; a.upsample2x = up;
+    a.Hout = up ? 2 * side : (down ? side / 2 : side); a.Wout = a.Hout;
+    a.stride = down ? 2 : 1; a.upsample2x = up;
     a.g.w = v->W<half_t>(p + ".w");
     a.g.bias = v->W<float>(p + ".b");
     a.g.N = cout;
@@ -147,7 +154,7 @@ int v_conv(VRun& r, const half_t* x, int side, int cin, const std::string& p, in
     float* ws = v->f32("ws", (size_t)(96ll << 20) / 4);
     VCKP(ws);
     a.g.workspace = ws; a.g.workspace_bytes = 96ll << 20;
-    VCK(gl_conv3x3(&a, r.st));
+    VCK(down ? gl_conv3x3_pad01(&a, r.st) : gl_conv3x3(&a, r.st));
     r.count();
     return 0;
 }
@@ -269,6 +276,93 @@ int launch_decode(gl_vae* v, int B, int side, hipStream_t st, int* launches) {
     return 0;
 }
 
+// Encoder.forward (model.py:428-459) + quant_conv + posterior sample: x fp32 NCHW image ("in.x") -> z fp32 NCHW ("out.z")
+int launch_encode(gl_vae* v, int B, int side, hipStream_t st, int* launches) {
+    const gl_vae_config& c = v->cfg;
+    VRun r{v, st, B, launches};
+    if (launches) *launches = 0;
+    const int nres = c.n_mult;
+    const float* x = v->f32("in.x", (size_t)B * c.out_ch * side * side);
+    half_t* xin = v->f16("in", (size_t)B * side * side * VCIN_PAD);
+    VCKP(x); VCKP(xin);
+    VCK(gl_pack_latent(x, B, c.out_ch, side * side, VCIN_PAD, 1, 0, xin, st));
+    r.count();
+    int ch = c.ch;
+    half_t* h = v->f16("conv_in", (size_t)B * side * side * ch);
+    VCKP(h);
+    VCK(v_conv(r, xin, side, VCIN_PAD, "encoder.conv_in", ch, 0, GL_EPI_BIAS, nullptr, h));
+    for (int lvl = 0; lvl < nres; ++lvl) {
+        const int cout = c.ch * c.ch_mult[lvl];
+        for (int i = 0; i < c.num_res_blocks; ++i) {
+            VCK(v_resnet(r, "encoder.down." + std::to_string(lvl) + ".block." + std::to_string(i), h, side, ch, cout,
+                         "down." + std::to_string(lvl) + "." + std::to_string(i), &h));
+            ch = cout;
+        }
+        if (lvl != nres - 1) {
+            half_t* d = v->f16("down." + std::to_string(lvl) + ".d", (size_t)B * (side / 2) * (side / 2) * ch);
+            VCKP(d);
+            VCK(v_conv(r, h, side, ch, "encoder.down." + std::to_string(lvl) + ".downsample.conv", ch, 0, GL_EPI_BIAS, nullptr, d,
+                       GL_OUT_F16_ROWMAJOR, 1));
+            h = d;
+            side /= 2;
+        }
+    }
+    VCK(v_resnet(r, "encoder.mid.block_1", h, side, ch, ch, "mid.1", &h));
+    VCK(v_attn(r, "encoder.mid.attn_1", h, side, ch, "mid.a", &h));
+    VCK(v_resnet(r, "encoder.mid.block_2", h, side, ch, ch, "mid.2", &h));
+    half_t* g;
+    VCK(v_gn(r, h, ch, side * side, "encoder.norm_out", true, "fin.gn", &g));
+    const int hw = side * side, zc2 = 2 * c.z_channels;
+    float* mom = v->f32("enc.h", (size_t)B * zc2 * hw);
+    float* noise = v->f32("in.noise", (size_t)B * c.embed_dim * hw);
+    float* z = v->f32("out.z", (size_t)B * c.embed_dim * hw);
+    VCKP(mom); VCKP(noise); VCKP(z);
+    VCK(v_conv(r, g, side, ch, "encoder.conv_out", zc2, 0, GL_EPI_BIAS, nullptr, mom, GL_OUT_F32_NCHW));
+    VCK(gl_vae_posterior(mom, v->W<float>("quant_conv.w"), v->W<float>("quant_conv.b"), noise, c.scale_factor, B, zc2, c.embed_dim, hw, z,
+                         nullptr, st));
+    r.count();
+    return 0;
+}
+
+// Shared by gl_vae_decode / gl_vae_encode once the inputs sit in the pool: eager launch, or one hipGraph per (B, side) (warm-up run
+// that allocates every pooled buffer and produces this call's result, then capture; replay afterwards).
+template <typename Launch>
+int run_plan(gl_vae* v, int B, int side, int use_graph, hipStream_t st, Launch launch) {
+    if (v->opt_epoch != g_gl_option_epoch || v->ovr_epoch != v->ovr.epoch) {
+        v->drop_graphs();
+        v->opt_epoch = g_gl_option_epoch;
+        v->ovr_epoch = v->ovr.epoch;
+    }
+    const auto key = std::make_pair((int)B, (int)side);
+    auto it = v->graphs.find(key);
+    if (use_graph && it == v->graphs.end()) {
+        VCK(launch(st, &v->launches));        // warm-up: allocates every pooled buffer
+        if (hipStreamSynchronize(st) != hipSuccess) return GL_ERR_BAD_ARG;
+        if (v->pool_changed) { v->drop_graphs(); v->pool_changed = false; }
+        if (v->cap_stream == nullptr && hipStreamCreateWithFlags(&v->cap_stream, hipStreamNonBlocking) != hipSuccess) return GL_ERR_UNSUPPORTED;
+        hipGraph_t graph = nullptr;
+        if (hipStreamBeginCapture(v->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return GL_ERR_UNSUPPORTED;
+        const int rc = launch(v->cap_stream, nullptr);
+        const hipError_t ec = hipStreamEndCapture(v->cap_stream, &graph);
+        if (rc != 0 || ec != hipSuccess || graph == nullptr) {
+            if (graph) (void)hipGraphDestroy(graph);
+            return rc != 0 ? rc : GL_ERR_UNSUPPORTED;
+        }
+        hipGraphExec_t exec = nullptr;
+        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ei != hipSuccess) return GL_ERR_UNSUPPORTED;
+        v->graphs[key] = exec;
+        // the warm-up run already produced this call's result
+    } else if (use_graph) {
+        if (hipGraphLaunch(it->second, st) != hipSuccess) return GL_ERR_BAD_ARG;
+    } else {
+        VCK(launch(st, &v->launches));
+        if (v->pool_changed) { v->drop_graphs(); v->pool_changed = false; }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int gl_vae_create(const gl_vae_config* cfg, gl_vae** out) {
@@ -306,6 +400,65 @@ extern "C" int gl_vae_create(const gl_vae_config* cfg, gl_vae** out) {
     return 0;
 }
 
+extern "C" int gl_vae_encoder_create(const gl_vae_config* cfg, gl_vae** out) {
+    if (!cfg || !out || cfg->n_mult < 1 || cfg->n_mult > 8 || cfg->ch <= 0 || (cfg->ch % 64) || cfg->num_res_blocks < 0 || cfg->z_channels <= 0 ||
+        cfg->out_ch <= 0 || cfg->out_ch > VCIN_PAD || cfg->embed_dim <= 0 || cfg->scale_factor == 0.0f)
+        return GL_ERR_BAD_ARG;
+    for (int l = 0; l < cfg->n_mult; ++l)
+        if (cfg->ch_mult[l] <= 0) return GL_ERR_BAD_ARG;
+    gl_vae* v = new gl_vae();
+    v->cfg = *cfg;
+    v->encoder = true;
+    const int nres = cfg->n_mult;
+    int ch = cfg->ch;
+    v->add("encoder.conv_in.w", 0, {ch, 9 * (int64_t)VCIN_PAD});
+    v->add("encoder.conv_in.b", 1, {ch});
+    for (int lvl = 0; lvl < nres; ++lvl) {
+        const int cout = cfg->ch * cfg->ch_mult[lvl];
+        for (int i = 0; i < cfg->num_res_blocks; ++i) {
+            plan_resnet(v, "encoder.down." + std::to_string(lvl) + ".block." + std::to_string(i), ch, cout);
+            ch = cout;
+        }
+        if (lvl != nres - 1) {
+            v->add("encoder.down." + std::to_string(lvl) + ".downsample.conv.w", 0, {ch, 9 * (int64_t)ch});
+            v->add("encoder.down." + std::to_string(lvl) + ".downsample.conv.b", 1, {ch});
+        }
+    }
+    plan_resnet(v, "encoder.mid.block_1", ch, ch);
+    const std::string ap = "encoder.mid.attn_1";
+    v->add(ap + ".norm.g", 1, {ch}); v->add(ap + ".norm.b", 1, {ch});
+    for (const char* n : {"q", "k", "v", "proj_out"}) { v->add(ap + "." + n + ".w", 0, {ch, ch}); v->add(ap + "." + n + ".b", 1, {ch}); }
+    plan_resnet(v, "encoder.mid.block_2", ch, ch);
+    v->add("encoder.norm_out.g", 1, {ch}); v->add("encoder.norm_out.b", 1, {ch});
+    v->add("encoder.conv_out.w", 0, {2 * cfg->z_channels, 9 * (int64_t)ch});
+    v->add("encoder.conv_out.b", 1, {2 * cfg->z_channels});
+    v->add("quant_conv.w", 1, {2 * cfg->embed_dim, 2 * cfg->z_channels});
+    v->add("quant_conv.b", 1, {2 * cfg->embed_dim});
+    *out = v;
+    return 0;
+}
+
+extern "C" int gl_vae_encode(gl_vae* v, const float* x, int32_t B, int32_t side, const float* noise, float* z, int32_t use_graph, void* stream) {
+    if (!v || !x || !noise || !z || B <= 0 || B >= 2048 || side <= 0 || side >= 1024 || !v->wbase || !v->encoder) return GL_ERR_BAD_ARG;
+    const gl_vae_config& c = v->cfg;
+    const int f = 1 << (c.n_mult - 1);
+    if (side % f) return GL_ERR_BAD_ARG;
+    gl_opts_scope opts_scope(v->ovr);
+    hipStream_t st = (hipStream_t)stream;
+    const int zs = side / f;
+    const size_t nx = (size_t)B * c.out_ch * side * side, nz = (size_t)B * c.embed_dim * zs * zs;
+    v->pool_changed = false;
+    float* xin = v->f32("in.x", nx);
+    float* nin = v->f32("in.noise", nz);
+    float* zbuf = v->f32("out.z", nz);
+    VCKP(xin); VCKP(nin); VCKP(zbuf);
+    if (hipMemcpyAsync(xin, x, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
+    if (hipMemcpyAsync(nin, noise, nz * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
+    VCK(run_plan(v, B, side, use_graph, st, [&](hipStream_t s, int* nl) { return launch_encode(v, B, side, s, nl); }));
+    if (hipMemcpyAsync(z, zbuf, nz * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
+    return 0;
+}
+
 extern "C" int gl_vae_destroy(gl_vae* v) {
     if (!v) return GL_ERR_BAD_ARG;
     v->drop_graphs();
@@ -338,7 +491,7 @@ extern "C" int gl_vae_load_weights(gl_vae* v, const void* packed, int64_t bytes,
 }
 
 extern "C" int gl_vae_decode(gl_vae* v, const float* z, int32_t B, int32_t side, float* out, int32_t use_graph, void* stream) {
-    if (!v || !z || !out || B <= 0 || side <= 0 || !v->wbase) return GL_ERR_BAD_ARG;
+    if (!v || !z || !out || B <= 0 || side <= 0 || !v->wbase || v->encoder) return GL_ERR_BAD_ARG;
     gl_opts_scope opts_scope(v->ovr);
     const gl_vae_config& c = v->cfg;
     hipStream_t st = (hipStream_t)stream;
@@ -351,38 +504,7 @@ extern "C" int gl_vae_decode(gl_vae* v, const float* z, int32_t B, int32_t side,
     float* obuf = v->f32("out", no);
     VCKP(zin); VCKP(obuf);
     if (hipMemcpyAsync(zin, z, nz * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
-    if (v->opt_epoch != g_gl_option_epoch || v->ovr_epoch != v->ovr.epoch) {
-        v->drop_graphs();
-        v->opt_epoch = g_gl_option_epoch;
-        v->ovr_epoch = v->ovr.epoch;
-    }
-    const auto key = std::make_pair((int)B, (int)side);
-    auto it = v->graphs.find(key);
-    if (use_graph && it == v->graphs.end()) {
-        VCK(launch_decode(v, B, side, st, &v->launches));        // warm-up: allocates every pooled buffer
-        if (hipStreamSynchronize(st) != hipSuccess) return GL_ERR_BAD_ARG;
-        if (v->pool_changed) { v->drop_graphs(); v->pool_changed = false; }
-        if (v->cap_stream == nullptr && hipStreamCreateWithFlags(&v->cap_stream, hipStreamNonBlocking) != hipSuccess) return GL_ERR_UNSUPPORTED;
-        hipGraph_t graph = nullptr;
-        if (hipStreamBeginCapture(v->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return GL_ERR_UNSUPPORTED;
-        const int rc = launch_decode(v, B, side, v->cap_stream, nullptr);
-        const hipError_t ec = hipStreamEndCapture(v->cap_stream, &graph);
-        if (rc != 0 || ec != hipSuccess || graph == nullptr) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc != 0 ? rc : GL_ERR_UNSUPPORTED;
-        }
-        hipGraphExec_t exec = nullptr;
-        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ei != hipSuccess) return GL_ERR_UNSUPPORTED;
-        v->graphs[key] = exec;
-        // the warm-up run already produced this call's result
-    } else if (use_graph) {
-        if (hipGraphLaunch(it->second, st) != hipSuccess) return GL_ERR_BAD_ARG;
-    } else {
-        VCK(launch_decode(v, B, side, st, &v->launches));
-        if (v->pool_changed) { v->drop_graphs(); v->pool_changed = false; }
-    }
+    VCK(run_plan(v, B, side, use_graph, st, [&](hipStream_t s, int* nl) { return launch_decode(v, B, side, s, nl); }));
     if (hipMemcpyAsync(out, obuf, no * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
     return 0;
 }

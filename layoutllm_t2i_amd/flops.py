@@ -6,7 +6,7 @@ Counted as the REFERENCE executes it (openaimodel.py:413-459): PositionNet, fuse
 projections are per-forward work there (this build hoists them; they are <0.2 % of the total)."""
 from __future__ import annotations
 
-from .arch import UNetConfig, build_plan
+from .arch import UNetConfig, VAEConfig, build_plan
 
 
 def unet_forward_flops(cfg: UNetConfig, hw: int, fuser_on: bool = True, n_ctx: int = 77, n_rel: int = 10) -> float:
@@ -63,3 +63,29 @@ def unet_forward_flops(cfg: UNetConfig, hw: int, fuser_on: bool = True, n_ctx: i
                 side *= 2
     f += lin(side * side, 9 * plan.out_channels_last, cfg.out_channels)
     return f
+
+
+def vae_encoder_flops(cfg: VAEConfig, B: int, side: int) -> float:
+    """AutoencoderKL.encode of B images of side x side (Encoder model.py:428-459 + quant_conv), 2 x MACs of every conv / 1x1 /
+    attention product: 1.1 TFLOP per 512x512 image at the real config."""
+    lin = lambda m, k, n: 2.0 * m * k * n
+    f = 0.0
+    ch = cfg.ch
+    f += lin(side * side, 9 * cfg.out_ch, ch)                   # conv_in
+
+    def resnet(n, cin, cout):
+        g = lin(n, 9 * cin, cout) + lin(n, 9 * cout, cout)
+        return g + (lin(n, cin, cout) if cin != cout else 0.0)
+    nres = len(cfg.ch_mult)
+    for lvl in range(nres):
+        cout = cfg.ch * cfg.ch_mult[lvl]
+        for _ in range(cfg.num_res_blocks):
+            f += resnet(side * side, ch, cout)
+            ch = cout
+        if lvl != nres - 1:
+            side //= 2
+            f += lin(side * side, 9 * ch, ch)                   # pad01 downsample
+    n = side * side
+    f += 2 * resnet(n, ch, ch) + 4 * lin(n, ch, ch) + 2.0 * 2.0 * n * n * ch     # mid: 2 ResnetBlocks, q / k / v / proj_out, QK^T + PV
+    f += lin(n, 9 * ch, 2 * cfg.z_channels) + lin(n, 2 * cfg.z_channels, 2 * cfg.embed_dim)
+    return B * f

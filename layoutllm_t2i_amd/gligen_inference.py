@@ -11,6 +11,11 @@ App-B#9), so only its entry-point name and argument meaning are kept; semantics 
 ``alpha_type``, ``save_folder_name``; ``config``: object/dict with ``batch_size``, ``guidance_scale``,
 ``no_plms`` (must be False), optional ``folder``.  Images are saved like the reference does
 (gligen_inference.py:437-446) when ``config.folder`` is given.
+
+``meta["input_image"]`` (a path or a PIL.Image) inpaints that image inside the layout boxes (gligen_inference.py:393-407): it is
+encoded by the checkpoint's VAE encoder, the mask is 0 inside the boxes, and the PLMS sampler replaces the known region of the
+latent at every step.  The reference asserts a 9-channel ``inpaint_mode`` checkpoint at this point; this package keeps rejecting
+those and runs this latent-blend inpainting on the 4-channel text_layout model instead.
 """
 from __future__ import annotations
 
@@ -42,7 +47,7 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     bs = _get(config, "batch_size", 1)
     args = dict(batch_size=bs, no_plms=bool(_get(config, "no_plms", False)), guidance_scale=_get(config, "guidance_scale", 7.5))
     m = dict(prompt=meta["prompt"], phrases=meta.get("phrases"), locations=meta["locations"],
-             alpha_type=meta.get("alpha_type", [0.3, 0.0, 0.7]))
+             alpha_type=meta.get("alpha_type", [0.3, 0.0, 0.7]), input_image=meta.get("input_image"))
     if starting_noise is None:
         starting_noise = torch.randn(bs, 4, 64, 64).to(device)
     if clip_model is None or clip_processor is None:

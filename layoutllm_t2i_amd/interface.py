@@ -159,7 +159,7 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
         autoencoder = _instantiate_reference(config["autoencoder"]).to(device).eval()
         autoencoder.load_state_dict(saved_ckpt["autoencoder"])
     else:
-        # decode stage on the HIP kernels; only `.decode(z)` is used on this path (interface.py:541)
+        # decode stage on the HIP kernels, plus `.encode(x)` for inpainting when the checkpoint holds the encoder
         ap = config["autoencoder"].get("params", {})
         dd = ap.get("ddconfig", {})
         vcfg = VAEConfig(ch=dd.get("ch", 128), ch_mult=tuple(dd.get("ch_mult", (1, 2, 4, 4))),
@@ -348,11 +348,27 @@ def _postprocess(samples):
     return out
 
 
+def _vae_factor(autoencoder) -> int:
+    cfg = getattr(autoencoder, "cfg", None)
+    return 2 ** (len(cfg.ch_mult) - 1) if cfg is not None else 8
+
+
+def load_input_image(image, side: int, device=None) -> torch.Tensor:
+    """gligen_inference.py:400-401 at any size: ``Image.open(path).convert("RGB").resize((side, side))`` (or that of a
+    ``PIL.Image``), pil_to_tensor, then ``(x / 255 - 0.5) / 0.5`` in fp32 on ``device`` -> [1, 3, side, side]."""
+    from PIL import Image
+    im = image if isinstance(image, Image.Image) else Image.open(image)
+    im = im.convert("RGB").resize((side, side))
+    x = torch.from_numpy(np.array(im, dtype=np.uint8)).permute(2, 0, 1).contiguous()       # torchvision pil_to_tensor
+    return (x.float().unsqueeze(0).to(device) / 255 - 0.5) / 0.5
+
+
 @torch.no_grad()
 def denoise(all_models, context, uc, relations, grounding_batch, starting_noise, alpha_type=None, guidance_scale=7.5,
-            steps=PLMS_STEPS):
+            steps=PLMS_STEPS, mask=None, x0=None):
     """The denoising hot path proper, from conditioning tensors to the final latent
-    (run_batch_images lines interface.py:505-539 without text/VAE stages)."""
+    (run_batch_images lines interface.py:505-539 without text/VAE stages).  ``mask`` [1|B, 1, L, L] (1 = keep) and ``x0``
+    [1|B, 4, L, L] (the encoded input image): inpainting, plms.py:95-99."""
     model, autoencoder, text_encoder, diffusion, config = all_models
     sampler = PLMSSampler(diffusion, model, alpha_generator_func=partial(alpha_generator, type=alpha_type),
                           set_alpha_scale=set_alpha_scale)
@@ -360,7 +376,7 @@ def denoise(all_models, context, uc, relations, grounding_batch, starting_noise,
     input = dict(x=starting_noise, timesteps=None, context=context, relations=relations, grounding_input=grounding_input,
                  inpainting_extra_input=None, grounding_extra_input=None)
     shape = tuple(starting_noise.shape)
-    return sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=None, x0=None)
+    return sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=mask, x0=x0)
 
 
 def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple):
@@ -380,21 +396,35 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
         context = text_encoder.encode([meta["prompt"]] * bs)
         relations = prepare_relation_phrases(meta["prompt"], bs, max_rel, text_encoder, device=device)
     uc = text_encoder.encode([""]).repeat(bs, 1, 1)          # the reference encodes bs copies of "" (interface.py:496)
+    mask = z0 = None
+    if meta.get("input_image") is not None:
+        # inpainting (gligen_inference.py:393-407): encode the input image, regenerate inside the boxes (mask 0), keep the rest
+        L = starting_noise.shape[-1]
+        side = _vae_factor(autoencoder) * L
+        ims = meta["input_image"]
+        if isinstance(ims, (list, tuple)):
+            if len(ims) != bs:
+                raise ValueError(f"input_image: {len(ims)} images for a batch of {bs}")
+            img = torch.cat([load_input_image(im, side, device) for im in ims], 0)
+        else:
+            img = load_input_image(ims, side, device)
+        z0 = autoencoder.encode(img)
+        mask = host.draw_masks_from_boxes(batch["boxes"], L).to(starting_noise.device)
     # S is a harness parameter: the reference hard-codes 50 (interface.py:507); ``args["steps"]`` overrides it
     samples = denoise(all_models, context, uc, relations, batch, starting_noise, meta.get("alpha_type"), cfg.guidance_scale,
-                      steps=int(args.get("steps", PLMS_STEPS)))        # per call: not sticky through the cached config dict
+                      steps=int(args.get("steps", PLMS_STEPS)), mask=mask, x0=z0)   # steps per call: not sticky through the cached config
     return _postprocess(autoencoder.decode(samples))
 
 
 @torch.no_grad()
 def run_one_image(all_models, args, meta, starting_noise=None, clip_model=None, clip_processor=None, device=None):
-    """interface.py:292-357."""
+    """interface.py:292-357.  ``meta["input_image"]`` (a path or a PIL.Image): inpaint that image inside the boxes."""
     return _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple=False)
 
 
 @torch.no_grad()
 def run_batch_images(all_models, args, meta, starting_noise=None, clip_model=None, clip_processor=None, device=None):
-    """interface.py:478-549."""
+    """interface.py:478-549.  ``meta["input_image"]``: a list with one image (path or PIL.Image) per sample, or one for all."""
     return _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple=True)
 
 

@@ -34,18 +34,24 @@ class LatentDiffusion:
         self.betas = torch.tensor(betas64, dtype=torch.float32, device=device)
         self.alphas_cumprod = torch.tensor(acp, dtype=torch.float32, device=device)
         self.alphas_cumprod_prev = torch.tensor(np.append(1.0, acp.astype(np.float64)[:-1]), dtype=torch.float32, device=device)
+        # q(x_t | x_0) coefficients (ddpm.py:39-40): fp64 sqrt of the fp64 cumprod (util.py:21-23 builds the betas with
+        # torch.linspace), stored as fp32 -- what q_sample and the masked PLMS step read
+        acp64 = np.cumprod(1.0 - (torch.linspace(linear_start ** 0.5, linear_end ** 0.5, timesteps, dtype=torch.float64) ** 2).numpy(), axis=0)
+        self.sqrt_alphas_cumprod = torch.tensor(np.sqrt(acp64), dtype=torch.float32, device=device)
+        self.sqrt_one_minus_alphas_cumprod = torch.tensor(np.sqrt(1.0 - acp64), dtype=torch.float32, device=device)
         self.clip_denoised = False
 
     def to(self, device):
-        for k in ("betas", "alphas_cumprod", "alphas_cumprod_prev"):
+        for k in ("betas", "alphas_cumprod", "alphas_cumprod_prev", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod"):
             setattr(self, k, getattr(self, k).to(device))
         return self
 
     def q_sample(self, x_start, t, noise=None):
-        """ldm.py:19-22 (inpainting only; kept for API parity)."""
+        """ldm.py:19-22: extract_into_tensor of the two fp32 buffers, a * x_start + s * noise."""
         noise = torch.randn_like(x_start) if noise is None else noise
-        a = self.alphas_cumprod.to(x_start.device)[t].sqrt().reshape(-1, 1, 1, 1)
-        s = (1.0 - self.alphas_cumprod.to(x_start.device)[t]).sqrt().reshape(-1, 1, 1, 1)
+        b = t.shape[0]
+        a = self.sqrt_alphas_cumprod.to(x_start.device).gather(-1, t.to(x_start.device)).reshape(b, *((1,) * (x_start.dim() - 1)))
+        s = self.sqrt_one_minus_alphas_cumprod.to(x_start.device).gather(-1, t.to(x_start.device)).reshape(b, *((1,) * (x_start.dim() - 1)))
         return a * x_start + s * noise
 
 

@@ -178,8 +178,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias=None, epi: in
 def conv3x3(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, B: int, Hin: int, Win: int, bias=None,
             stride: int = 1, upsample2x: bool = False, epi: int = EPI_BIAS, res=None, rowbias=None,
             rows_per_sample: int = 0, nchw_hw: int = 0, n_valid: Optional[int] = None, out16=None, in_split: int = 0,
-            w_split: bool = False) -> torch.Tensor:
+            w_split: bool = False, pad01: bool = False) -> torch.Tensor:
     """x [B*Hin*Win, Cin] fp16 NHWC; w [Cout, 9*Cin] fp16 (tap-major, channel-minor).
+    ``pad01`` (stride 2): the VAE encoder's Downsample, F.pad(x, (0, 1, 0, 1)) + pad-0 conv (gl_conv3x3_pad01), Hout = Hin // 2.
     ``in_split`` = 2: x is [B*Hin*Win, 2 Cin] = [hi | lo] pixel rows of a split-fp16 activation, both halves against the same weight;
     3 (with ``w_split``): plus the third pass hi.Wlo.  ``w_split``: w is [Cout, 18 Cin] = rows [Whi | Wlo] (gl_conv_args)."""
     _req(x, F16, "x")
@@ -194,6 +195,8 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, B: int, Hin: in
         raise ValueError("w must be [Cout, 9*Cin] ([Cout, 18*Cin] with w_split)")
     if upsample2x:
         Hout, Wout = 2 * Hin, 2 * Win
+    elif pad01:
+        Hout, Wout = Hin // 2, Win // 2
     else:
         Hout, Wout = (Hin + 2 - 3) // stride + 1, (Win + 2 - 3) // stride + 1
     a = ConvArgs()
@@ -204,8 +207,16 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, B: int, Hin: in
     a.g.w = w.data_ptr()
     a.g.N = N if n_valid is None else n_valid
     _fill_epilogue(a.g, epi, out, a.g.N, bias, res, None, rowbias, rows_per_sample, nchw_hw, out16)
-    check(_lib.lib().gl_conv3x3(C.byref(a), _stream()), "gl_conv3x3")
+    if pad01:
+        check(_lib.lib().gl_conv3x3_pad01(C.byref(a), _stream()), "gl_conv3x3_pad01")
+    else:
+        check(_lib.lib().gl_conv3x3(C.byref(a), _stream()), "gl_conv3x3")
     return out
+
+
+def conv3x3_pad01(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, B: int, Hin: int, Win: int, bias=None, **kw) -> torch.Tensor:
+    """conv2d(F.pad(x, (0, 1, 0, 1)), w, stride=2) on NHWC fp16 x (model.py:60-79): output [B*(Hin//2)*(Win//2), Cout]."""
+    return conv3x3(x, w, out, B, Hin, Win, bias, stride=2, pad01=True, **kw)
 
 
 def vt_ld(Nk: int) -> int:
@@ -506,6 +517,37 @@ def pack_latent(x: torch.Tensor, Cpad: int, reps: int, out: torch.Tensor, split:
     B, Cc, h, w = x.shape
     check(_lib.lib().gl_pack_latent(x.data_ptr(), B, Cc, h * w, Cpad, reps, int(split), out.data_ptr(), _stream()), "gl_pack_latent")
     return out
+
+
+def vae_posterior(h: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, noise: torch.Tensor, scale: float, z: torch.Tensor,
+                  mean: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """h fp32 [B, Cin, h, w] (Encoder.conv_out) -> z fp32 [B, E, h, w] = (mean + exp(clamp(logvar, -30, 20) / 2) * noise) * scale with
+    [mean | logvar] = quant_conv(h) in fp32 (w [2E, Cin], bias [2E]); ``mean`` optionally receives the posterior mean."""
+    for t, n in ((h, "h"), (w, "w"), (bias, "bias"), (noise, "noise"), (z, "z")):
+        _req(t, F32, n, 4)
+    B, Cin, hh, ww = h.shape
+    E = w.shape[0] // 2
+    if w.shape != (2 * E, Cin) or tuple(z.shape) != (B, E, hh, ww) or noise.shape != z.shape:
+        raise ValueError("vae_posterior: w [2E, Cin], noise / z [B, E, h, w]")
+    if mean is not None:
+        _req(mean, F32, "mean", 4)
+    check(_lib.lib().gl_vae_posterior(h.data_ptr(), w.data_ptr(), bias.data_ptr(), noise.data_ptr(), float(scale), B, Cin, E, hh * ww,
+                                      z.data_ptr(), _ptr(mean), _stream()), "gl_vae_posterior")
+    return z
+
+
+def latent_blend(x: torch.Tensor, x0: torch.Tensor, noise: torch.Tensor, mask: torch.Tensor, a: float, s: float) -> torch.Tensor:
+    """In place: x = (a * x0 + s * noise) * mask + (1 - mask) * x, bit-identical to that torch expression (plms.py:95-99).
+    x fp32 [B, C, h, w]; x0 / noise [1|B, C, h, w]; mask [1|B, 1, h, w]."""
+    for t, n in ((x, "x"), (x0, "x0"), (noise, "noise"), (mask, "mask")):
+        _req(t, F32, n, 4)
+    B, Cc, hh, ww = x.shape
+    if x0.shape[1:] != x.shape[1:] or noise.shape != x0.shape or x0.shape[0] not in (1, B) or \
+            tuple(mask.shape[1:]) != (1, hh, ww) or mask.shape[0] not in (1, B):
+        raise ValueError("latent_blend: x0 / noise [1|B, C, h, w], mask [1|B, 1, h, w]")
+    check(_lib.lib().gl_latent_blend(x.data_ptr(), x0.data_ptr(), noise.data_ptr(), mask.data_ptr(), float(a), float(s), B, Cc, hh * ww,
+                                     x0.shape[0], mask.shape[0], _stream()), "gl_latent_blend")
+    return x
 
 
 def softmax_rows(x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:

@@ -19,7 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
-from .arch import UNetConfig, VAEConfig, param_shapes, vae_decoder_param_shapes
+from .arch import UNetConfig, VAEConfig, param_shapes, vae_decoder_param_shapes, vae_encoder_param_shapes
 
 
 def _key(name: str, seed: int) -> int:
@@ -85,6 +85,11 @@ def state_dict(cfg: UNetConfig, seed: int = 0, only_prefix: str | None = None) -
 def vae_state_dict(cfg: VAEConfig, seed: int = 0) -> Dict[str, np.ndarray]:
     """Recipe weights of the VAE decode path (reference names), float32."""
     return {n: tensor("vae." + n, shp, seed) for n, shp in vae_decoder_param_shapes(cfg).items()}
+
+
+def vae_encoder_state_dict(cfg: VAEConfig, seed: int = 0) -> Dict[str, np.ndarray]:
+    """Recipe weights of the VAE encode path (reference names encoder.* / quant_conv.*), float32."""
+    return {n: tensor("vae." + n, shp, seed) for n, shp in vae_encoder_param_shapes(cfg).items()}
 
 
 def sd_first_conv(cfg: UNetConfig, seed: int = 0) -> Dict[str, np.ndarray]:

@@ -10,7 +10,10 @@ switch on every scale-0 step, step-0 double evaluation, Adams-Bashforth history 
     conditioning batch is [real grounding + prompt ; null grounding + ""], hoisted once per image;
   * the CFG combine and the x_prev update are two tiny fused HIP kernels on fp32 latents, evaluated
     in the reference's operation order (bit-identical to torch fp32 given the same eps);
-  * the schedule tables are computed once per S.
+  * the schedule tables are computed once per S;
+  * inpainting (``mask`` / ``x0``, plms.py:95-99): each step first replaces the known region,
+    x = q_sample(x0, t) * mask + (1 - mask) * x, as one fused in-place fp32 HIP kernel (gl_latent_blend, bit-identical to
+    the torch expression), with the q_sample noise drawn by ``torch.randn_like(x0)`` before the step's own draws.
 """
 from __future__ import annotations
 
@@ -59,8 +62,8 @@ class PLMSSampler(object):
 
     @torch.no_grad()
     def plms_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
-        if mask is not None:
-            raise NotImplementedError("inpainting masks are not on the layout-to-image path (interface.py:512)")
+        if mask is not None and x0 is None:
+            raise AssertionError("a mask needs x0, the latent of the image to keep (plms.py:96)")
         model, eng = self.model, self.model.engine
         dev = self.device
         b = shape[0]
@@ -109,11 +112,26 @@ class PLMSSampler(object):
             eng.plms_step(x_eval, x_a, x_out, e_out, e_terms, coefs, div, float(t_val), reps, float(guidance_scale),
                           model.fuser_scale, model.use_sd_conv, sq_at, s1m, sq_ap, dirc)
 
+        if mask is not None:
+            # q_sample coefficients of every step, read from the fp32 buffers (ldm.py:19-22); the x0 / mask operands, once
+            sac = self.diffusion.sqrt_alphas_cumprod.detach().cpu().numpy()
+            s1ac = self.diffusion.sqrt_one_minus_alphas_cumprod.detach().cpu().numpy()
+            x0_d = x0.to(dev, torch.float32).contiguous()
+            mask_d = mask.to(dev, torch.float32).contiguous()
+            if x0_d.shape[1:] != x.shape[1:] or x0_d.shape[0] not in (1, b) or tuple(mask_d.shape[1:]) != (1,) + tuple(x.shape[2:]) \
+                    or mask_d.shape[0] not in (1, b):
+                raise ValueError(f"x0 must be [1|{b}, {tuple(x.shape[1:])}] and mask [1|{b}, 1, {tuple(x.shape[2:])}], got "
+                                 f"{tuple(x0.shape)} and {tuple(mask.shape)}")
+
         for i, step in enumerate(time_range):
             if alphas is not None:
                 self.set_alpha_scale(model, alphas[i])
                 if alphas[i] == 0:
                     model.restore_first_conv_from_SD()
+            if mask is not None:
+                # plms.py:95-99: img = q_sample(x0, ts) * mask + (1 - mask) * img; the noise is randn_like(x0) on x0's device
+                noise = torch.randn_like(x0).to(dev, torch.float32).contiguous()
+                ops.latent_blend(x_a, x0_d, noise, mask_d, float(sac[int(step)]), float(s1ac[int(step)]))
             index = total_steps - i - 1
             t_next = time_range[min(i + 1, len(time_range) - 1)]
             e_t = free.pop()

@@ -11,6 +11,12 @@ head of d = 512, beyond the flash kernel's register budget; it runs once per ima
 Q.K^T (GEMM) -> row softmax -> P.V (GEMM against V^T), with 1/sqrt(C) folded into the q weights at
 pack time so the fp16 logits stay small.
 
+``VAEEncoder.encode(x)`` is AutoencoderKL.encode (autoencoder.py:34-38): Encoder.forward (model.py:368-459), quant_conv, the
+posterior sample and * scale_factor, through ``gl_vae_encoder_create`` / ``gl_vae_encode`` on the same engine (the stride-2
+Downsample with its asymmetric F.pad(x, (0, 1, 0, 1)) is ``gl_conv3x3_pad01``, quant_conv + posterior one fp32 kernel,
+``gl_vae_posterior``); ``encode_oplevel`` is its op-by-op test mirror.  ``VAEDecoder.encode`` delegates to an encoder built from
+the same state dict when it holds the encoder tensors (real GLIGEN checkpoints do).
+
 ``VAEDecoder.decode(z)`` has the reference's contract: z fp32 [B, 4, h, w] -> fp32 [B, 3, 8h, 8w].  It is a thin caller
 of the C engine (``gl_vae_create`` / ``gl_vae_load_weights`` / ``gl_vae_decode``, csrc/vae_engine.hip: plan, flat weight
 layout, activation pool, one hipGraph per (batch, side)); ``decode_oplevel`` is the same launch sequence issued op by op
@@ -18,58 +24,93 @@ from Python -- the test mirror the C engine must equal bitwise, like tests/engin
 """
 from __future__ import annotations
 
-from typing import Dict, Mapping
+from typing import Dict, Mapping, Optional, Tuple
 
 import torch
 
 from . import ops
 from ._lib import EPI_BIAS, EPI_RES, init_device
-from .arch import VAEConfig, vae_decoder_param_shapes
+from .arch import VAEConfig, vae_decoder_param_shapes, vae_encoder_param_shapes
 from .weights import CIN_PAD, _h, _t, pack_conv3x3
 
 F16, F32 = torch.float16, torch.float32
+_FP32_1X1 = ("post_quant_conv", "quant_conv")      # 1x1 convs on the 4 / 8-channel latent side: kept in fp32
 
 
-class VAEDecoder:
-    def __init__(self, state_dict: Mapping[str, object], cfg: VAEConfig = VAEConfig(), device="cuda:0"):
-        if not torch.cuda.is_available():
-            raise RuntimeError("VAEDecoder needs a GPU: there is no CPU fallback")
-        init_device()
-        self.cfg, self.device = cfg, torch.device(device)
-        self.scale_factor = cfg.scale_factor
-        need = vae_decoder_param_shapes(cfg)
-        missing = [k for k in need if k not in state_dict]
-        if missing:
-            raise KeyError(f"autoencoder state_dict is missing {len(missing)} decoder tensors, e.g. {missing[:3]}")
-        g = lambda k: _t(state_dict[k], self.device)
-        W: Dict[str, torch.Tensor] = {}
-        for name, shp in need.items():
-            if not name.endswith(".weight"):
-                continue
-            p = name[:-7]
-            w = g(name)
-            b = g(p + ".bias")
-            if len(shp) == 1:                       # GroupNorm affine
-                W[p + ".g"], W[p + ".b"] = w.contiguous(), b.contiguous()
-            elif shp[2] == 3:                       # 3x3 conv
-                W[p + ".w"] = pack_conv3x3(w, CIN_PAD if shp[1] < 64 else None)
-                W[p + ".b"] = b.contiguous()
-            elif p == "post_quant_conv":            # 1x1 on the 4-channel latent: applied in fp32 while packing
-                W[p + ".w"], W[p + ".b"] = w.reshape(shp[0], shp[1]).contiguous(), b.contiguous()
-            else:                                   # 1x1 conv = GEMM
-                w2, b2 = w.reshape(shp[0], shp[1]), b
-                if p.endswith("attn_1.q"):          # fold the softmax scale C^-0.5 (model.py:183) into q
-                    s = float(shp[0]) ** -0.5
-                    w2, b2 = w2 * s, b2 * s
-                W[p + ".w"], W[p + ".b"] = _h(w2), b2.contiguous()
-        self.W = W
-        self._pool: Dict[tuple, torch.Tensor] = {}
-        self._bind_engine()
+def _pack_kind(p: str, shp: Tuple[int, ...]) -> str:
+    if len(shp) == 1:
+        return "norm"                               # GroupNorm affine
+    if shp[2] == 3:
+        return "conv3x3"
+    return "f32_1x1" if p in _FP32_1X1 else "gemm"
+
+
+def packed_shapes(param_shapes: Mapping[str, Tuple[int, ...]]) -> Dict[str, Tuple[Tuple[int, ...], torch.dtype]]:
+    """CPU-side: the engine-table entries {name: (shape, dtype)} the packer makes from reference-named ``param_shapes``
+    (3x3 convs fp16 [Cout, 9 * Cin] with Cin < 64 padded to CIN_PAD, 1x1 convs fp16 [N, K] except the fp32 (post_)quant_conv,
+    norm affine and biases fp32)."""
+    out: Dict[str, Tuple[Tuple[int, ...], torch.dtype]] = {}
+    for name, shp in param_shapes.items():
+        if not name.endswith(".weight"):
+            continue
+        p, kind = name[:-7], _pack_kind(name[:-7], shp)
+        if kind == "norm":
+            out[p + ".g"], out[p + ".b"] = ((shp[0],), F32), ((shp[0],), F32)
+            continue
+        if kind == "conv3x3":
+            out[p + ".w"] = ((shp[0], 9 * (CIN_PAD if shp[1] < 64 else shp[1])), F16)
+        else:
+            out[p + ".w"] = ((shp[0], shp[1]), F32 if kind == "f32_1x1" else F16)
+        out[p + ".b"] = ((shp[0],), F32)
+    return out
+
+
+def _pack(state_dict: Mapping[str, object], need: Mapping[str, Tuple[int, ...]], device) -> Dict[str, torch.Tensor]:
+    """Reference-named tensors -> the engine's packed forms (``packed_shapes``); C^-0.5 folded into mid.attn_1.q."""
+    g = lambda k: _t(state_dict[k], device)
+    W: Dict[str, torch.Tensor] = {}
+    for name, shp in need.items():
+        if not name.endswith(".weight"):
+            continue
+        p = name[:-7]
+        w = g(name)
+        b = g(p + ".bias")
+        kind = _pack_kind(p, shp)
+        if kind == "norm":
+            W[p + ".g"], W[p + ".b"] = w.contiguous(), b.contiguous()
+        elif kind == "conv3x3":
+            W[p + ".w"] = pack_conv3x3(w, CIN_PAD if shp[1] < 64 else None)
+            W[p + ".b"] = b.contiguous()
+        elif kind == "f32_1x1":                     # 1x1 on the latent side: applied in fp32 (latent packing / posterior kernel)
+            W[p + ".w"], W[p + ".b"] = w.reshape(shp[0], shp[1]).contiguous(), b.contiguous()
+        else:                                       # 1x1 conv = GEMM
+            w2, b2 = w.reshape(shp[0], shp[1]), b
+            if p.endswith("attn_1.q"):              # fold the softmax scale C^-0.5 (model.py:183) into q
+                s = float(shp[0]) ** -0.5
+                w2, b2 = w2 * s, b2 * s
+            W[p + ".w"], W[p + ".b"] = _h(w2), b2.contiguous()
+    return W
+
+
+def encoder_unsupported(state_dict: Mapping[str, object], cfg: VAEConfig):
+    """Why this package cannot run the checkpoint's encoder (down-level attention, in_channels != out_ch), or None."""
+    attn = sorted(k for k in state_dict if k.startswith("encoder.down.") and ".attn." in k)
+    if attn:
+        return f"the VAE encoder has down-level attention ({attn[0]}); only attn_resolutions = [] is implemented"
+    w = state_dict.get("encoder.conv_in.weight")
+    if w is not None and tuple(w.shape)[1] != cfg.out_ch:
+        return f"the VAE encoder takes {tuple(w.shape)[1]} input channels, the decoder emits out_ch = {cfg.out_ch}"
+    return None
+
+
+class _VAEStage:
+    """Engine binding, option knob, pooled buffers and the ResnetBlock / AttnBlock op sequences shared by both stages."""
+    _encoder_stage = False
 
     def _bind_engine(self):
         """Moves the packed tensors into the C engine's flat layout (gl_vae_weight_at) and rebinds ``W`` to views of it."""
         from . import _lib
-        self.handle = _lib.create_vae(self.cfg)
+        self.handle = _lib.create_vae(self.cfg, encoder=self._encoder_stage)
         table, total = _lib.vae_weight_table(self.handle)
         flat = torch.zeros(total, dtype=torch.uint8, device=self.device)
         views = {}
@@ -91,7 +132,7 @@ class VAEDecoder:
         self.use_graphs = True
 
     def set_option(self, key: int, value: int) -> None:
-        """Override one gl_set_option knob for THIS decoder only (gl_vae_set_option)."""
+        """Override one gl_set_option knob for THIS stage only (gl_vae_set_option)."""
         from . import _lib
         _lib.check(_lib.lib().gl_vae_set_option(self.handle, int(key), int(value)), "gl_vae_set_option")
 
@@ -103,20 +144,6 @@ class VAEDecoder:
                 _lib.lib().gl_vae_destroy(h)
             except Exception:
                 pass
-
-    @classmethod
-    def from_packed(cls, W: Mapping[str, torch.Tensor], cfg: VAEConfig, device="cuda:0") -> "VAEDecoder":
-        """A decoder around ALREADY PACKED tensors (``self.W`` of another instance, e.g. received through
-        dist.broadcast_bundle): no state_dict, no repacking."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("VAEDecoder needs a GPU: there is no CPU fallback")
-        init_device()
-        self = cls.__new__(cls)
-        self.cfg, self.device, self.scale_factor = cfg, torch.device(device), cfg.scale_factor
-        self.W = {k: v.to(self.device) for k, v in W.items()}
-        self._pool = {}
-        self._bind_engine()
-        return self
 
     def buf(self, tag, shape, dtype=F16):
         key = (tag, tuple(shape), dtype)
@@ -168,6 +195,50 @@ class VAEDecoder:
             ops.gemm(s[b], vt2[b], o[b * N:(b + 1) * N])                  # P [N, Np] . V^T[C, Np]^T
         return ops.gemm(o, W[p + ".proj_out.w"], self.buf(tag, (M, C)), W[p + ".proj_out.b"], EPI_RES, res=x)
 
+
+class VAEDecoder(_VAEStage):
+    def __init__(self, state_dict: Mapping[str, object], cfg: VAEConfig = VAEConfig(), device="cuda:0"):
+        if not torch.cuda.is_available():
+            raise RuntimeError("VAEDecoder needs a GPU: there is no CPU fallback")
+        init_device()
+        self.cfg, self.device = cfg, torch.device(device)
+        self.scale_factor = cfg.scale_factor
+        need = vae_decoder_param_shapes(cfg)
+        missing = [k for k in need if k not in state_dict]
+        if missing:
+            raise KeyError(f"autoencoder state_dict is missing {len(missing)} decoder tensors, e.g. {missing[:3]}")
+        self.W = _pack(state_dict, need, self.device)
+        self._pool: Dict[tuple, torch.Tensor] = {}
+        self._bind_engine()
+        # the encode stage, when the state dict carries it (real GLIGEN checkpoints do); self.W stays decoder-only
+        enc_missing = [k for k in vae_encoder_param_shapes(cfg) if k not in state_dict]
+        self.encoder = VAEEncoder(state_dict, cfg, device) if not enc_missing else None
+        self._no_encoder = (f"this autoencoder has no encode stage: its state_dict lacks {len(enc_missing)} encoder tensors, "
+                            f"e.g. {enc_missing[:3]}") if enc_missing else None
+
+    @classmethod
+    def from_packed(cls, W: Mapping[str, torch.Tensor], cfg: VAEConfig, device="cuda:0") -> "VAEDecoder":
+        """A decoder around ALREADY PACKED tensors (``self.W`` of another instance, e.g. received through
+        dist.broadcast_bundle): no state_dict, no repacking."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("VAEDecoder needs a GPU: there is no CPU fallback")
+        init_device()
+        self = cls.__new__(cls)
+        self.cfg, self.device, self.scale_factor = cfg, torch.device(device), cfg.scale_factor
+        self.W = {k: v.to(self.device) for k, v in W.items()}
+        self._pool = {}
+        self._bind_engine()
+        self.encoder = None
+        self._no_encoder = ("this decoder was built from packed decoder weights: the encoder tensors (encoder.*, quant_conv.*) are "
+                            "not part of the packed bundle")
+        return self
+
+    def encode(self, x: torch.Tensor, noise=None) -> torch.Tensor:
+        """AutoencoderKL.encode (autoencoder.py:34-38) through the encoder built from the same state dict."""
+        if self.encoder is None:
+            raise RuntimeError(self._no_encoder)
+        return self.encoder.encode(x, noise)
+
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         """AutoencoderKL.decode through the C engine (one hipGraph replay per call after the first)."""
@@ -212,3 +283,90 @@ class VAEDecoder:
         out = torch.empty(B, cfg.out_ch, side, side, dtype=F32, device=self.device)
         ops.conv3x3(g, W["decoder.conv_out.w"], out, B, side, side, W["decoder.conv_out.b"], nchw_hw=side * side)
         return out
+
+
+class VAEEncoder(_VAEStage):
+    """AutoencoderKL.encode on the HIP engine: x fp32 [B, 3, H, H] in [-1, 1] -> z fp32 [B, embed_dim, H / f, H / f], f = 8."""
+    _encoder_stage = True
+
+    def __init__(self, state_dict: Mapping[str, object], cfg: VAEConfig = VAEConfig(), device="cuda:0"):
+        if not torch.cuda.is_available():
+            raise RuntimeError("VAEEncoder needs a GPU: there is no CPU fallback")
+        why = encoder_unsupported(state_dict, cfg)
+        if why:
+            raise NotImplementedError(why)
+        init_device()
+        self.cfg, self.device = cfg, torch.device(device)
+        self.scale_factor = cfg.scale_factor
+        need = vae_encoder_param_shapes(cfg)
+        missing = [k for k in need if k not in state_dict]
+        if missing:
+            raise KeyError(f"autoencoder state_dict is missing {len(missing)} encoder tensors, e.g. {missing[:3]}")
+        self.W = _pack(state_dict, need, self.device)
+        self._pool: Dict[tuple, torch.Tensor] = {}
+        self._bind_engine()
+
+    @property
+    def factor(self) -> int:
+        return 2 ** (len(self.cfg.ch_mult) - 1)
+
+    def _check(self, x: torch.Tensor):
+        x = x.to(self.device, F32).contiguous()
+        B, c, side, side_w = x.shape
+        f = self.factor
+        if c != self.cfg.out_ch or side != side_w:
+            raise ValueError(f"encode: expected a square [B, {self.cfg.out_ch}, H, H] image batch, got {tuple(x.shape)}")
+        if side % f or side >= 1024:
+            raise ValueError(f"encode: the image side must be a multiple of {f} and below 1024, got {side}")
+        return x, B, side, side // f
+
+    def _noise(self, noise, B, zs):
+        if noise is None:   # distributions.py:36: torch.randn(mean.shape) on the CPU default generator, then moved to the device
+            noise = torch.randn((B, self.cfg.embed_dim, zs, zs))
+        noise = noise.to(self.device, F32).contiguous()
+        if tuple(noise.shape) != (B, self.cfg.embed_dim, zs, zs):
+            raise ValueError(f"encode: noise must be [{B}, {self.cfg.embed_dim}, {zs}, {zs}], got {tuple(noise.shape)}")
+        return noise
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """posterior.sample() * scale_factor through the C engine (one hipGraph replay per call after the first)."""
+        from . import _lib
+        x, B, side, zs = self._check(x)
+        noise = self._noise(noise, B, zs)
+        z = torch.empty(B, self.cfg.embed_dim, zs, zs, dtype=F32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().gl_vae_encode(self.handle, x.data_ptr(), B, side, noise.data_ptr(), z.data_ptr(), int(self.use_graphs),
+                                                torch.cuda.current_stream(self.device).cuda_stream), "gl_vae_encode")
+        return z
+
+    @torch.no_grad()
+    def encode_oplevel(self, x: torch.Tensor, noise: torch.Tensor, return_mean: bool = False):
+        """The engine's launch sequence issued op by op from Python (test mirror; bitwise equal to ``encode``).
+        ``return_mean``: also the posterior mean (unscaled)."""
+        cfg, W = self.cfg, self.W
+        x, B, side, zs = self._check(x)
+        noise = self._noise(noise, B, zs)
+        nres = len(cfg.ch_mult)
+        ch = cfg.ch
+        xin = ops.pack_latent(x, CIN_PAD, 1, self.buf("in", (B * side * side, CIN_PAD)))
+        h = ops.conv3x3(xin, W["encoder.conv_in.w"], self.buf("conv_in", (B * side * side, ch)), B, side, side, W["encoder.conv_in.b"])
+        for lvl in range(nres):
+            cout = cfg.ch * cfg.ch_mult[lvl]
+            for i in range(cfg.num_res_blocks):
+                h = self._resnet(f"encoder.down.{lvl}.block.{i}", h, B, side, ch, cout, f"down.{lvl}.{i}")
+                ch = cout
+            if lvl != nres - 1:
+                p = f"encoder.down.{lvl}.downsample.conv"
+                h = ops.conv3x3_pad01(h, W[p + ".w"], self.buf(f"down.{lvl}.d", (B * (side // 2) ** 2, ch)), B, side, side, W[p + ".b"])
+                side //= 2
+        h = self._resnet("encoder.mid.block_1", h, B, side, ch, ch, "mid.1")
+        h = self._attn("encoder.mid.attn_1", h, B, side, ch, "mid.a")
+        h = self._resnet("encoder.mid.block_2", h, B, side, ch, ch, "mid.2")
+        g = self._gn(h, B, side * side, "encoder.norm_out", True, "fin.gn")
+        mom = torch.empty(B, 2 * cfg.z_channels, side, side, dtype=F32, device=self.device)
+        ops.conv3x3(g, W["encoder.conv_out.w"], mom, B, side, side, W["encoder.conv_out.b"], nchw_hw=side * side)
+        z = torch.empty(B, cfg.embed_dim, side, side, dtype=F32, device=self.device)
+        mean = torch.empty_like(z) if return_mean else None
+        ops.vae_posterior(mom, W["quant_conv.w"], W["quant_conv.b"], noise, cfg.scale_factor, z, mean)
+        return (z, mean) if return_mean else z
