@@ -384,6 +384,18 @@ int gl_load_weights(gl_engine* e, const void* packed, int64_t bytes, int32_t has
 int gl_set_conditioning(gl_engine* e, const float* context, const float* relations, const float* boxes,
                         const float* masks, const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t hw,
                         void* stream);
+/* gl_set_conditioning_hw: the same for a RECTANGULAR latent of h rows and w columns (ABI 15, additive).  gl_set_conditioning(.., hw) is
+ * gl_set_conditioning_hw(.., hw, hw) minus the shape check below: a square through either entry takes the same launches, tiles and graph.
+ * Shape rules: h and w must each be a positive multiple of 2^(number of downsamples) (8 for the shipped model and for the tiny test
+ * architecture) -- with fewer the upsampled tensor no longer matches the skip tensor it is concatenated with, where the reference fails
+ * too -- else GL_ERR_BAD_ARG, before anything is launched and without touching the handle's conditioning.  Box x coordinates scale with
+ * the level's w and box y coordinates with its h (attention.py:322-328); the per-level rectangle buffers and the graph cache are keyed by
+ * (h, w), so 64 x 96, 96 x 64 and 64 x 64 conditionings can alternate on one handle.  gl_unet_forward and gl_plms_step take the shape
+ * from the conditioning: every [.., hw, hw] below reads [.., h, w].  Tested range: up to 9216 tokens (64 x 96, 96 x 64 and 96 x 96 at
+ * 2B = 8). */
+int gl_set_conditioning_hw(gl_engine* e, const float* context, const float* relations, const float* boxes,
+                           const float* masks, const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t h, int32_t w,
+                           void* stream);
 /* gl_unet_forward: eps[Bn, out_ch, hw, hw] fp32 = UNet(x, t | conditioning).  x fp32 NCHW [Bn / reps, in_ch, hw, hw]:
  * with reps = 2 both CFG halves of a [cond ; uncond] conditioning batch share the latent.  t_dev: fp32 [Bn] device
  * timesteps, or NULL to use t_host for every sample.  fuser_scale = what set_alpha_scale wrote (interface.py:34-38;
@@ -470,6 +482,9 @@ int gl_vae_weight_at(const gl_vae* v, int32_t i, gl_weight_info* info);
 int64_t gl_vae_weights_bytes(const gl_vae* v);
 int gl_vae_load_weights(gl_vae* v, const void* packed, int64_t bytes, void* stream);
 int gl_vae_decode(gl_vae* v, const float* z, int32_t B, int32_t side, float* out, int32_t use_graph, void* stream);
+/* gl_vae_decode_hw: z fp32 [B, z_channels, h, w] -> out fp32 [B, out_ch, f * h, f * w], f = 2^(n_mult-1); one hipGraph per (B, h, w), the
+ * mid-block attention over h * w tokens.  gl_vae_decode(.., side) == gl_vae_decode_hw(.., side, side). */
+int gl_vae_decode_hw(gl_vae* v, const float* z, int32_t B, int32_t h, int32_t w, float* out, int32_t use_graph, void* stream);
 int gl_vae_num_launches(const gl_vae* v);
 int64_t gl_vae_pool_bytes(const gl_vae* v);
 int gl_sizeof_vae_config(void);
@@ -485,6 +500,11 @@ int gl_sizeof_vae_config(void);
  */
 int gl_vae_encoder_create(const gl_vae_config* cfg, gl_vae** out);
 int gl_vae_encode(gl_vae* v, const float* x, int32_t B, int32_t side, const float* noise, float* z, int32_t use_graph, void* stream);
+/* gl_vae_encode_hw: x fp32 [B, out_ch, h, w] -> z fp32 [B, embed_dim, h / f, w / f] with noise of z's shape; h and w each a multiple of f
+ * below 1024 (GL_ERR_BAD_ARG otherwise), one hipGraph per (B, h, w); the stride-2 Downsample pads one row below and one column right per
+ * axis.  gl_vae_encode(.., side) == gl_vae_encode_hw(.., side, side). */
+int gl_vae_encode_hw(gl_vae* v, const float* x, int32_t B, int32_t h, int32_t w, const float* noise, float* z, int32_t use_graph,
+                     void* stream);
 
 /*
  * CLIP towers of the reward stage: transformers.CLIPModel.get_image_features / get_text_features as the

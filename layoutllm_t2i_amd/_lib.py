@@ -180,6 +180,7 @@ PROTOTYPES = {
     "gl_weights_bytes": (i64, [vp]),
     "gl_load_weights": (i32, [vp, vp, i64, i32, vp]),
     "gl_set_conditioning": (i32, [vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, vp]),
+    "gl_set_conditioning_hw": (i32, [vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]),
     "gl_unet_forward": (i32, [vp, fp, fp, f32, i32, f32, i32, fp, i32, vp]),
     "gl_plms_step": (i32, [vp, C.POINTER(PlmsStepArgs), vp]),
     "gl_pool_bytes": (i64, [vp]),
@@ -208,11 +209,13 @@ PROTOTYPES = {
     "gl_vae_weights_bytes": (i64, [vp]),
     "gl_vae_load_weights": (i32, [vp, vp, i64, vp]),
     "gl_vae_decode": (i32, [vp, fp, i32, i32, fp, i32, vp]),
+    "gl_vae_decode_hw": (i32, [vp, fp, i32, i32, i32, fp, i32, vp]),
     "gl_vae_num_launches": (i32, [vp]),
     "gl_vae_pool_bytes": (i64, [vp]),
     "gl_sizeof_vae_config": (i32, []),
     "gl_vae_encoder_create": (i32, [C.POINTER(VaeConfigC), C.POINTER(vp)]),
     "gl_vae_encode": (i32, [vp, fp, i32, i32, fp, fp, i32, vp]),
+    "gl_vae_encode_hw": (i32, [vp, fp, i32, i32, i32, fp, fp, i32, vp]),
     "gl_conv3x3_pad01": (i32, [C.POINTER(ConvArgs), vp]),
     "gl_vae_posterior": (i32, [fp, fp, fp, fp, f32, i32, i32, i32, i32, fp, fp, vp]),
     "gl_latent_blend": (i32, [fp, fp, fp, fp, f32, f32, i32, i32, i32, i32, i32, vp]),

@@ -138,9 +138,9 @@ struct gl_engine {
     int device = -1;
     // conditioning
     bool cond_set = false;
-    int Bn = 0, R = 0, Lc = 0, hw = 0;
+    int Bn = 0, R = 0, Lc = 0, lat_h = 0, lat_w = 0;     // (lat_h, lat_w): the latent's rows and columns (gl_set_conditioning_hw)
     // graphs
-    std::map<std::tuple<int, int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
+    std::map<std::tuple<int, int, int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
     float fuser_scale_cur = -1e30f;
     std::vector<float> gate_host;      // the [n_st][4] array last computed
     float* gate_pin[2] = {nullptr, nullptr};           // pinned double buffer the async upload reads from
@@ -362,6 +362,8 @@ inline int vt_ld(int Nk) {
     const int n = (Nk + 63) / 64 * 64;
     return (n % 512 == 0) ? n + 64 : n;
 }
+// the per-resolution conditioning buffers (cond.rects.* / nvalid.* / poison.*) are named by rows x columns: 64x96, 96x64 and 64x64 are three levels
+inline std::string level_tag(int h, int w) { return std::to_string(h) + "x" + std::to_string(w); }
 inline int gn_nchunk(int HW) {
     if (HW <= 4096) { int c = HW / 4; if (c > 64) c = 64; return c < 1 ? 1 : c; }
     int c = HW / 512;
@@ -649,10 +651,10 @@ int feed_forward(Run& r, const half_t* xn, const float* res, const std::string& 
 
 // ResBlock._forward (openaimodel.py:211-231); skip = the popped skip-stack tensor of an output block (th.cat folded in).
 // need_h: the output also gets an fp16 copy (its consumer is a down / up conv, or the round-3 fp16-copy mode is on).
-int res_block(Run& r, const LayerD& l, Stream2 h, const Stream2* skip, int skip_c, int side, const void* emb_out, const std::string& tag,
+int res_block(Run& r, const LayerD& l, Stream2 h, const Stream2* skip, int skip_c, int sh, int sw, const void* emb_out, const std::string& tag,
               bool need_h, Stream2* out) {
     gl_engine* e = r.e;
-    const int Bn = e->Bn, HW = side * side, M = Bn * HW;
+    const int Bn = e->Bn, HW = sh * sw, M = Bn * HW;
     const std::string& p = l.prefix;
     const int c1 = l.cin - skip_c;
     const bool strict = g_strict != 0;
@@ -675,7 +677,7 @@ int res_block(Run& r, const LayerD& l, Stream2 h, const Stream2* skip, int skip_
     const int off = e->emb_off[p];
     void* h1 = h1f ? (void*)e->f32("rb.h1f", (size_t)M * l.cout) : (void*)e->h16("rb.h1", (size_t)M * l.cout);
     CKP(h1);
-    CK(r.conv(t, p + ".in_layers.2.w", p + ".in_layers.2.b", Bn, side, side, l.cin, 1, 0, h1, h1f ? GL_OUT_F32_ROWMAJOR : GL_OUT_F16_ROWMAJOR,
+    CK(r.conv(t, p + ".in_layers.2.w", p + ".in_layers.2.b", Bn, sh, sw, l.cin, 1, 0, h1, h1f ? GL_OUT_F32_ROWMAJOR : GL_OUT_F16_ROWMAJOR,
               GL_EPI_ROWBIAS, nullptr, 0, 0,
               precise ? (const void*)(reinterpret_cast<const float*>(emb_out) + off) : (const void*)(reinterpret_cast<const half_t*>(emb_out) + off),
               e->emb_total, HW, nullptr, 0, strict));
@@ -699,21 +701,21 @@ int res_block(Run& r, const LayerD& l, Stream2 h, const Stream2* skip, int skip_
     out->h = need_h ? e->h16(tag, (size_t)M * l.cout) : nullptr;
     CKP(out->f);
     if (need_h) CKP(out->h);
-    return r.conv(t2, p + ".out_layers.3.w", p + ".out_layers.3.b", Bn, side, side, l.cout, 1, 0, out->f, GL_OUT_F32_ROWMAJOR, GL_EPI_RES, sk, l.cout, 1,
+    return r.conv(t2, p + ".out_layers.3.w", p + ".out_layers.3.b", Bn, sh, sw, l.cout, 1, 0, out->f, GL_OUT_F32_ROWMAJOR, GL_EPI_RES, sk, l.cout, 1,
                   nullptr, 0, 0, out->h, 0, strict);
 }
 
 // SpatialTransformer.forward + BasicTransformerBlock._forward (attention.py:436-446, :394-402)
 // share_half: xin holds only the first Bn / 2 samples (the shared cond / uncond prefix): GroupNorm .. attn1 run on those rows, then xin and x
 // are duplicated into the second half and the block continues on all Bn samples (from the first conditioning-dependent op on).
-int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int side, bool fuser_on, const std::string& tag, bool need_h, Stream2* out,
+int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, int sw, bool fuser_on, const std::string& tag, bool need_h, Stream2* out,
                         bool share_half = false) {
     gl_engine* e = r.e;
     const gl_unet_config& cfg = e->cfg;
     const std::string& p = l.prefix;
     const std::string t = p + ".transformer_blocks.0";
     const int C = l.cin, d = l.d_head, H = cfg.num_heads;
-    const int Bn = e->Bn, N = side * side, M = Bn * N, mo = cfg.max_objs, R = e->R, Lc = e->Lc;
+    const int Bn = e->Bn, N = sh * sw, M = Bn * N, mo = cfg.max_objs, R = e->R, Lc = e->Lc;
     const std::string sl = std::to_string(li);
     float* xa = e->f32("st.xa", (size_t)M * C);
     float* xb = e->f32("st.xb", (size_t)M * C);
@@ -784,7 +786,7 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int side, 
     bool ln2_done = false;
     {
         const std::string rf = t + ".rela_fuse";
-        const std::string ss = std::to_string(side);
+        const std::string ss = level_tag(sh, sw);
         const int* rects = reinterpret_cast<const int*>(e->buf("cond.rects." + ss, (size_t)Bn * mo * 16));
         const int* nvalid = reinterpret_cast<const int*>(e->buf("cond.nvalid." + ss, (size_t)Bn * 4));
         const int* poison = reinterpret_cast<const int*>(e->buf("cond.poison." + ss, (size_t)Bn * 4));
@@ -804,12 +806,12 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int side, 
             // LayerNorm3 is never materialised: its per-row statistics, then the box means of LN3(x) and (in rela_merge) LN3(x) itself in fp32
             r.launches += 2;
             CK(gl_layernorm_stats(x, C, M, C, 1e-5f, stats, r.st));
-            CK(gl_rela_pool_ln3(x, stats, e->Wf(rf + ".norm3.g"), e->Wf(rf + ".norm3.b"), Bn, side, side, C, rects, nvalid, poison, mo, ms, feat,
+            CK(gl_rela_pool_ln3(x, stats, e->Wf(rf + ".norm3.g"), e->Wf(rf + ".norm3.b"), Bn, sh, sw, C, rects, nvalid, poison, mo, ms, feat,
                                 e->Wf(rf + ".norm1.g"), e->Wf(rf + ".norm1.b"), fn, r.st));
         } else {
             CK(r.ln(x, C, 1, hid, C, rf + ".norm3", Bn, N, N, 0, C, stats));
             ++r.launches;
-            CK(gl_rela_pool(hid, Bn, side, side, C, rects, nvalid, poison, mo, ms, feat, e->Wf(rf + ".norm1.g"), e->Wf(rf + ".norm1.b"), fn, r.st));
+            CK(gl_rela_pool(hid, Bn, sh, sw, C, rects, nvalid, poison, mo, ms, feat, e->Wf(rf + ".norm1.g"), e->Wf(rf + ".norm1.b"), fn, r.st));
         }
         CK(r.gemm(fn, C, rf + ".attn.q.w", Mo, q, C));
         const half_t* kv = e->h16("hoist.kvrel." + sl, (size_t)Bn * R * 2 * C);
@@ -825,7 +827,7 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int side, 
         ++r.launches;
         // ... and LayerNorm(norm2) of the merged rows in the same launch (the rows attn2's q projection reads)
         const bool fuse_ln2 = g_fuse_merge_ln && ms <= 32 && !strict;      // (strict: norm2 is a launch of its own that also writes the lo half)
-        CK(gl_rela_merge(x, 1, nullptr, stats, e->Wf(rf + ".norm3.g"), e->Wf(rf + ".norm3.b"), f2, Bn, side, side, C, rects, nvalid, poison, mo, ms, y,
+        CK(gl_rela_merge(x, 1, nullptr, stats, e->Wf(rf + ".norm3.g"), e->Wf(rf + ".norm3.b"), f2, Bn, sh, sw, C, rects, nvalid, poison, mo, ms, y,
                          fuse_ln2 ? e->Wf(t + ".norm2.g") : nullptr, fuse_ln2 ? e->Wf(t + ".norm2.b") : nullptr, fuse_ln2 ? lnb : nullptr, r.st));
         x = y;
         ln2_done = fuse_ln2;
@@ -881,12 +883,12 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
     const bool share = g_share != 0 && reps == 2 && uniform_t && (Bn % 2) == 0 && e->input_blocks.size() > 1 &&
                        !e->input_blocks[1].layers.empty() && e->input_blocks[1].layers[0].kind == RES;
     const int B0 = share ? Bn / 2 : Bn;
-    int side = e->hw;
+    int sh = e->lat_h, sw = e->lat_w;
     Run r{e, st, e->buf("splitk.ws", WS_BYTES)};
     CKP(r.ws);
-    const float* x_lat = e->f32("in.xlat", (size_t)(Bn / reps) * cfg.in_channels * side * side);
+    const float* x_lat = e->f32("in.xlat", (size_t)(Bn / reps) * cfg.in_channels * sh * sw);
     const float* t_buf = e->f32("in.t", Bn);
-    float* eps = e->f32("out.eps", (size_t)Bn * cfg.out_channels * side * side);
+    float* eps = e->f32("out.eps", (size_t)Bn * cfg.out_channels * sh * sw);
     CKP(x_lat); CKP(t_buf); CKP(eps);
     // time embedding (openaimodel.py:428-429) and all emb_layers in one GEMM (:172-178, :220)
     const bool strict = g_strict != 0;
@@ -914,26 +916,26 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
     CK(r.gemm(e2, 4 * mc * tw, "emb_all.w", Bn, emb_out, e->emb_total, precise ? GL_OUT_F32_ROWMAJOR : GL_OUT_F16_ROWMAJOR, "emb_all.b", GL_EPI_BIAS, nullptr, 0, 0,
               nullptr, nullptr, 0, nullptr, 0, 0, strict));
     // first conv on the zero-padded NHWC latent (openaimodel.py:299, :393-405)
-    half_t* xin = e->h16("in.x", (size_t)Bn * side * side * CIN_PAD);
+    half_t* xin = e->h16("in.x", (size_t)Bn * sh * sw * CIN_PAD);
     CKP(xin);
     ++r.launches;
-    CK(gl_pack_latent(x_lat, Bn / reps, cfg.in_channels, side * side, CIN_PAD, share ? 1 : reps, g_in_split && 3 * cfg.in_channels <= CIN_PAD, xin, st));
+    CK(gl_pack_latent(x_lat, Bn / reps, cfg.in_channels, sh * sw, CIN_PAD, share ? 1 : reps, g_in_split && 3 * cfg.in_channels <= CIN_PAD, xin, st));
     const std::string fc = sd_conv ? "sd_first_conv" : "input_blocks.0.0";
     // fp16 copies of stream tensors: only where a down / up conv consumes the tensor (precise mode: every GroupNorm and 1x1 conv
     // reads the fp32 stream), or everywhere in the round-3 fp16-copy mode
     auto first_kind = [&](const BlockD* b) { return b && !b->layers.empty() ? b->layers[0].kind : -1; };
     auto wants_h = [&](int next_kind) { return !precise || next_kind == DOWN || next_kind == UP; };
     Stream2 h;
-    h.f = e->f32("skip.0.f32", (size_t)Bn * side * side * mc);
-    h.h = wants_h(first_kind(e->input_blocks.size() > 1 ? &e->input_blocks[1] : nullptr)) ? e->h16("skip.0", (size_t)Bn * side * side * mc) : nullptr;
+    h.f = e->f32("skip.0.f32", (size_t)Bn * sh * sw * mc);
+    h.h = wants_h(first_kind(e->input_blocks.size() > 1 ? &e->input_blocks[1] : nullptr)) ? e->h16("skip.0", (size_t)Bn * sh * sw * mc) : nullptr;
     CKP(h.f);
-    CK(r.conv(xin, fc + ".w", fc + ".b", B0, side, side, CIN_PAD, 1, 0, h.f, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, nullptr, 0, 0, nullptr, 0, 0, h.h));
+    CK(r.conv(xin, fc + ".w", fc + ".b", B0, sh, sw, CIN_PAD, 1, 0, h.f, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, nullptr, 0, 0, nullptr, 0, 0, h.h));
     if (share) {            // skip-stack entry 0 is consumed at full batch by the last output block
-        CK(r.dup_rows(h.f, (size_t)B0 * side * side * mc * 4));
-        if (h.h) CK(r.dup_rows(h.h, (size_t)B0 * side * side * mc * 2));
+        CK(r.dup_rows(h.f, (size_t)B0 * sh * sw * mc * 4));
+        if (h.h) CK(r.dup_rows(h.h, (size_t)B0 * sh * sw * mc * 2));
     }
-    struct Skip { Stream2 s; int side, c; };
-    std::vector<Skip> skips{{h, side, mc}};
+    struct Skip { Stream2 s; int h, w, c; };
+    std::vector<Skip> skips{{h, sh, sw, mc}};
     int st_idx = 0;
     int h_c = mc;
 
@@ -949,58 +951,58 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
             if (l.kind == RES) {
                 if (half_first && j == 0) {
                     // the block's output tensors at FULL size first (the pool hands back the same buffers to the half-batch call below)
-                    CKP(e->f32(tag + ".f32", (size_t)Bn * side * side * l.cout));
-                    if (need_h) CKP(e->h16(tag, (size_t)Bn * side * side * l.cout));
+                    CKP(e->f32(tag + ".f32", (size_t)Bn * sh * sw * l.cout));
+                    if (need_h) CKP(e->h16(tag, (size_t)Bn * sh * sw * l.cout));
                     BnScope half(e, B0);
-                    CK(res_block(r, l, h, sk, sk_c, side, emb_out, tag, need_h, &o));
+                    CK(res_block(r, l, h, sk, sk_c, sh, sw, emb_out, tag, need_h, &o));
                     half_pending = true;
                 } else {
-                    CK(res_block(r, l, h, sk, sk_c, side, emb_out, tag, need_h, &o));
+                    CK(res_block(r, l, h, sk, sk_c, sh, sw, emb_out, tag, need_h, &o));
                 }
                 sk = nullptr; sk_c = 0;
             } else if (l.kind == ST) {
-                CK(spatial_transformer(r, l, st_idx++, h, side, fuser_on, tag, need_h, &o, half_pending));
+                CK(spatial_transformer(r, l, st_idx++, h, sh, sw, fuser_on, tag, need_h, &o, half_pending));
                 half_pending = false;       // the transformer duplicated its input and its own stream after attn1
             } else if (l.kind == DOWN) {
-                const int so = side / 2;
-                o.f = e->f32(tag + ".f32", (size_t)Bn * so * so * l.cout);
-                o.h = need_h ? e->h16(tag, (size_t)Bn * so * so * l.cout) : nullptr;
+                const int oh = sh / 2, ow = sw / 2;
+                o.f = e->f32(tag + ".f32", (size_t)Bn * oh * ow * l.cout);
+                o.h = need_h ? e->h16(tag, (size_t)Bn * oh * ow * l.cout) : nullptr;
                 CKP(o.f); CKP(h.h);
                 if (need_h) CKP(o.h);
                 const half_t* cin_ = h.h;
                 if (strict) {          // the stream tensor itself as [hi | lo] pixel rows
-                    half_t* hs = e->h16("conv.split", (size_t)Bn * side * side * 2 * l.cin);
+                    half_t* hs = e->h16("conv.split", (size_t)Bn * sh * sw * 2 * l.cin);
                     CKP(hs);
-                    CK(r.split(h.f, (int64_t)Bn * side * side, l.cin, hs));
+                    CK(r.split(h.f, (int64_t)Bn * sh * sw, l.cin, hs));
                     cin_ = hs;
                 }
-                CK(r.conv(cin_, l.prefix + ".w", l.prefix + ".b", Bn, side, side, l.cin, 2, 0, o.f, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, nullptr, 0, 0, nullptr,
+                CK(r.conv(cin_, l.prefix + ".w", l.prefix + ".b", Bn, sh, sw, l.cin, 2, 0, o.f, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, nullptr, 0, 0, nullptr,
                           0, 0, o.h, 0, strict));
-                side = so;
+                sh = oh; sw = ow;
             } else if (l.kind == UP) {
-                const int so = side * 2;
-                o.f = e->f32(tag + ".f32", (size_t)Bn * so * so * l.cout);
-                o.h = need_h ? e->h16(tag, (size_t)Bn * so * so * l.cout) : nullptr;
+                const int oh = sh * 2, ow = sw * 2;
+                o.f = e->f32(tag + ".f32", (size_t)Bn * oh * ow * l.cout);
+                o.h = need_h ? e->h16(tag, (size_t)Bn * oh * ow * l.cout) : nullptr;
                 CKP(o.f); CKP(h.h);
                 if (need_h) CKP(o.h);
                 const half_t* cin_ = h.h;
                 if (strict) {
-                    half_t* hs = e->h16("conv.split", (size_t)Bn * side * side * 2 * l.cin);
+                    half_t* hs = e->h16("conv.split", (size_t)Bn * sh * sw * 2 * l.cin);
                     CKP(hs);
-                    CK(r.split(h.f, (int64_t)Bn * side * side, l.cin, hs));
+                    CK(r.split(h.f, (int64_t)Bn * sh * sw, l.cin, hs));
                     cin_ = hs;
                 }
-                CK(r.conv(cin_, l.prefix + ".w", l.prefix + ".b", Bn, side, side, l.cin, 1, 1, o.f, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, nullptr, 0, 0, nullptr,
+                CK(r.conv(cin_, l.prefix + ".w", l.prefix + ".b", Bn, sh, sw, l.cin, 1, 1, o.f, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, nullptr, 0, 0, nullptr,
                           0, 0, o.h, 0, strict));
-                side = so;
+                sh = oh; sw = ow;
             } else {
                 return GL_ERR_BAD_ARG;
             }
             h = o;
             h_c = l.cout;
             if (half_pending && !(j + 1 < b.layers.size() && b.layers[j + 1].kind == ST)) {
-                CK(r.dup_rows(h.f, (size_t)B0 * side * side * h_c * 4));
-                if (h.h) CK(r.dup_rows(h.h, (size_t)B0 * side * side * h_c * 2));
+                CK(r.dup_rows(h.f, (size_t)B0 * sh * sw * h_c * 4));
+                if (h.h) CK(r.dup_rows(h.h, (size_t)B0 * sh * sw * h_c * 2));
                 half_pending = false;
             }
         }
@@ -1010,28 +1012,28 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
     for (size_t i = 1; i < e->input_blocks.size(); ++i) {
         CK(run_block(e->input_blocks[i], "skip." + std::to_string(i), nullptr, i + 1 < e->input_blocks.size() ? &e->input_blocks[i + 1] : &e->middle,
                      share && i == 1));
-        skips.push_back({h, side, h_c});
+        skips.push_back({h, sh, sw, h_c});
     }
     CK(run_block(e->middle, "mid", nullptr, e->output_blocks.empty() ? nullptr : &e->output_blocks[0]));
     for (size_t i = 0; i < e->output_blocks.size(); ++i) {
         const Skip sk = skips.back();
         skips.pop_back();
-        if (sk.side != side) return GL_ERR_BAD_ARG;
+        if (sk.h != sh || sk.w != sw) return GL_ERR_BAD_ARG;
         CK(run_block(e->output_blocks[i], "out." + std::to_string(i), &sk, i + 1 < e->output_blocks.size() ? &e->output_blocks[i + 1] : nullptr));
     }
     const int ocl = e->out_channels_last;
-    half_t* g = e->h16("fin.gn", (size_t)Bn * side * side * ocl * (strict ? 2 : 1));
+    half_t* g = e->h16("fin.gn", (size_t)Bn * sh * sw * ocl * (strict ? 2 : 1));
     CKP(g);
     if (strict) {
-        CK(r.gn(h.f, ocl, nullptr, 0, 1, Bn, side * side, "out.0", 1e-5f, 1, g, 2 * ocl, g + ocl));
+        CK(r.gn(h.f, ocl, nullptr, 0, 1, Bn, sh * sw, "out.0", 1e-5f, 1, g, 2 * ocl, g + ocl));
     } else if (precise) {
-        CK(r.gn(h.f, e->out_channels_last, nullptr, 0, 1, Bn, side * side, "out.0", 1e-5f, 1, g));
+        CK(r.gn(h.f, e->out_channels_last, nullptr, 0, 1, Bn, sh * sw, "out.0", 1e-5f, 1, g));
     } else {
         CKP(h.h);
-        CK(r.gn(h.h, e->out_channels_last, nullptr, 0, 0, Bn, side * side, "out.0", 1e-5f, 1, g));
+        CK(r.gn(h.h, e->out_channels_last, nullptr, 0, 0, Bn, sh * sw, "out.0", 1e-5f, 1, g));
     }
-    CK(r.conv(g, "out.2.w", "out.2.b", Bn, side, side, e->out_channels_last, 1, 0, eps, GL_OUT_F32_NCHW, GL_EPI_BIAS, nullptr, 0, 0, nullptr, 0, 0, nullptr,
-              side * side, strict));
+    CK(r.conv(g, "out.2.w", "out.2.b", Bn, sh, sw, e->out_channels_last, 1, 0, eps, GL_OUT_F32_NCHW, GL_EPI_BIAS, nullptr, 0, 0, nullptr, 0, 0, nullptr,
+              sh * sw, strict));
     if (n_launches) *n_launches = r.launches;
     return 0;
 }
@@ -1165,16 +1167,17 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
     return 0;
 }
 
-extern "C" int gl_set_conditioning(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
-                                   const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t hw, void* stream) {
-    if (!e || !e->wbase || !context || !relations || !boxes || !masks || !pos_emb || Bn <= 0 || Lc <= 0 || R <= 0 || hw <= 0) return GL_ERR_BAD_ARG;
+namespace {
+int set_conditioning(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks, const float* pos_emb,
+                     int32_t Bn, int32_t Lc, int32_t R, int32_t h, int32_t w, void* stream) {
+    if (!e || !e->wbase || !context || !relations || !boxes || !masks || !pos_emb || Bn <= 0 || Lc <= 0 || R <= 0 || h <= 0 || w <= 0) return GL_ERR_BAD_ARG;
     gl_opts_scope opts_scope(e->ovr);       // this handle's option overrides are in effect for the call
     const gl_unet_config& cfg = e->cfg;
     hipStream_t st = (hipStream_t)stream;
     const int mo = cfg.max_objs, ctx = cfg.context_dim, H = cfg.num_heads;
-    if (Bn != e->Bn || Lc != e->Lc || R != e->R || hw != e->hw) e->drop_graphs();     // shapes are part of the graph keys anyway
+    if (Bn != e->Bn || Lc != e->Lc || R != e->R || h != e->lat_h || w != e->lat_w) e->drop_graphs();     // shapes are part of the graph keys anyway
     e->pool_changed = false;
-    e->Bn = Bn; e->Lc = Lc; e->R = R; e->hw = hw;
+    e->Bn = Bn; e->Lc = Lc; e->R = R; e->lat_h = h; e->lat_w = w;
     Run r{e, st, e->buf("splitk.ws", WS_BYTES)};
     CKP(r.ws);
     // --- grounding tokens: PositionNet (text_grounding_net.py:26-43)
@@ -1238,22 +1241,22 @@ extern "C" int gl_set_conditioning(gl_engine* e, const float* context, const flo
     }
     // --- integer rectangles per transformer resolution (attention.py:321-346)
     {
-        std::vector<int> sides;
-        int cur = hw;
-        auto note = [&](int s) { for (int v : sides) if (v == s) return; sides.push_back(s); };
+        std::vector<std::pair<int, int>> sides;
+        int ch = h, cw = w;
+        auto note = [&](int a, int b) { for (auto& v : sides) if (v.first == a && v.second == b) return; sides.push_back({a, b}); };
         for (auto& b : e->input_blocks)
             for (auto& l : b.layers) {
-                if (l.kind == DOWN) cur /= 2;
-                else if (l.kind == ST) note(cur);
+                if (l.kind == DOWN) { ch /= 2; cw /= 2; }
+                else if (l.kind == ST) note(ch, cw);
             }
-        note(cur);
-        for (int s : sides) {
-            const std::string ss = std::to_string(s);
+        note(ch, cw);
+        for (auto& s : sides) {
+            const std::string ss = level_tag(s.first, s.second);
             int* rects = reinterpret_cast<int*>(e->buf("cond.rects." + ss, (size_t)Bn * mo * 16));
             int* nvalid = reinterpret_cast<int*>(e->buf("cond.nvalid." + ss, (size_t)Bn * 4));
             int* poison = reinterpret_cast<int*>(e->buf("cond.poison." + ss, (size_t)Bn * 4));
             CKP(rects); CKP(nvalid); CKP(poison);
-            rela_rects_kernel<<<dim3((Bn + 63) / 64), dim3(64), 0, st>>>(boxes, masks, Bn, mo, s, s, rects, nvalid, poison);
+            rela_rects_kernel<<<dim3((Bn + 63) / 64), dim3(64), 0, st>>>(boxes, masks, Bn, mo, s.first, s.second, rects, nvalid, poison);
             GL_CHECK_LAUNCH();
         }
         // Rows of the relation chain (attention.py:348-351 runs LN / cross-attention / FeedForward over all 30 rows of every sample; only
@@ -1265,7 +1268,7 @@ extern "C" int gl_set_conditioning(gl_engine* e, const float* context, const flo
             std::vector<int> nv((size_t)Bn * sides.size());
             int mx = 0;
             for (size_t k = 0; k < sides.size(); ++k) {
-                const int* nvalid = reinterpret_cast<const int*>(e->buf("cond.nvalid." + std::to_string(sides[k]), (size_t)Bn * 4));
+                const int* nvalid = reinterpret_cast<const int*>(e->buf("cond.nvalid." + level_tag(sides[k].first, sides[k].second), (size_t)Bn * 4));
                 CKP(nvalid);
                 if (hipMemcpyAsync(nv.data() + k * Bn, nvalid, (size_t)Bn * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return GL_ERR_BAD_ARG;
             }
@@ -1281,6 +1284,26 @@ extern "C" int gl_set_conditioning(gl_engine* e, const float* context, const flo
     e->cond_set = true;
     return 0;
 }
+}  // namespace
+
+extern "C" int gl_set_conditioning(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
+                                   const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t hw, void* stream) {
+    return set_conditioning(e, context, relations, boxes, masks, pos_emb, Bn, Lc, R, hw, hw, stream);
+}
+
+extern "C" int gl_set_conditioning_hw(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
+                                      const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t h, int32_t w, void* stream) {
+    if (!e) return GL_ERR_BAD_ARG;
+    // every DOWN halves both axes and every UP doubles them back: an axis that is not a multiple of 2^(number of downsamples) comes back
+    // shorter than the skip tensor it is concatenated with (the reference fails there too) -- rejected here, before anything is launched
+    int f = 1;
+    for (auto& b : e->input_blocks) for (auto& l : b.layers) if (l.kind == DOWN) f *= 2;
+    if (h <= 0 || w <= 0 || (h % f) != 0 || (w % f) != 0) {
+        e->err = "gl_set_conditioning_hw: h = " + std::to_string(h) + ", w = " + std::to_string(w) + " must be positive multiples of " + std::to_string(f);
+        return GL_ERR_BAD_ARG;
+    }
+    return set_conditioning(e, context, relations, boxes, masks, pos_emb, Bn, Lc, R, h, w, stream);
+}
 
 extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev, float t_host, int32_t reps, float fuser_scale, int32_t sd_conv,
                                float* eps, int32_t use_graph, void* stream) {
@@ -1289,9 +1312,10 @@ extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev,
     if (sd_conv && !e->has_sd) return GL_ERR_BAD_ARG;
     const gl_unet_config& cfg = e->cfg;
     hipStream_t st = (hipStream_t)stream;
-    const int Bn = e->Bn, side = e->hw;
-    const size_t nx = (size_t)(Bn / reps) * cfg.in_channels * side * side;
-    const size_t ne = (size_t)Bn * cfg.out_channels * side * side;
+    const int Bn = e->Bn;
+    const size_t hw = (size_t)e->lat_h * e->lat_w;
+    const size_t nx = (size_t)(Bn / reps) * cfg.in_channels * hw;
+    const size_t ne = (size_t)Bn * cfg.out_channels * hw;
     e->pool_changed = false;
     float* x_lat = e->f32("in.xlat", nx);
     float* t_buf = e->f32("in.t", Bn);
@@ -1318,7 +1342,7 @@ extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev,
         e->ovr_epoch = e->ovr.epoch;
     }
     const bool uniform_t = t_dev == nullptr;
-    const auto key = std::make_tuple(Bn, side, e->R, e->Lc, (int)fuser_on, (int)(sd_conv != 0), (int)reps + (uniform_t ? 16 : 0), e->rel_slots);
+    const auto key = std::make_tuple(Bn, e->lat_h, e->lat_w, e->R, e->Lc, (int)fuser_on, (int)(sd_conv != 0), (int)reps + (uniform_t ? 16 : 0), e->rel_slots);
     auto it = e->graphs.find(key);
     if (use_graph && it == e->graphs.end()) {
         // warm-up run allocates every pooled buffer, then the same launch sequence is captured
@@ -1359,8 +1383,8 @@ extern "C" int gl_plms_step(gl_engine* e, const gl_plms_step_args* a, void* stre
     const gl_unet_config& cfg = e->cfg;
     if (cfg.in_channels != cfg.out_channels) return GL_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    const int Bn = e->Bn, side = e->hw;
-    const size_t ne = (size_t)Bn * cfg.out_channels * side * side;
+    const int Bn = e->Bn;
+    const size_t ne = (size_t)Bn * cfg.out_channels * e->lat_h * e->lat_w;
     const size_t n = ne / a->reps;
     float* eps_i = e->f32("out.eps", ne);
     CKP(eps_i);

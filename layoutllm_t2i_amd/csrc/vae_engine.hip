@@ -6,7 +6,7 @@
 // (num_res_blocks + 1 ResnetBlocks each, nearest-2x upsample + conv between levels) -> GroupNorm(eps 1e-6) + swish ->
 // conv_out.  Like the UNet handle the engine owns the plan, the LIBRARY-DEFINED flat weight layout (gl_vae_weight_at: the
 // host packer fills it, the same buffer travels in the multi-GPU broadcast), a grow-only activation pool with stable
-// addresses and one hipGraph per (batch, latent side), captured on an engine-owned stream and replayed on the caller's.
+// addresses and one hipGraph per (batch, latent rows, latent columns), captured on an engine-owned stream and replayed on the caller's.
 // No new heavy kernels: every conv / 1x1 conv / GroupNorm goes through gl_conv3x3 / gl_gemm / gl_groupnorm (and therefore
 // through the 8-wave deep-pipelined kernel wherever its dispatch applies).
 //
@@ -21,6 +21,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -43,7 +44,7 @@ struct gl_vae {
     struct Buf { void* p; size_t bytes; };
     std::unordered_map<std::string, Buf> pool;
     bool pool_changed = false;
-    std::map<std::pair<int, int>, hipGraphExec_t> graphs;
+    std::map<std::tuple<int, int, int>, hipGraphExec_t> graphs;      // (B, h, w)
     hipStream_t cap_stream = nullptr;
     int launches = 0;
     int opt_epoch = 0;
@@ -106,6 +107,9 @@ void plan_resnet(gl_vae* v, const std::string& p, int cin, int cout) {
     if (cin != cout) { v->add(p + ".nin_shortcut.w", 0, {cout, cin}); v->add(p + ".nin_shortcut.b", 1, {cout}); }
 }
 
+// pool tags of per-resolution buffers carry rows x columns: 8x12 and 12x8 are different levels
+std::string lt(int h, int w) { return std::to_string(h) + "x" + std::to_string(w); }
+
 int gn_nchunk(int HW) {
     if (HW <= 4096) { int c = HW / 4; return c < 1 ? 1 : (c > 64 ? 64 : c); }
     const int c = HW / 512;
@@ -132,15 +136,16 @@ int v_gn(VRun& r, const half_t* x, int C, int HW, const std::string& p, bool sil
     return 0;
 }
 
-// down != 0: the encoder's Downsample (F.pad(x, (0, 1, 0, 1)) + stride-2 pad-0 conv, gl_conv3x3_pad01), side -> side / 2
-int v_conv(VRun& r, const half_t* x, int side, int cin, const std::string& p, int cout, int up, int epi, const void* res, void* out,
+// down != 0: the encoder's Downsample (F.pad(x, (0, 1, 0, 1)) + stride-2 pad-0 conv, gl_conv3x3_pad01), (h, w) -> (h / 2, w / 2)
+int v_conv(VRun& r, const half_t* x, int sh, int sw, int cin, const std::string& p, int cout, int up, int epi, const void* res, void* out,
            int out_mode = GL_OUT_F16_ROWMAJOR, int down = 0) {
     gl_vae* v = r.v;
     gl_conv_args a;
     memset(&a, 0, sizeof(a));
     a.in = x;
-    a.B = r.B; a.Hin = side; a.Win = side; a.Cin = cin;
-    a.Hout = up ? 2 * side : (down ? side / 2 : side); a.Wout = a.Hout;
+    a.B = r.B; a.Hin = sh; a.Win = sw; a.Cin = cin;
+    a.Hout = up ? 2 * sh : (down ? sh / 2 : sh);
+    a.Wout = up ? 2 * sw : (down ? sw / 2 : sw);
     a.stride = down ? 2 : 1; a.upsample2x = up;
     a.g.w = v->W<half_t>(p + ".w");
     a.g.bias = v->W<float>(p + ".b");
@@ -173,35 +178,36 @@ int v_gemm(VRun& r, const half_t* a_, int lda, const half_t* w, const float* bia
     return 0;
 }
 
-int v_resnet(VRun& r, const std::string& p, const half_t* x, int side, int cin, int cout, const std::string& tag, half_t** out) {
+int v_resnet(VRun& r, const std::string& p, const half_t* x, int sh, int sw, int cin, int cout, const std::string& tag, half_t** out) {
     gl_vae* v = r.v;
-    const int HW = side * side;
+    const int HW = sh * sw;
+    const std::string ss = lt(sh, sw);
     const size_t M = (size_t)r.B * HW;
     half_t *t1, *t2;
-    VCK(v_gn(r, x, cin, HW, p + ".norm1", true, "rn.gn." + std::to_string(cin) + "." + std::to_string(side), &t1));
-    half_t* h = v->f16("rn.h." + std::to_string(cout) + "." + std::to_string(side), M * cout);
+    VCK(v_gn(r, x, cin, HW, p + ".norm1", true, "rn.gn." + std::to_string(cin) + "." + ss, &t1));
+    half_t* h = v->f16("rn.h." + std::to_string(cout) + "." + ss, M * cout);
     VCKP(h);
-    VCK(v_conv(r, t1, side, cin, p + ".conv1", cout, 0, GL_EPI_BIAS, nullptr, h));
-    VCK(v_gn(r, h, cout, HW, p + ".norm2", true, "rn.gn." + std::to_string(cout) + "." + std::to_string(side), &t2));
+    VCK(v_conv(r, t1, sh, sw, cin, p + ".conv1", cout, 0, GL_EPI_BIAS, nullptr, h));
+    VCK(v_gn(r, h, cout, HW, p + ".norm2", true, "rn.gn." + std::to_string(cout) + "." + ss, &t2));
     const half_t* sk = x;
     if (cin != cout) {
-        half_t* s = v->f16("rn.sk." + std::to_string(cout) + "." + std::to_string(side), M * cout);
+        half_t* s = v->f16("rn.sk." + std::to_string(cout) + "." + ss, M * cout);
         VCKP(s);
         VCK(v_gemm(r, x, cin, v->W<half_t>(p + ".nin_shortcut.w"), v->W<float>(p + ".nin_shortcut.b"), (int)M, cout, cin, GL_EPI_BIAS, nullptr, s, cout));
         sk = s;
     }
     half_t* o = v->f16(tag, M * cout);
     VCKP(o);
-    VCK(v_conv(r, t2, side, cout, p + ".conv2", cout, 0, GL_EPI_RES, sk, o));
+    VCK(v_conv(r, t2, sh, sw, cout, p + ".conv2", cout, 0, GL_EPI_RES, sk, o));
     *out = o;
     return 0;
 }
 
 // single-head AttnBlock (model.py:150-202): d = C = 512 is beyond the flash kernel's register budget; Q.K^T (GEMM) -> row softmax
 // -> P.V (GEMM against V^T), per sample; C^-0.5 is folded into the q weights at pack time
-int v_attn(VRun& r, const std::string& p, const half_t* x, int side, int C, const std::string& tag, half_t** out) {
+int v_attn(VRun& r, const std::string& p, const half_t* x, int N, int C, const std::string& tag, half_t** out) {
     gl_vae* v = r.v;
-    const int N = side * side, B = r.B;
+    const int B = r.B;
     const size_t M = (size_t)B * N;
     half_t* hn;
     VCK(v_gn(r, x, C, N, p + ".norm", false, "at.gn", &hn));
@@ -234,106 +240,106 @@ int v_attn(VRun& r, const std::string& p, const half_t* x, int side, int C, cons
     return 0;
 }
 
-int launch_decode(gl_vae* v, int B, int side, hipStream_t st, int* launches) {
+int launch_decode(gl_vae* v, int B, int sh, int sw, hipStream_t st, int* launches) {
     const gl_vae_config& c = v->cfg;
     VRun r{v, st, B, launches};
     if (launches) *launches = 0;
     const int nres = c.n_mult;
     int ch = c.ch * c.ch_mult[nres - 1];
-    const float* z = v->f32("in.z", (size_t)B * c.z_channels * side * side);
+    const float* z = v->f32("in.z", (size_t)B * c.z_channels * sh * sw);
     VCKP(z);
-    half_t* xin = v->f16("in", (size_t)B * side * side * VCIN_PAD);
+    half_t* xin = v->f16("in", (size_t)B * sh * sw * VCIN_PAD);
     VCKP(xin);
     VCK(gl_latent_affine_pack(z, v->W<float>("post_quant_conv.w"), v->W<float>("post_quant_conv.b"), 1.0f / c.scale_factor, B, c.z_channels,
-                              side * side, VCIN_PAD, xin, st));
+                              sh * sw, VCIN_PAD, xin, st));
     r.count();
-    half_t* h = v->f16("conv_in", (size_t)B * side * side * ch);
+    half_t* h = v->f16("conv_in", (size_t)B * sh * sw * ch);
     VCKP(h);
-    VCK(v_conv(r, xin, side, VCIN_PAD, "decoder.conv_in", ch, 0, GL_EPI_BIAS, nullptr, h));
-    VCK(v_resnet(r, "decoder.mid.block_1", h, side, ch, ch, "mid.1", &h));
-    VCK(v_attn(r, "decoder.mid.attn_1", h, side, ch, "mid.a", &h));
-    VCK(v_resnet(r, "decoder.mid.block_2", h, side, ch, ch, "mid.2", &h));
+    VCK(v_conv(r, xin, sh, sw, VCIN_PAD, "decoder.conv_in", ch, 0, GL_EPI_BIAS, nullptr, h));
+    VCK(v_resnet(r, "decoder.mid.block_1", h, sh, sw, ch, ch, "mid.1", &h));
+    VCK(v_attn(r, "decoder.mid.attn_1", h, sh * sw, ch, "mid.a", &h));
+    VCK(v_resnet(r, "decoder.mid.block_2", h, sh, sw, ch, ch, "mid.2", &h));
     for (int lvl = nres - 1; lvl >= 0; --lvl) {
         const int cout = c.ch * c.ch_mult[lvl];
         for (int i = 0; i <= c.num_res_blocks; ++i) {
-            VCK(v_resnet(r, "decoder.up." + std::to_string(lvl) + ".block." + std::to_string(i), h, side, ch, cout,
+            VCK(v_resnet(r, "decoder.up." + std::to_string(lvl) + ".block." + std::to_string(i), h, sh, sw, ch, cout,
                          "up." + std::to_string(lvl) + "." + std::to_string(i), &h));
             ch = cout;
         }
         if (lvl != 0) {
-            half_t* u = v->f16("up." + std::to_string(lvl) + ".u", (size_t)B * 4 * side * side * ch);
+            half_t* u = v->f16("up." + std::to_string(lvl) + ".u", (size_t)B * 4 * sh * sw * ch);
             VCKP(u);
-            VCK(v_conv(r, h, side, ch, "decoder.up." + std::to_string(lvl) + ".upsample.conv", ch, 1, GL_EPI_BIAS, nullptr, u));
+            VCK(v_conv(r, h, sh, sw, ch, "decoder.up." + std::to_string(lvl) + ".upsample.conv", ch, 1, GL_EPI_BIAS, nullptr, u));
             h = u;
-            side *= 2;
+            sh *= 2; sw *= 2;
         }
     }
     half_t* g;
-    VCK(v_gn(r, h, ch, side * side, "decoder.norm_out", true, "fin.gn", &g));
-    float* out = v->f32("out", (size_t)B * c.out_ch * side * side);
+    VCK(v_gn(r, h, ch, sh * sw, "decoder.norm_out", true, "fin.gn", &g));
+    float* out = v->f32("out", (size_t)B * c.out_ch * sh * sw);
     VCKP(out);
-    VCK(v_conv(r, g, side, ch, "decoder.conv_out", c.out_ch, 0, GL_EPI_BIAS, nullptr, out, GL_OUT_F32_NCHW));
+    VCK(v_conv(r, g, sh, sw, ch, "decoder.conv_out", c.out_ch, 0, GL_EPI_BIAS, nullptr, out, GL_OUT_F32_NCHW));
     return 0;
 }
 
 // Encoder.forward (model.py:428-459) + quant_conv + posterior sample: x fp32 NCHW image ("in.x") -> z fp32 NCHW ("out.z")
-int launch_encode(gl_vae* v, int B, int side, hipStream_t st, int* launches) {
+int launch_encode(gl_vae* v, int B, int sh, int sw, hipStream_t st, int* launches) {
     const gl_vae_config& c = v->cfg;
     VRun r{v, st, B, launches};
     if (launches) *launches = 0;
     const int nres = c.n_mult;
-    const float* x = v->f32("in.x", (size_t)B * c.out_ch * side * side);
-    half_t* xin = v->f16("in", (size_t)B * side * side * VCIN_PAD);
+    const float* x = v->f32("in.x", (size_t)B * c.out_ch * sh * sw);
+    half_t* xin = v->f16("in", (size_t)B * sh * sw * VCIN_PAD);
     VCKP(x); VCKP(xin);
-    VCK(gl_pack_latent(x, B, c.out_ch, side * side, VCIN_PAD, 1, 0, xin, st));
+    VCK(gl_pack_latent(x, B, c.out_ch, sh * sw, VCIN_PAD, 1, 0, xin, st));
     r.count();
     int ch = c.ch;
-    half_t* h = v->f16("conv_in", (size_t)B * side * side * ch);
+    half_t* h = v->f16("conv_in", (size_t)B * sh * sw * ch);
     VCKP(h);
-    VCK(v_conv(r, xin, side, VCIN_PAD, "encoder.conv_in", ch, 0, GL_EPI_BIAS, nullptr, h));
+    VCK(v_conv(r, xin, sh, sw, VCIN_PAD, "encoder.conv_in", ch, 0, GL_EPI_BIAS, nullptr, h));
     for (int lvl = 0; lvl < nres; ++lvl) {
         const int cout = c.ch * c.ch_mult[lvl];
         for (int i = 0; i < c.num_res_blocks; ++i) {
-            VCK(v_resnet(r, "encoder.down." + std::to_string(lvl) + ".block." + std::to_string(i), h, side, ch, cout,
+            VCK(v_resnet(r, "encoder.down." + std::to_string(lvl) + ".block." + std::to_string(i), h, sh, sw, ch, cout,
                          "down." + std::to_string(lvl) + "." + std::to_string(i), &h));
             ch = cout;
         }
         if (lvl != nres - 1) {
-            half_t* d = v->f16("down." + std::to_string(lvl) + ".d", (size_t)B * (side / 2) * (side / 2) * ch);
+            half_t* d = v->f16("down." + std::to_string(lvl) + ".d", (size_t)B * (sh / 2) * (sw / 2) * ch);
             VCKP(d);
-            VCK(v_conv(r, h, side, ch, "encoder.down." + std::to_string(lvl) + ".downsample.conv", ch, 0, GL_EPI_BIAS, nullptr, d,
+            VCK(v_conv(r, h, sh, sw, ch, "encoder.down." + std::to_string(lvl) + ".downsample.conv", ch, 0, GL_EPI_BIAS, nullptr, d,
                        GL_OUT_F16_ROWMAJOR, 1));
             h = d;
-            side /= 2;
+            sh /= 2; sw /= 2;
         }
     }
-    VCK(v_resnet(r, "encoder.mid.block_1", h, side, ch, ch, "mid.1", &h));
-    VCK(v_attn(r, "encoder.mid.attn_1", h, side, ch, "mid.a", &h));
-    VCK(v_resnet(r, "encoder.mid.block_2", h, side, ch, ch, "mid.2", &h));
+    VCK(v_resnet(r, "encoder.mid.block_1", h, sh, sw, ch, ch, "mid.1", &h));
+    VCK(v_attn(r, "encoder.mid.attn_1", h, sh * sw, ch, "mid.a", &h));
+    VCK(v_resnet(r, "encoder.mid.block_2", h, sh, sw, ch, ch, "mid.2", &h));
     half_t* g;
-    VCK(v_gn(r, h, ch, side * side, "encoder.norm_out", true, "fin.gn", &g));
-    const int hw = side * side, zc2 = 2 * c.z_channels;
+    VCK(v_gn(r, h, ch, sh * sw, "encoder.norm_out", true, "fin.gn", &g));
+    const int hw = sh * sw, zc2 = 2 * c.z_channels;
     float* mom = v->f32("enc.h", (size_t)B * zc2 * hw);
     float* noise = v->f32("in.noise", (size_t)B * c.embed_dim * hw);
     float* z = v->f32("out.z", (size_t)B * c.embed_dim * hw);
     VCKP(mom); VCKP(noise); VCKP(z);
-    VCK(v_conv(r, g, side, ch, "encoder.conv_out", zc2, 0, GL_EPI_BIAS, nullptr, mom, GL_OUT_F32_NCHW));
+    VCK(v_conv(r, g, sh, sw, ch, "encoder.conv_out", zc2, 0, GL_EPI_BIAS, nullptr, mom, GL_OUT_F32_NCHW));
     VCK(gl_vae_posterior(mom, v->W<float>("quant_conv.w"), v->W<float>("quant_conv.b"), noise, c.scale_factor, B, zc2, c.embed_dim, hw, z,
                          nullptr, st));
     r.count();
     return 0;
 }
 
-// Shared by gl_vae_decode / gl_vae_encode once the inputs sit in the pool: eager launch, or one hipGraph per (B, side) (warm-up run
+// Shared by gl_vae_decode / gl_vae_encode once the inputs sit in the pool: eager launch, or one hipGraph per (B, h, w) (warm-up run
 // that allocates every pooled buffer and produces this call's result, then capture; replay afterwards).
 template <typename Launch>
-int run_plan(gl_vae* v, int B, int side, int use_graph, hipStream_t st, Launch launch) {
+int run_plan(gl_vae* v, int B, int sh, int sw, int use_graph, hipStream_t st, Launch launch) {
     if (v->opt_epoch != g_gl_option_epoch || v->ovr_epoch != v->ovr.epoch) {
         v->drop_graphs();
         v->opt_epoch = g_gl_option_epoch;
         v->ovr_epoch = v->ovr.epoch;
     }
-    const auto key = std::make_pair((int)B, (int)side);
+    const auto key = std::make_tuple((int)B, (int)sh, (int)sw);
     auto it = v->graphs.find(key);
     if (use_graph && it == v->graphs.end()) {
         VCK(launch(st, &v->launches));        // warm-up: allocates every pooled buffer
@@ -439,14 +445,18 @@ extern "C" int gl_vae_encoder_create(const gl_vae_config* cfg, gl_vae** out) {
 }
 
 extern "C" int gl_vae_encode(gl_vae* v, const float* x, int32_t B, int32_t side, const float* noise, float* z, int32_t use_graph, void* stream) {
-    if (!v || !x || !noise || !z || B <= 0 || B >= 2048 || side <= 0 || side >= 1024 || !v->wbase || !v->encoder) return GL_ERR_BAD_ARG;
+    return gl_vae_encode_hw(v, x, B, side, side, noise, z, use_graph, stream);
+}
+
+extern "C" int gl_vae_encode_hw(gl_vae* v, const float* x, int32_t B, int32_t h, int32_t w, const float* noise, float* z, int32_t use_graph,
+                                void* stream) {
+    if (!v || !x || !noise || !z || B <= 0 || B >= 2048 || h <= 0 || h >= 1024 || w <= 0 || w >= 1024 || !v->wbase || !v->encoder) return GL_ERR_BAD_ARG;
     const gl_vae_config& c = v->cfg;
     const int f = 1 << (c.n_mult - 1);
-    if (side % f) return GL_ERR_BAD_ARG;
+    if ((h % f) || (w % f)) return GL_ERR_BAD_ARG;
     gl_opts_scope opts_scope(v->ovr);
     hipStream_t st = (hipStream_t)stream;
-    const int zs = side / f;
-    const size_t nx = (size_t)B * c.out_ch * side * side, nz = (size_t)B * c.embed_dim * zs * zs;
+    const size_t nx = (size_t)B * c.out_ch * h * w, nz = (size_t)B * c.embed_dim * (h / f) * (w / f);
     v->pool_changed = false;
     float* xin = v->f32("in.x", nx);
     float* nin = v->f32("in.noise", nz);
@@ -454,7 +464,7 @@ extern "C" int gl_vae_encode(gl_vae* v, const float* x, int32_t B, int32_t side,
     VCKP(xin); VCKP(nin); VCKP(zbuf);
     if (hipMemcpyAsync(xin, x, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
     if (hipMemcpyAsync(nin, noise, nz * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
-    VCK(run_plan(v, B, side, use_graph, st, [&](hipStream_t s, int* nl) { return launch_encode(v, B, side, s, nl); }));
+    VCK(run_plan(v, B, h, w, use_graph, st, [&](hipStream_t s, int* nl) { return launch_encode(v, B, h, w, s, nl); }));
     if (hipMemcpyAsync(z, zbuf, nz * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
     return 0;
 }
@@ -491,20 +501,23 @@ extern "C" int gl_vae_load_weights(gl_vae* v, const void* packed, int64_t bytes,
 }
 
 extern "C" int gl_vae_decode(gl_vae* v, const float* z, int32_t B, int32_t side, float* out, int32_t use_graph, void* stream) {
-    if (!v || !z || !out || B <= 0 || side <= 0 || !v->wbase || v->encoder) return GL_ERR_BAD_ARG;
+    return gl_vae_decode_hw(v, z, B, side, side, out, use_graph, stream);
+}
+
+extern "C" int gl_vae_decode_hw(gl_vae* v, const float* z, int32_t B, int32_t h, int32_t w, float* out, int32_t use_graph, void* stream) {
+    if (!v || !z || !out || B <= 0 || h <= 0 || w <= 0 || !v->wbase || v->encoder) return GL_ERR_BAD_ARG;
     gl_opts_scope opts_scope(v->ovr);
     const gl_vae_config& c = v->cfg;
     hipStream_t st = (hipStream_t)stream;
-    const size_t nz = (size_t)B * c.z_channels * side * side;
-    int oside = side;
-    for (int l = 1; l < c.n_mult; ++l) oside *= 2;
-    const size_t no = (size_t)B * c.out_ch * oside * oside;
+    const size_t nz = (size_t)B * c.z_channels * h * w;
+    const size_t f = (size_t)1 << (c.n_mult - 1);
+    const size_t no = (size_t)B * c.out_ch * (f * h) * (f * w);
     v->pool_changed = false;
     float* zin = v->f32("in.z", nz);
     float* obuf = v->f32("out", no);
     VCKP(zin); VCKP(obuf);
     if (hipMemcpyAsync(zin, z, nz * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
-    VCK(run_plan(v, B, side, use_graph, st, [&](hipStream_t s, int* nl) { return launch_decode(v, B, side, s, nl); }));
+    VCK(run_plan(v, B, h, w, use_graph, st, [&](hipStream_t s, int* nl) { return launch_decode(v, B, h, w, s, nl); }));
     if (hipMemcpyAsync(out, obuf, no * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
     return 0;
 }

@@ -23,6 +23,14 @@ from .weights import PackedWeights
 F16, F32 = torch.float16, torch.float32
 
 
+def check_latent_hw(cfg: UNetConfig, h: int, w: int) -> None:
+    """The shape rule of a rectangular latent (gl_set_conditioning_hw): rows and columns each a positive multiple of
+    2^(number of downsamples) -- with fewer, an upsampled map no longer matches the skip tensor it is concatenated with."""
+    f = 2 ** (len(cfg.channel_mult) - 1)
+    if h <= 0 or w <= 0 or h % f or w % f:
+        raise ValueError(f"latent shape {h} x {w}: rows and columns must each be a positive multiple of {f}")
+
+
 class UNetEngine:
     def __init__(self, packed: PackedWeights):
         if not torch.cuda.is_available():
@@ -85,10 +93,17 @@ class UNetEngine:
 
     # ------------------------------------------------------------------ conditioning (once per image)
     @torch.no_grad()
-    def set_conditioning(self, context, relations, boxes, masks, positive_embeddings, hw: int) -> None:
+    def set_conditioning(self, context, relations, boxes, masks, positive_embeddings, hw) -> None:
         """context [Bn,77,ctx], relations [Bn,R,ctx], boxes [Bn,30,4], masks [Bn,30],
         positive_embeddings [Bn,30,in_dim]: fp32 tensors (any device).  Null grounding = zeros
-        (text_layout_tokinzer_input.py:47-62).  ``hw`` = latent side (64 for 512x512)."""
+        (text_layout_tokinzer_input.py:47-62).  ``hw`` = latent side (64 for 512x512; gl_set_conditioning), or ``(h, w)`` = latent rows
+        and columns (gl_set_conditioning_hw): each a multiple of 2^(number of downsamples), else ValueError before anything is launched."""
+        rect = not isinstance(hw, int)
+        if rect:
+            h, w = (int(v) for v in hw)
+            check_latent_hw(self.cfg, h, w)
+        else:
+            h = w = hw
         dev = self.dev
         f32 = lambda t: torch.as_tensor(t, dtype=F32).to(dev).contiguous()
         context, relations = f32(context), f32(relations)
@@ -102,33 +117,37 @@ class UNetEngine:
             raise ValueError("conditioning batch sizes differ")
         R, Lc = relations.shape[1], context.shape[1]
         with torch.cuda.device(dev):
-            check(self._lib.gl_set_conditioning(self.handle, context.data_ptr(), relations.data_ptr(), boxes.data_ptr(), masks.data_ptr(),
-                                                pe.data_ptr(), Bn, Lc, R, hw, self._stream()), "gl_set_conditioning")
+            if rect:
+                check(self._lib.gl_set_conditioning_hw(self.handle, context.data_ptr(), relations.data_ptr(), boxes.data_ptr(), masks.data_ptr(),
+                                                       pe.data_ptr(), Bn, Lc, R, h, w, self._stream()), "gl_set_conditioning_hw")
+            else:
+                check(self._lib.gl_set_conditioning(self.handle, context.data_ptr(), relations.data_ptr(), boxes.data_ptr(), masks.data_ptr(),
+                                                    pe.data_ptr(), Bn, Lc, R, hw, self._stream()), "gl_set_conditioning")
         self._cond_refs = (context, relations, boxes, masks, pe)      # read asynchronously by the launched kernels
-        self.cond = dict(Bn=Bn, mo=mo, R=R, Lc=Lc, hw=hw)
+        self.cond = dict(Bn=Bn, mo=mo, R=R, Lc=Lc, hw=hw, H=h, W=w)
 
     # ------------------------------------------------------------------ forward
     def _check_x(self, x_lat: torch.Tensor, reps: int):
         c = self.cond
         if c is None:
             raise RuntimeError("call set_conditioning() first")
-        Bn, side = c["Bn"], c["hw"]
-        if x_lat.shape[0] * reps != Bn or x_lat.shape[-1] != side or x_lat.shape[1] != self.cfg.in_channels:
-            raise ValueError(f"latent batch {tuple(x_lat.shape)} x reps {reps} does not match conditioning batch {Bn} @ {side}")
+        Bn, H, W = c["Bn"], c["H"], c["W"]
+        if x_lat.dim() != 4 or x_lat.shape[0] * reps != Bn or tuple(x_lat.shape[-2:]) != (H, W) or x_lat.shape[1] != self.cfg.in_channels:
+            raise ValueError(f"latent batch {tuple(x_lat.shape)} x reps {reps} does not match conditioning batch {Bn} @ {H} x {W}")
         if not x_lat.is_cuda or x_lat.dtype != F32 or not x_lat.is_contiguous():
             raise _lib.HipLibraryError("latent must be a contiguous fp32 GPU tensor (the HIP path has no CPU fallback)")
-        return Bn, side
+        return Bn, H, W
 
     @torch.no_grad()
     def forward(self, x_lat: torch.Tensor, t, fuser_scale: float = 1.0, sd_conv: bool = False, reps: int = 1,
                 eps_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x_lat fp32 [Bn/reps, 4, hw, hw] (NCHW, like the reference); returns eps fp32 [Bn, 4, hw, hw].
+        """x_lat fp32 [Bn/reps, 4, h, w] (NCHW, like the reference); returns eps fp32 [Bn, 4, h, w].
         With reps=2 the latent is shared by both CFG halves of a [cond ; uncond] conditioning batch."""
-        Bn, side = self._check_x(x_lat, reps)
+        Bn, H, W = self._check_x(x_lat, reps)
         if sd_conv and not self.P.has_sd_conv:
             raise RuntimeError("SD first-conv weights were not packed")
         if eps_out is None:
-            eps_out = self.buf("out.eps", (Bn, self.cfg.out_channels, side, side), F32)
+            eps_out = self.buf("out.eps", (Bn, self.cfg.out_channels, H, W), F32)
         t_dev, t_host, keep = None, 0.0, None
         if torch.is_tensor(t):
             if t.numel() == 1:

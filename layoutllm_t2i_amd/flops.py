@@ -9,7 +9,8 @@ from __future__ import annotations
 from .arch import UNetConfig, VAEConfig, build_plan
 
 
-def unet_forward_flops(cfg: UNetConfig, hw: int, fuser_on: bool = True, n_ctx: int = 77, n_rel: int = 10) -> float:
+def unet_forward_flops(cfg: UNetConfig, hw, fuser_on: bool = True, n_ctx: int = 77, n_rel: int = 10) -> float:
+    """``hw``: the latent side, or (h, w) for a rectangular latent (both multiples of 2^(number of downsamples))."""
     plan = build_plan(cfg)
     mo, ctx, te = cfg.max_objs, cfg.context_dim, cfg.time_embed_dim
     f = 0.0
@@ -20,10 +21,10 @@ def unet_forward_flops(cfg: UNetConfig, hw: int, fuser_on: bool = True, n_ctx: i
 
     f += lin(1, cfg.model_channels, te) + lin(1, te, te)
     f += lin(mo, cfg.pos_in_dim + cfg.position_dim, 512) + lin(mo, 512, 512) + lin(mo, 512, cfg.pos_out_dim)
-    side = hw
+    side = (hw, hw) if isinstance(hw, int) else tuple(int(v) for v in hw)
 
     def layer(l, side):
-        n = side * side
+        n = side[0] * side[1]
         g = 0.0
         if l.kind == "conv_in":
             g += lin(n, 9 * l.cin, l.cout)
@@ -53,25 +54,26 @@ def unet_forward_flops(cfg: UNetConfig, hw: int, fuser_on: bool = True, n_ctx: i
         for l in b.layers:
             f += layer(l, side)
             if l.kind == "down":
-                side //= 2
+                side = (side[0] // 2, side[1] // 2)
     for l in plan.middle.layers:
         f += layer(l, side)
     for b in plan.output_blocks:
         for l in b.layers:
             f += layer(l, side)
             if l.kind == "up":
-                side *= 2
-    f += lin(side * side, 9 * plan.out_channels_last, cfg.out_channels)
+                side = (side[0] * 2, side[1] * 2)
+    f += lin(side[0] * side[1], 9 * plan.out_channels_last, cfg.out_channels)
     return f
 
 
-def vae_encoder_flops(cfg: VAEConfig, B: int, side: int) -> float:
-    """AutoencoderKL.encode of B images of side x side (Encoder model.py:428-459 + quant_conv), 2 x MACs of every conv / 1x1 /
+def vae_encoder_flops(cfg: VAEConfig, B: int, side) -> float:
+    """AutoencoderKL.encode of B images of side x side, or of H x W with side = (H, W) (Encoder model.py:428-459 + quant_conv), 2 x MACs of every conv / 1x1 /
     attention product: 1.1 TFLOP per 512x512 image at the real config."""
     lin = lambda m, k, n: 2.0 * m * k * n
     f = 0.0
     ch = cfg.ch
-    f += lin(side * side, 9 * cfg.out_ch, ch)                   # conv_in
+    sh, sw = (side, side) if isinstance(side, int) else (int(v) for v in side)
+    f += lin(sh * sw, 9 * cfg.out_ch, ch)                       # conv_in
 
     def resnet(n, cin, cout):
         g = lin(n, 9 * cin, cout) + lin(n, 9 * cout, cout)
@@ -80,12 +82,12 @@ def vae_encoder_flops(cfg: VAEConfig, B: int, side: int) -> float:
     for lvl in range(nres):
         cout = cfg.ch * cfg.ch_mult[lvl]
         for _ in range(cfg.num_res_blocks):
-            f += resnet(side * side, ch, cout)
+            f += resnet(sh * sw, ch, cout)
             ch = cout
         if lvl != nres - 1:
-            side //= 2
-            f += lin(side * side, 9 * ch, ch)                   # pad01 downsample
-    n = side * side
+            sh, sw = sh // 2, sw // 2
+            f += lin(sh * sw, 9 * ch, ch)                       # pad01 downsample
+    n = sh * sw
     f += 2 * resnet(n, ch, ch) + 4 * lin(n, ch, ch) + 2.0 * 2.0 * n * n * ch     # mid: 2 ResnetBlocks, q / k / v / proj_out, QK^T + PV
     f += lin(n, 9 * ch, 2 * cfg.z_channels) + lin(n, 2 * cfg.z_channels, 2 * cfg.embed_dim)
     return B * f

@@ -7,6 +7,9 @@ App-B#9), so only its entry-point name and argument meaning are kept; semantics 
 
     run(meta, config, starting_noise=None) -> list[PIL.Image]
 
+``config`` may carry ``height`` / ``width`` (pixels, multiples of 64; default: the 64 x 64 latent, 512 pixels): they size the starting noise when none is passed;
+a passed ``starting_noise`` [bs, 4, h, w] decides the shape itself (image = 8h x 8w).
+
 ``meta``: ``ckpt`` (path), ``prompt``, ``phrases``, ``locations`` (ltrb, normalised), optional
 ``alpha_type``, ``save_folder_name``; ``config``: object/dict with ``batch_size``, ``guidance_scale``,
 ``no_plms`` (must be False), optional ``folder``.  Images are saved like the reference does
@@ -49,7 +52,8 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     m = dict(prompt=meta["prompt"], phrases=meta.get("phrases"), locations=meta["locations"],
              alpha_type=meta.get("alpha_type", [0.3, 0.0, 0.7]), input_image=meta.get("input_image"))
     if starting_noise is None:
-        starting_noise = torch.randn(bs, 4, 64, 64).to(device)
+        h, w = interface.latent_hw(_get(config, "height"), _get(config, "width"), all_models[1])
+        starting_noise = torch.randn(bs, 4, h, w).to(device)
     if clip_model is None or clip_processor is None:
         from transformers import CLIPModel, CLIPProcessor
         version = "openai/clip-vit-large-patch14"

@@ -102,18 +102,23 @@ def step_coefs(sched: Dict[str, np.ndarray], index: int) -> Tuple[float, float, 
     return (float(np.sqrt(a_t)), float(s1m), float(np.sqrt(a_prev)), float(np.sqrt(np.float32(1.0) - a_prev)))
 
 
-def draw_masks_from_boxes(boxes, size: int):
+def draw_masks_from_boxes(boxes, size):
     """inpaint_mask_func.py:16-41 with randomize_fg_mask / random_add_bg_mask off: per sample a [size, size] mask of ones (1 = keep)
     with every box's rectangle set to 0 (regenerate).  Box coordinates (ltrb, normalised) are scaled in float32 and truncated with
     int(); the rectangle is the python slice [y0:y1, x0:x1], so all-zero, reversed and sub-pixel boxes change nothing and negative
-    ends count from the far side.  Returns a CPU float32 torch tensor [B, 1, size, size]."""
+    ends count from the far side.  Returns a CPU float32 torch tensor [B, 1, size, size].
+
+    ``size`` = ``(H, W)`` (this project's extension; the reference function is square only): x0, x1 are int() of the float32 product
+    with W, y0, y1 of the product with H -> [B, 1, H, W].  For H == W that is the square function, bit for bit."""
     import torch
     if torch.is_tensor(boxes):
         boxes = boxes.detach().cpu().numpy()
     boxes = np.asarray(boxes, dtype=np.float32)
-    out = np.ones((boxes.shape[0], 1, size, size), np.float32)
+    H, W = (size, size) if isinstance(size, (int, np.integer)) else (int(v) for v in size)
+    scale = np.array([W, H, W, H], np.float32)
+    out = np.ones((boxes.shape[0], 1, H, W), np.float32)
     for k, box in enumerate(boxes):
         for bx in box:
-            x0, y0, x1, y1 = (int(v) for v in bx * np.float32(size))
+            x0, y0, x1, y1 = (int(v) for v in bx * scale)
             out[k, 0, y0:y1, x0:x1] = 0
     return torch.from_numpy(out)

@@ -353,12 +353,14 @@ def _vae_factor(autoencoder) -> int:
     return 2 ** (len(cfg.ch_mult) - 1) if cfg is not None else 8
 
 
-def load_input_image(image, side: int, device=None) -> torch.Tensor:
+def load_input_image(image, side, device=None) -> torch.Tensor:
     """gligen_inference.py:400-401 at any size: ``Image.open(path).convert("RGB").resize((side, side))`` (or that of a
-    ``PIL.Image``), pil_to_tensor, then ``(x / 255 - 0.5) / 0.5`` in fp32 on ``device`` -> [1, 3, side, side]."""
+    ``PIL.Image``), pil_to_tensor, then ``(x / 255 - 0.5) / 0.5`` in fp32 on ``device`` -> [1, 3, side, side].  ``side`` may be
+    ``(H, W)``: the image is resized to PIL's (W, H) -> [1, 3, H, W]."""
     from PIL import Image
+    H, W = (side, side) if isinstance(side, int) else (int(v) for v in side)
     im = image if isinstance(image, Image.Image) else Image.open(image)
-    im = im.convert("RGB").resize((side, side))
+    im = im.convert("RGB").resize((W, H))
     x = torch.from_numpy(np.array(im, dtype=np.uint8)).permute(2, 0, 1).contiguous()       # torchvision pil_to_tensor
     return (x.float().unsqueeze(0).to(device) / 255 - 0.5) / 0.5
 
@@ -367,9 +369,11 @@ def load_input_image(image, side: int, device=None) -> torch.Tensor:
 def denoise(all_models, context, uc, relations, grounding_batch, starting_noise, alpha_type=None, guidance_scale=7.5,
             steps=PLMS_STEPS, mask=None, x0=None):
     """The denoising hot path proper, from conditioning tensors to the final latent
-    (run_batch_images lines interface.py:505-539 without text/VAE stages).  ``mask`` [1|B, 1, L, L] (1 = keep) and ``x0``
-    [1|B, 4, L, L] (the encoded input image): inpainting, plms.py:95-99."""
+    (run_batch_images lines interface.py:505-539 without text/VAE stages).  ``mask`` [1|B, 1, h, w] (1 = keep) and ``x0``
+    [1|B, 4, h, w] (the encoded input image): inpainting, plms.py:95-99.  The latent's shape [B, 4, h, w] is ``starting_noise``'s
+    (plms.py:68-71); h != w needs both to be multiples of 2^(number of UNet downsamples) = 8."""
     model, autoencoder, text_encoder, diffusion, config = all_models
+    _check_noise(model, starting_noise)
     sampler = PLMSSampler(diffusion, model, alpha_generator_func=partial(alpha_generator, type=alpha_type),
                           set_alpha_scale=set_alpha_scale)
     grounding_input = model.grounding_tokenizer_input.prepare(grounding_batch, text_encoder)
@@ -379,8 +383,16 @@ def denoise(all_models, context, uc, relations, grounding_batch, starting_noise,
     return sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=mask, x0=x0)
 
 
+def _check_noise(model, starting_noise) -> None:
+    """A rectangular starting noise that breaks the engine's shape rule is refused here, before any encoder or kernel runs."""
+    if torch.is_tensor(starting_noise) and starting_noise.dim() == 4 and starting_noise.shape[-2] != starting_noise.shape[-1]:
+        from .engine import check_latent_hw
+        check_latent_hw(model.cfg, int(starting_noise.shape[-2]), int(starting_noise.shape[-1]))
+
+
 def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple):
     model, autoencoder, text_encoder, diffusion, config = all_models
+    _check_noise(model, starting_noise)
     config.update(args)                      # mutates the caller's dict, like interface.py:297/484
     cfg = _AttrDict(config)
     if cfg.get("no_plms", False):
@@ -399,8 +411,8 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     mask = z0 = None
     if meta.get("input_image") is not None:
         # inpainting (gligen_inference.py:393-407): encode the input image, regenerate inside the boxes (mask 0), keep the rest
-        L = starting_noise.shape[-1]
-        side = _vae_factor(autoencoder) * L
+        L = tuple(int(v) for v in starting_noise.shape[-2:])              # latent (h, w); the image is vae_factor times that per axis
+        side = tuple(_vae_factor(autoencoder) * v for v in L)
         ims = meta["input_image"]
         if isinstance(ims, (list, tuple)):
             if len(ims) != bs:
@@ -428,22 +440,49 @@ def run_batch_images(all_models, args, meta, starting_noise=None, clip_model=Non
     return _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple=True)
 
 
+def latent_hw(height=None, width=None, autoencoder=None):
+    """Latent (h, w) of a ``height`` x ``width`` pixel image: each a positive multiple of 8 * vae_factor (the UNet halves the latent three
+    times, the VAE scales it by vae_factor = 8: multiples of 64 pixels), else ValueError.  None = the reference's 64 latent rows / columns
+    (interface.py:388, :566), 512 pixels with the shipped VAE."""
+    f = _vae_factor(autoencoder)
+    height, width = (64 * f if v is None else v for v in (height, width))
+    for name, v in (("height", height), ("width", width)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0 or v % (8 * f):
+            raise ValueError(f"{name} = {v!r}: must be a positive multiple of {8 * f} pixels")
+    return int(height) // f, int(width) // f
+
+
 def generate_one_image(all_models, caption, label, bbox, clip_model=None, clip_processor=None, device=None):
-    """interface.py:376-395 (converts xywh -> ltrb, :383)."""
+    """interface.py:376-395 (converts xywh -> ltrb, :383): the reference's signature and its 512 x 512 image."""
+    return generate_one_image_sized(all_models, caption, label, bbox, clip_model, clip_processor, device)
+
+
+def generate_one_image_sized(all_models, caption, label, bbox, clip_model=None, clip_processor=None, device=None, height=None, width=None):
+    """``generate_one_image`` with ``height`` / ``width`` (pixels, multiples of 64).  They only size the starting noise
+    ``torch.randn(1, 4, height / 8, width / 8)``; None (the default) is the reference's 64 latent rows / columns = 512 pixels, drawn the
+    same way."""
+    h, w = latent_hw(height, width, all_models[1])
     args = dict(batch_size=1, no_plms=False, guidance_scale=7.5)
     bbox = [convert_xywh_to_ltrb(b) for b in bbox]
     meta = dict(prompt=caption, phrases=label, locations=bbox, alpha_type=[0.3, 0.0, 0.7])
-    starting_noise = torch.randn(args["batch_size"], 4, 64, 64).to(device)
+    starting_noise = torch.randn(args["batch_size"], 4, h, w).to(device)
     warnings.filterwarnings("ignore", category=DeprecationWarning)
     return run_one_image(all_models, args, meta, starting_noise, clip_model, clip_processor, device=device)
 
 
 def generate_batch_images(all_models, captions, labels, bboxes, clip_model=None, clip_processor=None, device=None):
-    """interface.py:551-570 (boxes are NOT converted here, App-B#10)."""
+    """interface.py:551-570 (boxes are NOT converted here, App-B#10): the reference's signature and its 512 x 512 images."""
+    return generate_batch_images_sized(all_models, captions, labels, bboxes, clip_model, clip_processor, device)
+
+
+def generate_batch_images_sized(all_models, captions, labels, bboxes, clip_model=None, clip_processor=None, device=None, height=None,
+                                width=None):
+    """``generate_batch_images`` with ``height`` / ``width`` (pixels, multiples of 64): as in generate_one_image_sized."""
+    h, w = latent_hw(height, width, all_models[1])
     bs = len(captions)
     args = dict(batch_size=bs, no_plms=False, guidance_scale=7.5)
     meta = dict(prompts=captions, phrases=labels, locations=bboxes, alpha_type=[0.3, 0.0, 0.7])
-    starting_noise = torch.randn(bs, 4, 64, 64).to(device)
+    starting_noise = torch.randn(bs, 4, h, w).to(device)
     warnings.filterwarnings("ignore", category=DeprecationWarning)
     return run_batch_images(all_models, args, meta, starting_noise, clip_model, clip_processor, device=device)
 
@@ -601,14 +640,15 @@ def encode_conditioning(all_models, tok, rows, phrase_encoder, device):
 
 
 def prompt_noise(seeds, latent=64):
-    """Starting noise [n, 4, latent, latent], row i drawn from its OWN CPU generator seeded with ``seeds[i]``: a prompt's
-    noise does not depend on the batch it is in or the rank it runs on."""
+    """Starting noise [n, 4, latent, latent] (``latent`` = (h, w): [n, 4, h, w]), row i drawn from its OWN CPU generator seeded with
+    ``seeds[i]``: a prompt's noise does not depend on the batch it is in or the rank it runs on."""
+    lh, lw = (latent, latent) if isinstance(latent, int) else (int(v) for v in latent)
     rows = []
     for sd_ in seeds:
         g = torch.Generator(device="cpu")
         g.manual_seed(int(sd_))
-        rows.append(torch.randn(1, 4, latent, latent, generator=g))
-    return torch.cat(rows, 0) if rows else torch.zeros(0, 4, latent, latent)
+        rows.append(torch.randn(1, 4, lh, lw, generator=g))
+    return torch.cat(rows, 0) if rows else torch.zeros(0, 4, lh, lw)
 
 
 @torch.no_grad()
@@ -631,14 +671,20 @@ def run_shard(all_models, cond, noise, device, alpha_type=(0.3, 0.0, 0.7), guida
 
 @torch.no_grad()
 def generate_batch_images_sharded(all_models, captions=None, labels=None, bboxes=None, clip_model=None, clip_processor=None,
-                                  device=None, seeds=None, src=0, steps=PLMS_STEPS, latent=64):
+                                  device=None, seeds=None, src=0, steps=PLMS_STEPS, latent=64, height=None, width=None):
     """``generate_batch_images`` (interface.py:551-570) across the ranks of a torch.distributed job.  Rank ``src`` passes the
     prompts (the others pass None) and gets the list of PIL images in prompt order; the other ranks get None.
     Per call: one object broadcast of the conditioning rows (~0.4 MB per prompt), no collective during the 51 sampling
-    steps, one gather of uint8 images.  ``seeds[i]`` seeds prompt i's starting noise (default: i)."""
+    steps, one gather of uint8 images.  ``seeds[i]`` seeds prompt i's starting noise (default: i).  ``height`` / ``width`` (pixels,
+    multiples of 64, the same on every rank) size the starting noise as in generate_batch_images_sized; an axis left None stays at ``latent``
+    (512 pixels by default)."""
     import torch.distributed as dist
     from .dist import shard_indices
     from PIL import Image
+    if height is not None or width is not None:          # validated on every rank alike, before the first collective
+        f = _vae_factor(all_models[1])
+        lh, lw = (latent, latent) if isinstance(latent, int) else latent
+        latent = latent_hw(f * lh if height is None else height, f * lw if width is None else width, all_models[1])
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if multi else (0, 1)
     box = [None]

@@ -162,7 +162,8 @@ class UNetModel:
             raise RuntimeError("model.grounding_tokenizer_input is not set (interface.py:370)")
         return self.grounding_tokenizer_input.get_null_input()
 
-    def set_conditioning(self, context, relations, grounding: dict, hw: int, key=None) -> None:
+    def set_conditioning(self, context, relations, grounding: dict, hw, key=None) -> None:
+        """``hw``: the latent side, or (h, w) for a rectangular latent (UNetEngine.set_conditioning)."""
         if key is not None and key == self._cond_key:
             return
         self.engine.set_conditioning(context, relations, grounding["boxes"], grounding["masks"],
@@ -174,7 +175,8 @@ class UNetModel:
         """UNetModel.forward (openaimodel.py:413-459): one B-sized evaluation."""
         x = input["x"]
         g = self.grounding_of(input)
-        self.set_conditioning(input["context"], input["relations"], g, x.shape[-1], key=None)
+        H, W = (int(v) for v in x.shape[-2:])
+        self.set_conditioning(input["context"], input["relations"], g, H if H == W else (H, W), key=None)
         t = input["timesteps"]
         return self.engine.forward(x.to(self.device, torch.float32).contiguous(), t, self.fuser_scale, self.use_sd_conv, 1).clone()
 

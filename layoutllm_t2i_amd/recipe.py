@@ -109,16 +109,17 @@ _GRID8 = [  # fixed 8-box layout (ltrb, normalised) used when no dataset layout 
 ]
 
 
-def synth_inputs(cfg: UNetConfig, batch: int, hw: int, n_boxes: int = 8, n_rel: int = 3,
+def synth_inputs(cfg: UNetConfig, batch: int, hw, n_boxes: int = 8, n_rel: int = 3,
                  max_relations: int = 10, seed: int = 1234, boxes=None) -> Dict[str, np.ndarray]:
     """Synthetic conditioning of the shapes interface.py:527-535 feeds the UNet.
 
     context/uc ~ N(0,1) [B,77,ctx]; relations: first n_rel rows N(0,1), rest 0, [B,R,ctx];
     boxes [B,30,4] ltrb with the first n_boxes valid; masks [B,30]; text embeddings N(0,1) on
-    valid rows.  Latent x ~ N(0,1) [B,4,hw,hw].
+    valid rows.  Latent x ~ N(0,1) [B,4,hw,hw], or [B,4,h,w] with hw = (h, w).
     """
     mo = cfg.max_objs
-    x = normal("in.x", (batch, cfg.in_channels, hw, hw), seed)
+    lh, lw = (hw, hw) if isinstance(hw, int) else (int(v) for v in hw)
+    x = normal("in.x", (batch, cfg.in_channels, lh, lw), seed)
     context = normal("in.context", (batch, 77, cfg.context_dim), seed)
     uc = np.repeat(normal("in.uc", (1, 77, cfg.context_dim), seed), batch, axis=0)
     relations = np.zeros((batch, max_relations, cfg.context_dim), np.float32)

@@ -72,7 +72,7 @@ class PLMSSampler(object):
             img = torch.randn(shape, device=dev)
             input["x"] = img
         x = img.to(dev, torch.float32).contiguous().clone()
-        side = x.shape[-1]
+        H, W = (int(v) for v in x.shape[-2:])
         n = x.numel()
 
         time_range = np.flip(self.ddim_timesteps)
@@ -95,7 +95,7 @@ class PLMSSampler(object):
             ctx, rel = f32(input["context"]), f32(input["relations"])
             grounding = {k: f32(g[k]) for k in ("boxes", "masks", "positive_embeddings")}
             reps = 1
-        model.set_conditioning(ctx, rel, grounding, side, key=None)
+        model.set_conditioning(ctx, rel, grounding, H if H == W else (H, W), key=None)      # (H, W): the rectangular entry and its shape check
 
         ring = [eng.buf(f"plms.e{j}", tuple(x.shape), torch.float32) for j in range(4)]
         x_a = eng.buf("plms.x", tuple(x.shape), torch.float32)    # running latent (the engine copies it per forward)

@@ -19,7 +19,7 @@ the same state dict when it holds the encoder tensors (real GLIGEN checkpoints d
 
 ``VAEDecoder.decode(z)`` has the reference's contract: z fp32 [B, 4, h, w] -> fp32 [B, 3, 8h, 8w].  It is a thin caller
 of the C engine (``gl_vae_create`` / ``gl_vae_load_weights`` / ``gl_vae_decode``, csrc/vae_engine.hip: plan, flat weight
-layout, activation pool, one hipGraph per (batch, side)); ``decode_oplevel`` is the same launch sequence issued op by op
+layout, activation pool, one hipGraph per (batch, h, w)); ``decode_oplevel`` is the same launch sequence issued op by op
 from Python -- the test mirror the C engine must equal bitwise, like tests/engine_pyref.py for the UNet.
 """
 from __future__ import annotations
@@ -160,20 +160,20 @@ class _VAEStage:
         partial = self.buf("gn.partial", (B * nchunk * 64,), F32)
         return ops.groupnorm(x, None, B, HW, self.W[p + ".g"], self.W[p + ".b"], 1e-6, silu, self.buf(tag, (B * HW, C)), partial)
 
-    def _resnet(self, p, x, B, side, cin, cout, tag):
-        W, HW = self.W, side * side
+    def _resnet(self, p, x, B, sh, sw, cin, cout, tag):
+        W, HW, side = self.W, sh * sw, f"{sh}x{sw}"
         t = self._gn(x, B, HW, p + ".norm1", True, f"rn.gn.{cin}.{side}")
-        h = ops.conv3x3(t, W[p + ".conv1.w"], self.buf(f"rn.h.{cout}.{side}", (B * HW, cout)), B, side, side, W[p + ".conv1.b"])
+        h = ops.conv3x3(t, W[p + ".conv1.w"], self.buf(f"rn.h.{cout}.{side}", (B * HW, cout)), B, sh, sw, W[p + ".conv1.b"])
         t2 = self._gn(h, B, HW, p + ".norm2", True, f"rn.gn.{cout}.{side}")
         if cin != cout:
             sk = ops.gemm(x, W[p + ".nin_shortcut.w"], self.buf(f"rn.sk.{cout}.{side}", (B * HW, cout)), W[p + ".nin_shortcut.b"])
         else:
             sk = x
-        return ops.conv3x3(t2, W[p + ".conv2.w"], self.buf(tag, (B * HW, cout)), B, side, side, W[p + ".conv2.b"],
+        return ops.conv3x3(t2, W[p + ".conv2.w"], self.buf(tag, (B * HW, cout)), B, sh, sw, W[p + ".conv2.b"],
                            epi=EPI_RES, res=sk)
 
-    def _attn(self, p, x, B, side, C, tag):
-        W, N = self.W, side * side
+    def _attn(self, p, x, B, N, C, tag):
+        W = self.W
         M = B * N
         hn = self._gn(x, B, N, p + ".norm", False, "at.gn")
         q = ops.gemm(hn, W[p + ".q.w"], self.buf("at.q", (M, C)), W[p + ".q.b"])
@@ -245,13 +245,17 @@ class VAEDecoder(_VAEStage):
         from . import _lib
         cfg = self.cfg
         z = z.to(self.device, F32).contiguous()
-        B, zc, side, side_w = z.shape
-        assert side == side_w and zc == cfg.z_channels
-        oside = side * 2 ** (len(cfg.ch_mult) - 1)
-        out = torch.empty(B, cfg.out_ch, oside, oside, dtype=F32, device=self.device)
+        B, zc, sh, sw = z.shape
+        assert zc == cfg.z_channels
+        f = 2 ** (len(cfg.ch_mult) - 1)
+        out = torch.empty(B, cfg.out_ch, f * sh, f * sw, dtype=F32, device=self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().gl_vae_decode(self.handle, z.data_ptr(), B, side, out.data_ptr(), int(self.use_graphs),
-                                                torch.cuda.current_stream(self.device).cuda_stream), "gl_vae_decode")
+            if sh == sw:
+                _lib.check(_lib.lib().gl_vae_decode(self.handle, z.data_ptr(), B, sh, out.data_ptr(), int(self.use_graphs), st), "gl_vae_decode")
+            else:
+                _lib.check(_lib.lib().gl_vae_decode_hw(self.handle, z.data_ptr(), B, sh, sw, out.data_ptr(), int(self.use_graphs), st),
+                           "gl_vae_decode_hw")
         return out
 
     @torch.no_grad()
@@ -259,34 +263,34 @@ class VAEDecoder(_VAEStage):
         """The engine's launch sequence issued op by op from Python (test mirror; bitwise equal to ``decode``)."""
         cfg, W = self.cfg, self.W
         z = z.to(self.device, F32).contiguous()
-        B, zc, side, side_w = z.shape
-        assert side == side_w and zc == cfg.z_channels
+        B, zc, sh, sw = z.shape
+        assert zc == cfg.z_channels
         nres = len(cfg.ch_mult)
         ch = cfg.ch * cfg.ch_mult[nres - 1]
         xin = ops.latent_affine_pack(z, W["post_quant_conv.w"], W["post_quant_conv.b"], 1.0 / cfg.scale_factor, CIN_PAD,
-                                     self.buf("in", (B * side * side, CIN_PAD)))
-        h = ops.conv3x3(xin, W["decoder.conv_in.w"], self.buf("conv_in", (B * side * side, ch)), B, side, side, W["decoder.conv_in.b"])
-        h = self._resnet("decoder.mid.block_1", h, B, side, ch, ch, "mid.1")
-        h = self._attn("decoder.mid.attn_1", h, B, side, ch, "mid.a")
-        h = self._resnet("decoder.mid.block_2", h, B, side, ch, ch, "mid.2")
+                                     self.buf("in", (B * sh * sw, CIN_PAD)))
+        h = ops.conv3x3(xin, W["decoder.conv_in.w"], self.buf("conv_in", (B * sh * sw, ch)), B, sh, sw, W["decoder.conv_in.b"])
+        h = self._resnet("decoder.mid.block_1", h, B, sh, sw, ch, ch, "mid.1")
+        h = self._attn("decoder.mid.attn_1", h, B, sh * sw, ch, "mid.a")
+        h = self._resnet("decoder.mid.block_2", h, B, sh, sw, ch, ch, "mid.2")
         for lvl in reversed(range(nres)):
             cout = cfg.ch * cfg.ch_mult[lvl]
             for i in range(cfg.num_res_blocks + 1):
-                h = self._resnet(f"decoder.up.{lvl}.block.{i}", h, B, side, ch, cout, f"up.{lvl}.{i}")
+                h = self._resnet(f"decoder.up.{lvl}.block.{i}", h, B, sh, sw, ch, cout, f"up.{lvl}.{i}")
                 ch = cout
             if lvl != 0:
                 p = f"decoder.up.{lvl}.upsample.conv"
-                h = ops.conv3x3(h, W[p + ".w"], self.buf(f"up.{lvl}.u", (B * 4 * side * side, ch)), B, side, side, W[p + ".b"],
+                h = ops.conv3x3(h, W[p + ".w"], self.buf(f"up.{lvl}.u", (B * 4 * sh * sw, ch)), B, sh, sw, W[p + ".b"],
                                 upsample2x=True)
-                side *= 2
-        g = self._gn(h, B, side * side, "decoder.norm_out", True, "fin.gn")
-        out = torch.empty(B, cfg.out_ch, side, side, dtype=F32, device=self.device)
-        ops.conv3x3(g, W["decoder.conv_out.w"], out, B, side, side, W["decoder.conv_out.b"], nchw_hw=side * side)
+                sh, sw = 2 * sh, 2 * sw
+        g = self._gn(h, B, sh * sw, "decoder.norm_out", True, "fin.gn")
+        out = torch.empty(B, cfg.out_ch, sh, sw, dtype=F32, device=self.device)
+        ops.conv3x3(g, W["decoder.conv_out.w"], out, B, sh, sw, W["decoder.conv_out.b"], nchw_hw=sh * sw)
         return out
 
 
 class VAEEncoder(_VAEStage):
-    """AutoencoderKL.encode on the HIP engine: x fp32 [B, 3, H, H] in [-1, 1] -> z fp32 [B, embed_dim, H / f, H / f], f = 8."""
+    """AutoencoderKL.encode on the HIP engine: x fp32 [B, 3, H, W] in [-1, 1] -> z fp32 [B, embed_dim, H / f, W / f], f = 8."""
     _encoder_stage = True
 
     def __init__(self, state_dict: Mapping[str, object], cfg: VAEConfig = VAEConfig(), device="cuda:0"):
@@ -312,32 +316,39 @@ class VAEEncoder(_VAEStage):
 
     def _check(self, x: torch.Tensor):
         x = x.to(self.device, F32).contiguous()
-        B, c, side, side_w = x.shape
+        if x.dim() != 4 or x.shape[1] != self.cfg.out_ch:
+            raise ValueError(f"encode: expected a [B, {self.cfg.out_ch}, H, W] image batch, got {tuple(x.shape)}")
+        B, c, sh, sw = x.shape
         f = self.factor
-        if c != self.cfg.out_ch or side != side_w:
-            raise ValueError(f"encode: expected a square [B, {self.cfg.out_ch}, H, H] image batch, got {tuple(x.shape)}")
-        if side % f or side >= 1024:
-            raise ValueError(f"encode: the image side must be a multiple of {f} and below 1024, got {side}")
-        return x, B, side, side // f
+        for side in (sh, sw):
+            if side % f or side >= 1024:
+                raise ValueError(f"encode: the image's height and width must each be a multiple of {f} and below 1024, got {sh} x {sw}")
+        return x, B, (sh, sw), (sh // f, sw // f)
 
     def _noise(self, noise, B, zs):
+        shape = (B, self.cfg.embed_dim, *zs)
         if noise is None:   # distributions.py:36: torch.randn(mean.shape) on the CPU default generator, then moved to the device
-            noise = torch.randn((B, self.cfg.embed_dim, zs, zs))
+            noise = torch.randn(shape)
         noise = noise.to(self.device, F32).contiguous()
-        if tuple(noise.shape) != (B, self.cfg.embed_dim, zs, zs):
-            raise ValueError(f"encode: noise must be [{B}, {self.cfg.embed_dim}, {zs}, {zs}], got {tuple(noise.shape)}")
+        if tuple(noise.shape) != shape:
+            raise ValueError(f"encode: noise must be {list(shape)}, got {tuple(noise.shape)}")
         return noise
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """posterior.sample() * scale_factor through the C engine (one hipGraph replay per call after the first)."""
         from . import _lib
-        x, B, side, zs = self._check(x)
+        x, B, (sh, sw), zs = self._check(x)
         noise = self._noise(noise, B, zs)
-        z = torch.empty(B, self.cfg.embed_dim, zs, zs, dtype=F32, device=self.device)
+        z = torch.empty(B, self.cfg.embed_dim, *zs, dtype=F32, device=self.device)
+        st = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().gl_vae_encode(self.handle, x.data_ptr(), B, side, noise.data_ptr(), z.data_ptr(), int(self.use_graphs),
-                                                torch.cuda.current_stream(self.device).cuda_stream), "gl_vae_encode")
+            if sh == sw:
+                _lib.check(_lib.lib().gl_vae_encode(self.handle, x.data_ptr(), B, sh, noise.data_ptr(), z.data_ptr(), int(self.use_graphs), st),
+                           "gl_vae_encode")
+            else:
+                _lib.check(_lib.lib().gl_vae_encode_hw(self.handle, x.data_ptr(), B, sh, sw, noise.data_ptr(), z.data_ptr(),
+                                                       int(self.use_graphs), st), "gl_vae_encode_hw")
         return z
 
     @torch.no_grad()
@@ -345,28 +356,28 @@ class VAEEncoder(_VAEStage):
         """The engine's launch sequence issued op by op from Python (test mirror; bitwise equal to ``encode``).
         ``return_mean``: also the posterior mean (unscaled)."""
         cfg, W = self.cfg, self.W
-        x, B, side, zs = self._check(x)
+        x, B, (sh, sw), zs = self._check(x)
         noise = self._noise(noise, B, zs)
         nres = len(cfg.ch_mult)
         ch = cfg.ch
-        xin = ops.pack_latent(x, CIN_PAD, 1, self.buf("in", (B * side * side, CIN_PAD)))
-        h = ops.conv3x3(xin, W["encoder.conv_in.w"], self.buf("conv_in", (B * side * side, ch)), B, side, side, W["encoder.conv_in.b"])
+        xin = ops.pack_latent(x, CIN_PAD, 1, self.buf("in", (B * sh * sw, CIN_PAD)))
+        h = ops.conv3x3(xin, W["encoder.conv_in.w"], self.buf("conv_in", (B * sh * sw, ch)), B, sh, sw, W["encoder.conv_in.b"])
         for lvl in range(nres):
             cout = cfg.ch * cfg.ch_mult[lvl]
             for i in range(cfg.num_res_blocks):
-                h = self._resnet(f"encoder.down.{lvl}.block.{i}", h, B, side, ch, cout, f"down.{lvl}.{i}")
+                h = self._resnet(f"encoder.down.{lvl}.block.{i}", h, B, sh, sw, ch, cout, f"down.{lvl}.{i}")
                 ch = cout
             if lvl != nres - 1:
                 p = f"encoder.down.{lvl}.downsample.conv"
-                h = ops.conv3x3_pad01(h, W[p + ".w"], self.buf(f"down.{lvl}.d", (B * (side // 2) ** 2, ch)), B, side, side, W[p + ".b"])
-                side //= 2
-        h = self._resnet("encoder.mid.block_1", h, B, side, ch, ch, "mid.1")
-        h = self._attn("encoder.mid.attn_1", h, B, side, ch, "mid.a")
-        h = self._resnet("encoder.mid.block_2", h, B, side, ch, ch, "mid.2")
-        g = self._gn(h, B, side * side, "encoder.norm_out", True, "fin.gn")
-        mom = torch.empty(B, 2 * cfg.z_channels, side, side, dtype=F32, device=self.device)
-        ops.conv3x3(g, W["encoder.conv_out.w"], mom, B, side, side, W["encoder.conv_out.b"], nchw_hw=side * side)
-        z = torch.empty(B, cfg.embed_dim, side, side, dtype=F32, device=self.device)
+                h = ops.conv3x3_pad01(h, W[p + ".w"], self.buf(f"down.{lvl}.d", (B * (sh // 2) * (sw // 2), ch)), B, sh, sw, W[p + ".b"])
+                sh, sw = sh // 2, sw // 2
+        h = self._resnet("encoder.mid.block_1", h, B, sh, sw, ch, ch, "mid.1")
+        h = self._attn("encoder.mid.attn_1", h, B, sh * sw, ch, "mid.a")
+        h = self._resnet("encoder.mid.block_2", h, B, sh, sw, ch, ch, "mid.2")
+        g = self._gn(h, B, sh * sw, "encoder.norm_out", True, "fin.gn")
+        mom = torch.empty(B, 2 * cfg.z_channels, sh, sw, dtype=F32, device=self.device)
+        ops.conv3x3(g, W["encoder.conv_out.w"], mom, B, sh, sw, W["encoder.conv_out.b"], nchw_hw=sh * sw)
+        z = torch.empty(B, cfg.embed_dim, sh, sw, dtype=F32, device=self.device)
         mean = torch.empty_like(z) if return_mean else None
         ops.vae_posterior(mom, W["quant_conv.w"], W["quant_conv.b"], noise, cfg.scale_factor, z, mean)
         return (z, mean) if return_mean else z
