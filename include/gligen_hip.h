@@ -617,7 +617,11 @@ int gl_vae_set_option(gl_vae* v, int key, int value);
 /* measurement hook (tools/g8_probe.py): what = 8 copies the per-block cycle stamps [entry, prologue done, main loop done,
  * epilogue done] (4 x uint64 per block, up to 4096 blocks) that the timestamping instantiation of the 8-wave GEMM / conv
  * kernel writes while gl_set_option(32, 1) is in effect (synchronous device-to-host copy); what = 9 copies one uint64: the
- * number of gl_gemm / gl_conv3x3 calls this process has served with the 8-wave kernel (the tests of that kernel assert it moved). */
+ * number of gl_gemm / gl_conv3x3 calls this process has served with the 8-wave kernel (the tests of that kernel assert it moved);
+ * what = 10 copies ten uint64: the gl_attention calls this process has served per kernel form -- [0] software-pipelined split-fp16
+ * kernel, [1] 8-wave split-fp16 kernel, [2] 4-wave split-fp16 kernel, double-buffered, [3] 4-wave split-fp16 kernel, single buffer set,
+ * [4..6] single-fp16 8-wave kernel with the running max on the FMA path / in the accumulator init / in the padding column (PRE 0 / 1 / 2),
+ * [7..9] single-fp16 4-wave kernel, PRE 0 / 1 / 2 (tests/test_gpu_attention_layouts.py asserts which form took each launch). */
 int gl_debug_read(int what, void* dst, int64_t bytes);
 /* one-time per-process setup (raises dynamic-LDS limits of the tiled kernels); idempotent */
 int gl_init(void);

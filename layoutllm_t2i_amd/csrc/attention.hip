@@ -21,9 +21,16 @@
 #include "common.h"
 #include "gligen_hip.h"
 #include "opts.h"
+#include <atomic>
+#include <cstring>
 #include <type_traits>
 
 namespace {
+
+// launches per kernel form (tests read them: gl_debug_read(10)), so that a dispatcher that quietly stopped choosing a form cannot pass them
+enum { AC_SPLIT_PIPE = 0, AC_SPLIT_8W, AC_SPLIT_4W_DBUF, AC_SPLIT_4W_SINGLE, AC_F16_8W_PRE0, AC_F16_4W_PRE0 = AC_F16_8W_PRE0 + 3, AC_COUNT = AC_F16_4W_PRE0 + 3 };
+std::atomic<uint64_t> g_attn_launches[AC_COUNT];
+inline void attn_count(int form) { g_attn_launches[form].fetch_add(1, std::memory_order_relaxed); }
 
 #define g_attn_qt2 gl_opt(3)  // default 0;          // block shape: 0 auto, 3 always 8 waves, 4 always 4 waves
 #define g_attn_padmax gl_opt(29)  // default 1;       // running max carried in the operands' padding column where the head dim has one (gl_set_option 29; 0 = FMA path)
@@ -1063,6 +1070,7 @@ int launch_attn_split(const gl_attn_args& a, hipStream_t st) {
             if (a.d == 32) attn_split_pipe_kernel<4><<<grid, dim3(512), attn_pipe_lds<4>(), st>>>(a);
             else if (a.d == 40) attn_split_pipe_kernel<5><<<grid, dim3(512), attn_pipe_lds<5>(), st>>>(a);
             else attn_split_pipe_kernel<6><<<grid, dim3(512), attn_pipe_lds<6>(), st>>>(a);
+            attn_count(AC_SPLIT_PIPE);
             GL_CHECK_LAUNCH();
             return 0;
         }
@@ -1070,12 +1078,14 @@ int launch_attn_split(const gl_attn_args& a, hipStream_t st) {
     if constexpr (DQK <= 48) {
         if (a.Nq >= 512 && g_attn_split_var != 1) {
             attn_split_kernel<DQK, 8, true><<<dim3(gl_cdiv(a.Nq, 256) * a.H * a.B), dim3(512), attn_split_lds<DQK, true>(), st>>>(a);
+            attn_count(AC_SPLIT_8W);
             GL_CHECK_LAUNCH();
             return 0;
         }
     }
     if constexpr (DQK <= 80) attn_split_kernel<DQK, 4, true><<<dim3(gl_cdiv(a.Nq, 128) * a.H * a.B), dim3(256), attn_split_lds<DQK, true>(), st>>>(a);
     else attn_split_kernel<DQK, 4, false><<<dim3(gl_cdiv(a.Nq, 128) * a.H * a.B), dim3(256), attn_split_lds<DQK, false>(), st>>>(a);
+    attn_count(DQK <= 80 ? AC_SPLIT_4W_DBUF : AC_SPLIT_4W_SINGLE);
     GL_CHECK_LAUNCH();
     return 0;
 }
@@ -1136,6 +1146,7 @@ int launch_attn(const gl_attn_args& a, hipStream_t st) {
     if (a.q_prescaled && DQK >= 80) attn_kernel<DQK, QT, NW, 1><<<grid, dim3(64 * NW), 0, st>>>(a, flags);
     else if (a.q_prescaled && g_attn_padmax && a.d + 8 == DQK) attn_kernel<DQK, QT, NW, 2><<<grid, dim3(64 * NW), 0, st>>>(a, flags);
     else attn_kernel<DQK, QT, NW, 0><<<grid, dim3(64 * NW), 0, st>>>(a, flags);
+    attn_count((NW == 8 ? AC_F16_8W_PRE0 : AC_F16_4W_PRE0) + (a.q_prescaled && DQK >= 80 ? 1 : a.q_prescaled && g_attn_padmax && a.d + 8 == DQK ? 2 : 0));
     GL_CHECK_LAUNCH();
     return 0;
 }
@@ -1159,6 +1170,15 @@ int launch_attn_auto(const gl_attn_args& a, hipStream_t st) {
 }
 
 }  // namespace
+
+// gl_debug_read(10): AC_COUNT x uint64, in the order of the enum above
+int gl_attn_read_launch_counts(void* dst, int64_t bytes) {
+    if (!dst || bytes < (int64_t)(AC_COUNT * sizeof(uint64_t))) return GL_ERR_BAD_ARG;
+    uint64_t n[AC_COUNT];
+    for (int i = 0; i < AC_COUNT; ++i) n[i] = g_attn_launches[i].load(std::memory_order_relaxed);
+    memcpy(dst, n, sizeof n);
+    return 0;
+}
 
 extern "C" int gl_attention(const gl_attn_args* a, void* stream) {
     if (!a || !a->q || !a->k || !a->vt || !a->out) return GL_ERR_BAD_ARG;

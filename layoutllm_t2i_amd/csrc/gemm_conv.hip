@@ -967,9 +967,12 @@ extern "C" int gl_init_gemm(void) {
     return 0;
 }
 
+int gl_attn_read_launch_counts(void* dst, int64_t bytes);       // attention.hip
+
 // measurement hook: per-block cycle stamps of the timestamping 8-wave kernel (gl_set_option(32, 1)); 4 x uint64 per block
 extern "C" int gl_debug_read(int what, void* dst, int64_t bytes) {
     if (what == 8) return gl8_read_stamps(dst, bytes);
+    if (what == 10) return gl_attn_read_launch_counts(dst, bytes);
     if (what == 9) {
         if (!dst || bytes < (int64_t)sizeof(uint64_t)) return GL_ERR_BAD_ARG;
         const uint64_t n = g8_launches.load(std::memory_order_relaxed);

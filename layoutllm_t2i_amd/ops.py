@@ -583,6 +583,19 @@ def gemm8_launch_count() -> int:
     return int(n.value)
 
 
+ATTN_FORMS = ("split_pipe", "split_8w", "split_4w_dbuf", "split_4w_single", "f16_8w_pre0", "f16_8w_pre1", "f16_8w_pre2", "f16_4w_pre0",
+              "f16_4w_pre1", "f16_4w_pre2")
+
+
+def attention_launch_counts() -> dict:
+    """gl_attention calls this process has served, per kernel form (gl_debug_read(10), names in ATTN_FORMS): the tests assert that the form
+    they mean to test, and only that one, took their launches."""
+    import ctypes
+    n = (ctypes.c_uint64 * len(ATTN_FORMS))()
+    check(_lib.lib().gl_debug_read(10, ctypes.byref(n), ctypes.sizeof(n)), "gl_debug_read")
+    return {k: int(v) for k, v in zip(ATTN_FORMS, n)}
+
+
 # ------------------------------------------------------------------------------------------- CLIP towers (reward stage)
 def clip_patchify(pixel_values: torch.Tensor, patch: int, Kpad: int, out: torch.Tensor) -> torch.Tensor:
     """pixel_values fp32 [B, 3, S, S] -> fp16 [B * (S/patch)^2, Kpad] patch rows (K index (c, i, j), zero-padded)."""

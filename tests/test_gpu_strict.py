@@ -329,7 +329,7 @@ def test_qkv_projection_writes_both_vt_halves(B, rows, C, d):
                                          (40, 8, 4096, 4126, 1), (48, 3, 777, 1000, 1), (32, 2, 1024, 33, 2)])
 def test_split_attention(d, H, Nq, Nk, B):
     """gl_attention with q_lo / k_lo / vt_lo: three-pass QK^T and P.V on hi + lo operands vs fp64 attention of the unrounded q, k, v;
-    out_lo holds the residual of the output."""
+    out_lo holds the residual of the output.  Both forms of the scale: passed as an argument, and folded into q (q_prescaled, what the engine does)."""
     C = H * d
     q, k, v = rnd(f"aq{d}{Nq}", (B * Nq, C)) * 1.2, rnd(f"ak{d}{Nk}", (B * Nk, C)) * 1.2, rnd(f"av{d}{Nk}", (B * Nk, C))
     scale = d ** -0.5
@@ -359,6 +359,17 @@ def test_split_attention(d, H, Nq, Nk, B):
     r, r1 = rel(got, want), rel(plain, want)
     print(f"[split attention d={d} Nq={Nq} Nk={Nk}] rel_l2 = {r:.2e} (single-fp16 kernel {r1:.2e})")
     assert torch.isfinite(out).all() and r < 1e-6 and r1 > 20 * r
+    # q_prescaled, the only form the engine launches: d^-1/2 log2(e) folded into q before the split, the scale argument (wrong on purpose) ignored
+    from layoutllm_t2i_amd.weights import q_fold
+    qph, qpl = split(q * q_fold(d))
+    outp = torch.empty(B * Nq, 2 * C, dtype=torch.float16, device=DEV)
+    ops.attention(qph.to(DEV), Nq * C, C, kh.to(DEV), Nk * C, C, vt_h, outp, Nq * 2 * C, 2 * C, B, H, d, Nq, Nk, 123.0, q_prescaled=True,
+                  q_lo=qpl.to(DEV), k_lo=kl.to(DEV), vt_lo=vt_l, out_lo=outp[:, C:])
+    Qp = f(qph, qpl).view(B, -1, H, d).transpose(1, 2)
+    wantp = (torch.softmax(Qp @ K.transpose(-1, -2) * math.log(2.0), -1) @ V).transpose(1, 2).reshape(B * Nq, C)
+    rp = rel(outp[:, :C].float() + outp[:, C:].float(), wantp)
+    print(f"[split attention d={d} Nq={Nq} Nk={Nk}] q_prescaled: rel_l2 = {rp:.2e}")
+    assert torch.isfinite(outp).all() and rp < 1e-6 and r1 > 20 * rp
 
 
 # ------------------------------------------------------------------------------------------- engine

@@ -13,6 +13,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_gpu_kernels as T  # noqa: E402
 import test_gpu_strict as S  # noqa: E402
+import test_gpu_attention_layouts as L  # noqa: E402
 STRICT = bool(int(os.environ.get("FUZZ_STRICT", "0")))      # FUZZ_STRICT=1: only the strict-mode kernels (three-pass loop, split attention, [hi | lo] V^T tail)
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
@@ -31,8 +32,10 @@ def c64(lo, hi):
 
 def strict_case():
     """round 6: the three-pass main loop against the K-walk and fp64 (GEMM and conv), the split-fp16 attention kernels (round-5 kernel below 512
-    queries, the software-pipelined one from 512 on at d = 32 / 40 / 48), the [hi | lo] QKV projection's transposed tail"""
-    k = rng.choice(["gemm3", "gemm3", "conv3", "attn_s", "attn_s", "attn_pipe", "attn_pipe", "vt2"])
+    queries, the software-pipelined one from 512 on at d = 32 / 40 / 48), the [hi | lo] QKV projection's transposed tail; the split attention
+    kernels also in one of the engine's operand layouts (tests/test_gpu_attention_layouts.py: dispatch counter, bits equal to the contiguous launch,
+    whole-tensor and per-row bounds on planted hard logits)"""
+    k = rng.choice(["gemm3", "gemm3", "conv3", "attn_s", "attn_s", "attn_pipe", "attn_pipe", "attn_lay", "attn_lay", "vt2"])
     if k == "gemm3":
         return S.test_gemm_three_pass_loop_vs_kwalk, (rng.randint(1, 6000), 32 * rng.randint(1, 60), c64(64, 2560), rng.choice(["res", "hilo"]))
     if k == "conv3":
@@ -42,6 +45,16 @@ def strict_case():
     if k == "attn_s":
         d = rng.choice([8, 16, 24, 32, 40, 48, 64, 80, 128, 160])
         return S.test_split_attention, (d, rng.choice([1, 2, 4]), rng.randint(2, 500), rng.randint(1, 900), rng.choice([1, 2]))
+    if k == "attn_lay":
+        if rng.random() < 0.5:
+            d, H, Nq, Nk = rng.choice([8, 16, 24, 32, 40, 48, 64, 80, 128, 160]), rng.choice([1, 2, 4]), rng.randint(6, 500), rng.randint(1, 900)
+        else:
+            d, H, Nq, Nk = rng.choice([32, 40, 48]), rng.choice([1, 2, 4]), rng.randint(512, 2200), rng.randint(1, 2300)
+        lay = rng.choice(L.ALL4 if Nq <= Nk else ("cross4c", "gapped"))          # the fused-QKV layouts hold q in the first Nq of the Nk rows
+        ref = L.split_case(d, H, Nq, Nk, 2)
+        if 50.0 * ref["e32"] > ref["hi_only"]:          # operands on which the per-row bound (5 x e32) would not stay 10 x below the error of a
+            return None                                 # dropped lo term: the check asserts that premise, so draw again
+        return L.test_split_attention_layouts, (L.split_form(d, Nq), d, H, Nq, Nk, 0, (lay,))
     if k == "attn_pipe":
         return S.test_split_attention, (rng.choice([32, 40, 48]), rng.choice([1, 2, 4]), rng.randint(512, 2200), rng.randint(1, 2300), 1)
     H, d = rng.choice([(8, 40), (8, 80), (4, 48), (8, 24), (8, 160), (2, 32)])
