@@ -290,6 +290,25 @@ int gl_timestep_embedding_f32(const float* t, int32_t B, int32_t dim, float* out
 int gl_posnet_input_f32(const float* boxes, const float* masks, const float* emb, const float* null_pos, const float* null_xyxy,
                         int32_t rows, int32_t in_dim, int32_t num_freqs, float* out, void* stream);
 
+/*
+ * text_image grounding (GLIGEN's *_box_text_image checkpoints; text_image_grounding_net.py:41-62, interface.py:114-130), additive to ABI 15.
+ *   gl_posnet_input_ti(_f32) : both MLP inputs of the text_image PositionNet in one launch, one block per (b, i) row:
+ *                              out_text [rows, in_dim + 8 F]  = [ text_emb * tm + (1 - tm) * null_text    | xyxy ]
+ *                              out_image[rows, in_dim + 8 F]  = [ image_emb * im + (1 - im) * null_image  | xyxy ]
+ *                              xyxy = fourier(box) * m + (1 - m) * null_xyxy, computed once.  masks / text_masks / image_masks [rows] fp32;
+ *                              fp16 outputs, or fp32 with _f32 (strict mode, then gl_split_f32).
+ *   gl_image_ground_feature  : out[i, :] = norm * (feat[i, :] . P) / || feat[i, :] . P ||_2 in fp32: the CLIP image embedding projected into the
+ *                              text feature space and rescaled (interface.py:126-129: project(feature, P.T) = feature @ P, / norm() * 28.7).
+ *                              feat, out [n, dim], proj [dim, dim] row-major, fp32; dim <= 1024; one block per image.
+ */
+int gl_posnet_input_ti(const float* boxes, const float* masks, const float* text_masks, const float* image_masks, const float* text_emb,
+                       const float* image_emb, const float* null_text, const float* null_image, const float* null_xyxy, int32_t rows,
+                       int32_t in_dim, int32_t num_freqs, void* out_text, void* out_image, void* stream);
+int gl_posnet_input_ti_f32(const float* boxes, const float* masks, const float* text_masks, const float* image_masks, const float* text_emb,
+                           const float* image_emb, const float* null_text, const float* null_image, const float* null_xyxy, int32_t rows,
+                           int32_t in_dim, int32_t num_freqs, float* out_text, float* out_image, void* stream);
+int gl_image_ground_feature(const float* feat, const float* proj, int32_t n, int32_t dim, float norm, float* out, void* stream);
+
 /* gl_silu_f16: y = silu(x) elementwise fp16 (emb_layers SiLU, openaimodel.py:173). n % 8 == 0. */
 int gl_silu_f16(const void* x, void* y, int64_t n, void* stream);
 
@@ -355,6 +374,12 @@ typedef struct gl_unet_config {          /* UNetModel.__init__ arguments (openai
                                     its third pass x.Wlo -- with it the engine reproduces the reference's fp32 weights to ~22 bits.  The default
                                     mode of such a handle reads the Whi halves and computes what a handle without the flag computes; the table is
                                     twice the size (5 GB for the GLIGEN UNet).  0 = the compact table (only the 1x1 convs keep [Whi | Wlo]). */
+    int32_t grounding;           /* additive to ABI 15.  0 = the text PositionNet (text_grounding_net.py; a zeroed field keeps the earlier behaviour);
+                                    1 = the text_image PositionNet (text_image_grounding_net.py): the weight table holds position_net.linears_text.* /
+                                    linears_image.* / null_text / null_image / null_xyxy, every box yields TWO grounding tokens (text, image), and the
+                                    handle is conditioned through gl_set_conditioning_ti.  n_ground = max_objs (0) or 2 * max_objs (1) is the token count
+                                    of the gated self-attention (keys N + n_ground); gl_create rejects n_ground > 64.  The relation chain keeps
+                                    max_objs boxes. */
 } gl_unet_config;
 
 typedef struct gl_engine gl_engine;      /* opaque */
@@ -396,6 +421,18 @@ int gl_set_conditioning(gl_engine* e, const float* context, const float* relatio
 int gl_set_conditioning_hw(gl_engine* e, const float* context, const float* relations, const float* boxes,
                            const float* masks, const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t h, int32_t w,
                            void* stream);
+/* gl_set_conditioning_ti: the conditioning of a text_image handle (gl_unet_config.grounding = 1; additive to ABI 15).  The six grounding
+ * tensors of text_image_grounding_net.py:41: boxes [Bn, max_objs, 4], masks / text_masks / image_masks [Bn, max_objs], text_emb / image_emb
+ * [Bn, max_objs, pos_in_dim], fp32; null grounding = all six zero (tokens of MLP(null features)).  The grounding tokens of sample b are
+ * objs[b] = [objs_text (max_objs rows) | objs_image (max_objs rows)] (cat(dim=1), :62).  (h, w): the shape rule of gl_set_conditioning_hw.
+ * The text entries on a text_image handle, and this entry on a text handle, return GL_ERR_BAD_ARG. */
+int gl_set_conditioning_ti(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
+                           const float* text_masks, const float* image_masks, const float* text_emb, const float* image_emb, int32_t Bn,
+                           int32_t Lc, int32_t R, int32_t h, int32_t w, void* stream);
+/* gl_last_error: the message of the handle's last GL_ERR_BAD_ARG that carries one (a conditioning entry of the wrong grounding family, a
+ * latent shape that breaks the shape rule, strict mode without split weights), copied NUL-terminated into dst (at most bytes - 1
+ * characters).  Returns the message's full length, 0 when there is none.  Additive to ABI 15. */
+int gl_last_error(const gl_engine* e, char* dst, int32_t bytes);
 /* gl_unet_forward: eps[Bn, out_ch, hw, hw] fp32 = UNet(x, t | conditioning).  x fp32 NCHW [Bn / reps, in_ch, hw, hw]:
  * with reps = 2 both CFG halves of a [cond ; uncond] conditioning batch share the latent.  t_dev: fp32 [Bn] device
  * timesteps, or NULL to use t_host for every sample.  fuser_scale = what set_alpha_scale wrote (interface.py:34-38;

@@ -19,6 +19,9 @@ ABI_VERSION = 15
 EPI_BIAS, EPI_SILU, EPI_GEGLU, EPI_RES, EPI_GATE_RES, EPI_ROWBIAS = range(6)
 OUT_F16_ROWMAJOR, OUT_F32_NCHW, OUT_F32_ROWMAJOR, OUT_F16_HILO = 0, 1, 2, 3
 
+# gl_unet_config.grounding
+GROUNDING_IDS = {"text": 0, "text_image": 1}
+
 vp = C.c_void_p
 i32 = C.c_int32
 i64 = C.c_int64
@@ -100,6 +103,7 @@ class UNetConfigC(C.Structure):
         ("pos_in_dim", i32), ("pos_out_dim", i32), ("fourier_freqs", i32),
         ("max_objs", i32),
         ("split_weights", i32),
+        ("grounding", i32),
     ]
 
 
@@ -181,6 +185,11 @@ PROTOTYPES = {
     "gl_load_weights": (i32, [vp, vp, i64, i32, vp]),
     "gl_set_conditioning": (i32, [vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, vp]),
     "gl_set_conditioning_hw": (i32, [vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]),
+    "gl_set_conditioning_ti": (i32, [vp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]),
+    "gl_posnet_input_ti": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp, vp, vp]),
+    "gl_posnet_input_ti_f32": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, fp, fp, vp]),
+    "gl_image_ground_feature": (i32, [fp, fp, i32, i32, f32, fp, vp]),
+    "gl_last_error": (i32, [vp, C.c_char_p, i32]),
     "gl_unet_forward": (i32, [vp, fp, fp, f32, i32, f32, i32, fp, i32, vp]),
     "gl_plms_step": (i32, [vp, C.POINTER(PlmsStepArgs), vp]),
     "gl_pool_bytes": (i64, [vp]),
@@ -293,6 +302,7 @@ def unet_config_c(cfg) -> UNetConfigC:
     c.num_heads, c.context_dim = cfg.num_heads, cfg.context_dim
     c.pos_in_dim, c.pos_out_dim, c.fourier_freqs, c.max_objs = cfg.pos_in_dim, cfg.pos_out_dim, cfg.fourier_freqs, cfg.max_objs
     c.split_weights = int(bool(getattr(cfg, "split_weights", False)))
+    c.grounding = GROUNDING_IDS[getattr(cfg, "grounding", "text")]
     return c
 
 
@@ -338,6 +348,13 @@ def weight_table(handle: int):
         check(l.gl_weight_at(handle, i, C.byref(info)), "gl_weight_at")
         out.append((info.name.decode(), int(info.offset), int(info.nbytes), int(info.dtype), tuple(int(info.shape[k]) for k in range(info.ndim))))
     return out, int(l.gl_weights_bytes(handle))
+
+
+def last_error(handle: int) -> str:
+    """gl_last_error: the message the handle's last failing entry left (empty when there is none)"""
+    buf = C.create_string_buffer(512)
+    n = lib().gl_last_error(handle, buf, len(buf))
+    return buf.value.decode() if n > 0 else ""
 
 
 def check(code: int, what: str) -> None:

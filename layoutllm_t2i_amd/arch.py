@@ -34,6 +34,15 @@ class UNetConfig:
     # [Whi | Wlo] halves, which the engine's strict mode (option 50: split-fp16 operands, within north_star's tolerance of the fp32
     # reference) needs for its third pass; the default mode of such an engine reads the Whi halves.  Twice the weight bytes.
     split_weights: bool = False
+    # the grounding tokenizer (config['model']['params']['grounding_tokenizer']['target']): "text" = text_grounding_net.PositionNet (one token
+    # per box), "text_image" = text_image_grounding_net.PositionNet (GLIGEN's *_box_text_image checkpoints: a text token and an image token
+    # per box, gl_unet_config.grounding = 1)
+    grounding: str = "text"
+
+    @property
+    def n_ground(self) -> int:
+        """grounding tokens per sample, the extra keys of the gated self-attention: max_objs (text) or 2 * max_objs (text_image)"""
+        return self.max_objs * (2 if self.grounding == "text_image" else 1)
 
     @property
     def time_embed_dim(self) -> int:
@@ -47,6 +56,13 @@ class UNetConfig:
     def from_dict(params: dict) -> "UNetConfig":
         """Accepts the ``config['model']['params']`` dict of a GLIGEN checkpoint."""
         gt = (params.get("grounding_tokenizer") or {}).get("params", {})
+        target = (params.get("grounding_tokenizer") or {}).get("target")
+        if target is None or target.endswith(".text_grounding_net.PositionNet") or target == "text_grounding_net.PositionNet":
+            grounding = "text"
+        elif target.endswith("text_image_grounding_net.PositionNet"):
+            grounding = "text_image"
+        else:
+            raise NotImplementedError(f"grounding_tokenizer target {target!r}: only the text and text_image PositionNets are supported")
         # variants that share parameter names / shapes with this UNet but compute something else must not load silently
         # (load_state_dict(strict=False), interface.py:91, would accept them): openaimodel.py:246-262, attention.py:362-384
         if params.get("fuser_type", "gatedSA") != "gatedSA":
@@ -72,6 +88,7 @@ class UNetConfig:
             pos_in_dim=int(gt.get("in_dim", 768)),
             pos_out_dim=int(gt.get("out_dim", 768)),
             fourier_freqs=int(gt.get("fourier_freqs", 8)),
+            grounding=grounding,
         )
 
 
@@ -268,6 +285,21 @@ def param_shapes(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
             raise ValueError(l.kind)
     out.update(norm_params("out.0", plan.out_channels_last))
     out.update(conv_params("out.2", plan.out_channels_last, cfg.out_channels))
+    if cfg.grounding == "text_image":
+        # text_image_grounding_net.py:19-38, in module registration order
+        for chain in ("linears_text", "linears_image"):
+            out[f"position_net.{chain}.0.weight"] = (512, cfg.pos_in_dim + cfg.position_dim)
+            out[f"position_net.{chain}.0.bias"] = (512,)
+            out[f"position_net.{chain}.2.weight"] = (512, 512)
+            out[f"position_net.{chain}.2.bias"] = (512,)
+            out[f"position_net.{chain}.4.weight"] = (cfg.pos_out_dim, 512)
+            out[f"position_net.{chain}.4.bias"] = (cfg.pos_out_dim,)
+        out["position_net.null_text_feature"] = (cfg.pos_in_dim,)
+        out["position_net.null_image_feature"] = (cfg.pos_in_dim,)
+        out["position_net.null_position_feature"] = (cfg.position_dim,)
+        return out
+    if cfg.grounding != "text":
+        raise ValueError(f"grounding = {cfg.grounding!r}")
     out["position_net.null_positive_feature"] = (cfg.pos_in_dim,)
     out["position_net.null_position_feature"] = (cfg.position_dim,)
     out["position_net.linears.0.weight"] = (512, cfg.pos_in_dim + cfg.position_dim)

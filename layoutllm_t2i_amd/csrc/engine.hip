@@ -67,6 +67,20 @@ __global__ void fill_f32_kernel(float* __restrict__ y, float v, int n) {
     if (i < n) y[i] = v;
 }
 
+// text_image PositionNet (text_image_grounding_net.py:60-62): the two MLP chains run chain-major ([2, B, n] rows); objs = cat([objs_text,
+// objs_image], dim=1) is sample-major ([B, 2 n] rows).  Rows are copied as 32-bit words (fp16 rows have an even number of elements).
+__global__ void cat_chains_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int B, int n, int words) {
+    const size_t total = (size_t)2 * B * n * words;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int wd = (int)(i % words);
+        const size_t row = i / words;               // (c * B + b) * n + k
+        const int k = (int)(row % n);
+        const size_t cb = row / n;
+        const int b = (int)(cb % B), c = (int)(cb / B);
+        dst[(((size_t)b * 2 + c) * n + k) * words + wd] = src[i];
+    }
+}
+
 // Integer pixel rectangles of RelationCrossAttention.forward (attention.py:321-346) for one resolution, one thread per
 // sample (the `break` at the first padded or degenerate box is sequential).  Arithmetic mirrors the reference exactly:
 // float32 multiply by the python int, truncation toward zero (.to(torch.int)), x1 / y1 clamped with torch.minimum,
@@ -349,12 +363,28 @@ void build_table(gl_engine* e) {
     add_lin(e, "emb_all", off, te);
     add_norm(e, "out.0", e->out_channels_last);
     add_conv3(e, "out.2", e->out_channels_last, c.out_channels);
+    if (c.grounding == 1) {
+        // text_image PositionNet (text_image_grounding_net.py:19-38): two MLPs, three null features
+        add_w(e, "position_net.null_text", 1, {c.pos_in_dim});
+        add_w(e, "position_net.null_image", 1, {c.pos_in_dim});
+        add_w(e, "position_net.null_xyxy", 1, {8 * c.fourier_freqs});
+        for (const char* n : {"position_net.linears_text", "position_net.linears_image"}) {
+            const std::string p = n;
+            add_lin(e, p + ".0", 512, c.pos_in_dim + 8 * c.fourier_freqs);
+            add_lin(e, p + ".2", 512, 512);
+            add_lin(e, p + ".4", c.pos_out_dim, 512);
+        }
+        return;
+    }
     add_w(e, "position_net.null_pos", 1, {c.pos_in_dim});
     add_w(e, "position_net.null_xyxy", 1, {8 * c.fourier_freqs});
     add_lin(e, "position_net.linears.0", 512, c.pos_in_dim + 8 * c.fourier_freqs);
     add_lin(e, "position_net.linears.2", 512, 512);
     add_lin(e, "position_net.linears.4", c.pos_out_dim, 512);
 }
+
+// grounding tokens per sample (the fuser's extra keys): max_objs for the text PositionNet, 2 * max_objs for text_image
+inline int n_ground(const gl_unet_config& c) { return c.grounding == 1 ? 2 * c.max_objs : c.max_objs; }
 
 inline int vt_ld(int Nk) {
     // row stride (keys) of a V^T buffer: Nk rounded up to the 64-key tile, plus one tile when that is a multiple of 512
@@ -715,7 +745,7 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, in
     const std::string& p = l.prefix;
     const std::string t = p + ".transformer_blocks.0";
     const int C = l.cin, d = l.d_head, H = cfg.num_heads;
-    const int Bn = e->Bn, N = sh * sw, M = Bn * N, mo = cfg.max_objs, R = e->R, Lc = e->Lc;
+    const int Bn = e->Bn, N = sh * sw, M = Bn * N, mo = cfg.max_objs, ng = n_ground(cfg), R = e->R, Lc = e->Lc;
     const std::string sl = std::to_string(li);
     float* xa = e->f32("st.xa", (size_t)M * C);
     float* xb = e->f32("st.xb", (size_t)M * C);
@@ -762,18 +792,19 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, in
         const std::string f = t + ".fuser";
         // [x ; objs] rows per sample padded to a multiple of 8 so that the QKV epilogue can store V^T in 16-byte pieces; the
         // pad rows are never normalised into (arbitrary finite-or-not contents): as keys they are masked by the attention
-        // kernel (Nk = N + mo), as queries they are not used (Nq = N)
-        const int rows = N + ((mo + 7) & ~7);
+        // kernel (Nk = N + ng), as queries they are not used (Nq = N).  ng = the grounding-token count (n_ground): max_objs, or
+        // 2 * max_objs on a text_image handle; the relation chain below keeps mo = max_objs boxes
+        const int rows = N + ((ng + 7) & ~7);
         half_t* cat = e->h16("st.cat", (size_t)Bn * rows * lnw);
         CKP(cat);
         if (strict) {
-            CK(r.ln(x, C, 1, cat, lnw, f + ".norm1", Bn, N, rows, 0, C, nullptr, e->f32("hoist.objs32s." + sl, (size_t)Bn * mo * C), mo, 1, true));
+            CK(r.ln(x, C, 1, cat, lnw, f + ".norm1", Bn, N, rows, 0, C, nullptr, e->f32("hoist.objs32s." + sl, (size_t)Bn * ng * C), ng, 1, true));
         } else if (precise) {
-            CK(r.ln(x, C, 1, cat, C, f + ".norm1", Bn, N, rows, 0, C, nullptr, e->f32("hoist.objs32." + sl, (size_t)Bn * mo * C), mo, 1));
+            CK(r.ln(x, C, 1, cat, C, f + ".norm1", Bn, N, rows, 0, C, nullptr, e->f32("hoist.objs32." + sl, (size_t)Bn * ng * C), ng, 1));
         } else {
-            CK(r.ln(x, C, 1, cat, C, f + ".norm1", Bn, N, rows, 0, C, nullptr, e->h16("hoist.objs." + sl, (size_t)Bn * mo * C), mo));
+            CK(r.ln(x, C, 1, cat, C, f + ".norm1", Bn, N, rows, 0, C, nullptr, e->h16("hoist.objs." + sl, (size_t)Bn * ng * C), ng));
         }
-        CK(self_attention(r, cat, rows, N, N + mo, C, d, f + ".attn", "st.fa", &att));
+        CK(self_attention(r, cat, rows, N, N + ng, C, d, f + ".attn", "st.fa", &att));
         float* y = nxt(x);
         CK(r.gemm(att, lnw, f + ".attn.o.w", M, y, C, GL_OUT_F32_ROWMAJOR, f + ".attn.o.b", GL_EPI_GATE_RES, x, C, 1, gates + 0, nullptr, 0, nullptr, 0, 0, strict));
         x = y;
@@ -1046,7 +1077,8 @@ extern "C" int gl_create(const gl_unet_config* cfg, gl_engine** out) {
     if (cfg->n_levels <= 0 || cfg->n_levels > 8 || cfg->n_attn_res < 0 || cfg->n_attn_res > 8 || cfg->num_heads <= 0) return GL_ERR_BAD_ARG;
     if (cfg->model_channels % 64 || cfg->context_dim % 64 || cfg->pos_in_dim % 8 || cfg->pos_out_dim != cfg->context_dim) return GL_ERR_UNSUPPORTED;
     if ((cfg->pos_in_dim + 8 * cfg->fourier_freqs) % 64) return GL_ERR_UNSUPPORTED;
-    if (cfg->in_channels > CIN_PAD || cfg->max_objs <= 0 || cfg->max_objs > 64) return GL_ERR_UNSUPPORTED;
+    if (cfg->grounding != 0 && cfg->grounding != 1) return GL_ERR_UNSUPPORTED;
+    if (cfg->in_channels > CIN_PAD || cfg->max_objs <= 0 || n_ground(*cfg) > 64) return GL_ERR_UNSUPPORTED;
     gl_engine* e = new gl_engine();
     e->cfg = *cfg;
     build_plan(e);
@@ -1114,13 +1146,22 @@ extern "C" int gl_load_weights(gl_engine* e, const void* packed, int64_t bytes, 
 // capture), and again when key 51 changed since -- a split handle that stays in default mode never pays for the chain.
 int strict_hoists(gl_engine* e, hipStream_t st) {
     const gl_unet_config& cfg = e->cfg;
-    const int Bn = e->Bn, Lc = e->Lc, mo = cfg.max_objs, ctx = cfg.context_dim, H = cfg.num_heads;
+    const int Bn = e->Bn, Lc = e->Lc, mo = cfg.max_objs, ng = n_ground(cfg), ctx = cfg.context_dim, H = cfg.num_heads;
+    const bool ti = cfg.grounding == 1;
+    const int nch = ti ? 2 : 1;                      // MLP chains of the PositionNet: text (+ image)
     const int pin_dim = cfg.pos_in_dim + 8 * cfg.fourier_freqs;
     const float* context = e->f32("cond.in.context", (size_t)Bn * Lc * ctx);
     const float* boxes = e->f32("cond.in.boxes", (size_t)Bn * mo * 4);
     const float* masks = e->f32("cond.in.masks", (size_t)Bn * mo);
     const float* pos_emb = e->f32("cond.in.posemb", (size_t)Bn * mo * cfg.pos_in_dim);
     CKP(context); CKP(boxes); CKP(masks); CKP(pos_emb);
+    const float *text_masks = nullptr, *image_masks = nullptr, *image_emb = nullptr;
+    if (ti) {
+        text_masks = e->f32("cond.in.tmasks", (size_t)Bn * mo);
+        image_masks = e->f32("cond.in.imasks", (size_t)Bn * mo);
+        image_emb = e->f32("cond.in.imgemb", (size_t)Bn * mo * cfg.pos_in_dim);
+        CKP(text_masks); CKP(image_masks); CKP(image_emb);
+    }
     Run r{e, st, e->buf("splitk.ws", WS_BYTES)};
     CKP(r.ws);
     gl_opts strict_opts = *(tl_gl_opts ? tl_gl_opts : &g_gl_opts);
@@ -1128,32 +1169,51 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
     const gl_opts* prev_opts = tl_gl_opts;
     tl_gl_opts = &strict_opts;                       // Run::gemm decides the third pass from the strict keys
     struct Restore { const gl_opts* p; ~Restore() { tl_gl_opts = p; } } restore{prev_opts};
-    const size_t rows = (size_t)Bn * mo;
-    float* pin32 = e->f32("pn.in32", rows * pin_dim);
-    half_t* pins = e->h16("pn.ins", rows * 2 * pin_dim);
-    half_t* h1s = e->h16("pn.h1s", rows * 2 * 512);
-    half_t* h2s = e->h16("pn.h2s", rows * 2 * 512);
-    half_t* objss = e->h16("pn.objss", rows * 2 * cfg.pos_out_dim);
+    const size_t rows = (size_t)Bn * mo;             // rows of ONE chain; the token rows of the fuser are Bn * ng
+    const int D = cfg.pos_out_dim;
+    float* pin32 = e->f32("pn.in32", nch * rows * pin_dim);
+    half_t* pins = e->h16("pn.ins", nch * rows * 2 * pin_dim);
+    half_t* h1s = e->h16("pn.h1s", nch * rows * 2 * 512);
+    half_t* h2s = e->h16("pn.h2s", nch * rows * 2 * 512);
+    half_t* objss = e->h16("pn.objss", nch * rows * 2 * D);
     half_t* ctxs = e->h16("cond.ctxs", (size_t)Bn * Lc * 2 * ctx);
     CKP(pin32); CKP(pins); CKP(h1s); CKP(h2s); CKP(objss); CKP(ctxs);
-    CK(gl_posnet_input_f32(boxes, masks, pos_emb, e->Wf("position_net.null_pos"), e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim,
-                           cfg.fourier_freqs, pin32, st));
-    CK(r.split(pin32, (int64_t)rows, pin_dim, pins));
-    auto lin = [&](const half_t* a, int k, const std::string& w, void* out, int ldc, int out_mode, int epi) {
-        return r.gemm(a, 2 * k, w + ".w", (int)rows, out, ldc, out_mode, w + ".b", epi, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0, true);
+    if (ti) {
+        CK(gl_posnet_input_ti_f32(boxes, masks, text_masks, image_masks, pos_emb, image_emb, e->Wf("position_net.null_text"),
+                                  e->Wf("position_net.null_image"), e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim, cfg.fourier_freqs, pin32,
+                                  pin32 + rows * pin_dim, st));
+    } else {
+        CK(gl_posnet_input_f32(boxes, masks, pos_emb, e->Wf("position_net.null_pos"), e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim,
+                               cfg.fourier_freqs, pin32, st));
+    }
+    CK(r.split(pin32, (int64_t)(nch * rows), pin_dim, pins));
+    auto lin = [&](const half_t* a, int k, const std::string& w, void* out, int ldc, int out_mode, int epi, size_t m) {
+        return r.gemm(a, 2 * k, w + ".w", (int)m, out, ldc, out_mode, w + ".b", epi, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0, true);
     };
-    CK(lin(pins, pin_dim, "position_net.linears.0", h1s, 2 * 512, GL_OUT_F16_HILO, GL_EPI_SILU));
-    CK(lin(h1s, 512, "position_net.linears.2", h2s, 2 * 512, GL_OUT_F16_HILO, GL_EPI_SILU));
-    CK(lin(h2s, 512, "position_net.linears.4", objss, 2 * cfg.pos_out_dim, GL_OUT_F16_HILO, GL_EPI_BIAS));
+    for (int c = 0; c < nch; ++c) {                  // chain c on rows [c * rows, (c + 1) * rows) of every buffer
+        const std::string pw = !ti ? "position_net.linears" : (c == 0 ? "position_net.linears_text" : "position_net.linears_image");
+        const size_t o = c * rows;
+        CK(lin(pins + o * 2 * pin_dim, pin_dim, pw + ".0", h1s + o * 2 * 512, 2 * 512, GL_OUT_F16_HILO, GL_EPI_SILU, rows));
+        CK(lin(h1s + o * 2 * 512, 512, pw + ".2", h2s + o * 2 * 512, 2 * 512, GL_OUT_F16_HILO, GL_EPI_SILU, rows));
+        CK(lin(h2s + o * 2 * 512, 512, pw + ".4", objss + o * 2 * D, 2 * D, GL_OUT_F16_HILO, GL_EPI_BIAS, rows));
+    }
+    if (ti) {                                        // objs = cat([objs_text, objs_image], dim=1): sample-major token rows
+        half_t* cat = e->h16("pn.objss.cat", (size_t)Bn * ng * 2 * D);
+        CKP(cat);
+        cat_chains_kernel<<<dim3(256), dim3(256), 0, st>>>(reinterpret_cast<const uint32_t*>(objss), reinterpret_cast<uint32_t*>(cat), Bn, mo, D);
+        GL_CHECK_LAUNCH();
+        objss = cat;
+    }
+    const size_t tok = (size_t)Bn * ng;
     CK(r.split(context, (int64_t)Bn * Lc, ctx, ctxs));
     for (size_t li = 0; li < e->st_layers.size(); ++li) {
         const LayerD& l = e->st_layers[li];
         const std::string t = l.prefix + ".transformer_blocks.0";
         const std::string sl = std::to_string(li);
         const int C = l.cin, d = l.d_head;
-        float* o32 = e->f32("hoist.objs32s." + sl, rows * C);
+        float* o32 = e->f32("hoist.objs32s." + sl, tok * C);
         CKP(o32);
-        CK(lin(objss, cfg.pos_out_dim, t + ".fuser.linear", o32, C, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS));
+        CK(lin(objss, D, t + ".fuser.linear", o32, C, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, tok));
         half_t* kv = e->h16("hoist.kvctxs." + sl, (size_t)Bn * Lc * 4 * C);
         const int ldc_ = vt_ld(Lc);
         half_t* vt = e->h16("hoist.vtctxs." + sl, (size_t)2 * Bn * H * d * ldc_);
@@ -1168,13 +1228,19 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
 }
 
 namespace {
+// pos_emb: the phrase embeddings (positive_embeddings of the text PositionNet, text_embeddings of the text_image one); text_masks /
+// image_masks / image_emb: the three further inputs of a text_image handle (text_image_grounding_net.py:41), NULL on a text handle
 int set_conditioning(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks, const float* pos_emb,
-                     int32_t Bn, int32_t Lc, int32_t R, int32_t h, int32_t w, void* stream) {
+                     const float* text_masks, const float* image_masks, const float* image_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t h,
+                     int32_t w, void* stream) {
     if (!e || !e->wbase || !context || !relations || !boxes || !masks || !pos_emb || Bn <= 0 || Lc <= 0 || R <= 0 || h <= 0 || w <= 0) return GL_ERR_BAD_ARG;
     gl_opts_scope opts_scope(e->ovr);       // this handle's option overrides are in effect for the call
     const gl_unet_config& cfg = e->cfg;
     hipStream_t st = (hipStream_t)stream;
-    const int mo = cfg.max_objs, ctx = cfg.context_dim, H = cfg.num_heads;
+    const int mo = cfg.max_objs, ng = n_ground(cfg), ctx = cfg.context_dim, H = cfg.num_heads;
+    const bool ti = cfg.grounding == 1;
+    const int nch = ti ? 2 : 1;
+    if (ti && (!text_masks || !image_masks || !image_emb)) return GL_ERR_BAD_ARG;
     if (Bn != e->Bn || Lc != e->Lc || R != e->R || h != e->lat_h || w != e->lat_w) e->drop_graphs();     // shapes are part of the graph keys anyway
     e->pool_changed = false;
     e->Bn = Bn; e->Lc = Lc; e->R = R; e->lat_h = h; e->lat_w = w;
@@ -1182,18 +1248,37 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     CKP(r.ws);
     // --- grounding tokens: PositionNet (text_grounding_net.py:26-43)
     const int pin_dim = cfg.pos_in_dim + 8 * cfg.fourier_freqs;
-    half_t* pin = e->h16("pn.in", (size_t)Bn * mo * pin_dim);
-    half_t* h1 = e->h16("pn.h1", (size_t)Bn * mo * 512);
-    half_t* h2 = e->h16("pn.h2", (size_t)Bn * mo * 512);
-    half_t* objs = e->h16("pn.objs", (size_t)Bn * mo * cfg.pos_out_dim);
+    // (text_image_grounding_net.py:41-62: two chains, text then image, chain-major [nch, Bn * mo] rows until the final concatenation)
+    const size_t crow = (size_t)Bn * mo;
+    const int D = cfg.pos_out_dim;
+    half_t* pin = e->h16("pn.in", nch * crow * pin_dim);
+    half_t* h1 = e->h16("pn.h1", nch * crow * 512);
+    half_t* h2 = e->h16("pn.h2", nch * crow * 512);
+    half_t* objs = e->h16("pn.objs", nch * crow * D);
     half_t* ctx16 = e->h16("cond.ctx", (size_t)Bn * Lc * ctx);
     half_t* rel16 = e->h16("cond.rel", (size_t)Bn * R * ctx);
     CKP(pin); CKP(h1); CKP(h2); CKP(objs); CKP(ctx16); CKP(rel16);
-    CK(gl_posnet_input(boxes, masks, pos_emb, e->Wf("position_net.null_pos"), e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim,
-                       cfg.fourier_freqs, pin, st));
-    CK(r.gemm(pin, pin_dim, "position_net.linears.0.w", Bn * mo, h1, 512, GL_OUT_F16_ROWMAJOR, "position_net.linears.0.b", GL_EPI_SILU));
-    CK(r.gemm(h1, 512, "position_net.linears.2.w", Bn * mo, h2, 512, GL_OUT_F16_ROWMAJOR, "position_net.linears.2.b", GL_EPI_SILU));
-    CK(r.gemm(h2, 512, "position_net.linears.4.w", Bn * mo, objs, cfg.pos_out_dim, GL_OUT_F16_ROWMAJOR, "position_net.linears.4.b"));
+    if (ti) {
+        CK(gl_posnet_input_ti(boxes, masks, text_masks, image_masks, pos_emb, image_emb, e->Wf("position_net.null_text"), e->Wf("position_net.null_image"),
+                              e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim, cfg.fourier_freqs, pin, pin + crow * pin_dim, st));
+    } else {
+        CK(gl_posnet_input(boxes, masks, pos_emb, e->Wf("position_net.null_pos"), e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim,
+                           cfg.fourier_freqs, pin, st));
+    }
+    for (int c = 0; c < nch; ++c) {
+        const std::string pw = !ti ? "position_net.linears" : (c == 0 ? "position_net.linears_text" : "position_net.linears_image");
+        const size_t o = c * crow;
+        CK(r.gemm(pin + o * pin_dim, pin_dim, pw + ".0.w", Bn * mo, h1 + o * 512, 512, GL_OUT_F16_ROWMAJOR, pw + ".0.b", GL_EPI_SILU));
+        CK(r.gemm(h1 + o * 512, 512, pw + ".2.w", Bn * mo, h2 + o * 512, 512, GL_OUT_F16_ROWMAJOR, pw + ".2.b", GL_EPI_SILU));
+        CK(r.gemm(h2 + o * 512, 512, pw + ".4.w", Bn * mo, objs + o * D, D, GL_OUT_F16_ROWMAJOR, pw + ".4.b"));
+    }
+    if (ti) {               // objs = cat([objs_text, objs_image], dim=1): sample b's ng token rows are [text (mo) | image (mo)]
+        half_t* cat = e->h16("pn.objs.cat", (size_t)Bn * ng * D);
+        CKP(cat);
+        cat_chains_kernel<<<dim3(256), dim3(256), 0, st>>>(reinterpret_cast<const uint32_t*>(objs), reinterpret_cast<uint32_t*>(cat), Bn, mo, D / 2);
+        GL_CHECK_LAUNCH();
+        objs = cat;
+    }
     f32_to_f16_kernel<<<dim3(256), dim3(256), 0, st>>>(context, ctx16, (size_t)Bn * Lc * ctx);
     f32_to_f16_kernel<<<dim3(64), dim3(256), 0, st>>>(relations, rel16, (size_t)Bn * R * ctx);
     GL_CHECK_LAUNCH();
@@ -1204,11 +1289,11 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
         const int C = l.cin, d = l.d_head;
         // fuser.linear(objs) (attention.py:228)
         // (both forms are kept hoisted: fp32 rows for the precise mode's LayerNorm over [x ; objs], fp16 rows for the fp16-copy mode)
-        half_t* o = e->h16("hoist.objs." + sl, (size_t)Bn * mo * C);
-        float* o32 = e->f32("hoist.objs32." + sl, (size_t)Bn * mo * C);
+        half_t* o = e->h16("hoist.objs." + sl, (size_t)Bn * ng * C);
+        float* o32 = e->f32("hoist.objs32." + sl, (size_t)Bn * ng * C);
         CKP(o); CKP(o32);
-        CK(r.gemm(objs, cfg.pos_out_dim, t + ".fuser.linear.w", Bn * mo, o, C, GL_OUT_F16_ROWMAJOR, t + ".fuser.linear.b"));
-        CK(r.gemm(objs, cfg.pos_out_dim, t + ".fuser.linear.w", Bn * mo, o32, C, GL_OUT_F32_ROWMAJOR, t + ".fuser.linear.b"));
+        CK(r.gemm(objs, D, t + ".fuser.linear.w", Bn * ng, o, C, GL_OUT_F16_ROWMAJOR, t + ".fuser.linear.b"));
+        CK(r.gemm(objs, D, t + ".fuser.linear.w", Bn * ng, o32, C, GL_OUT_F32_ROWMAJOR, t + ".fuser.linear.b"));
         // attn2 K/V of the text context (attention.py:124-125)
         half_t* kv = e->h16("hoist.kvctx." + sl, (size_t)Bn * Lc * 2 * C);
         const int ldc_ = vt_ld(Lc);
@@ -1228,11 +1313,16 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     //     when the handle is in strict mode at this point, else with the first strict forward
     e->strict_hoists_ok = false;
     if (cfg.split_weights) {
+        // (the last three: a text_image handle's further inputs; src == NULL on a text handle)
         struct { const char* tag; const float* src; size_t n; } keep[] = {{"cond.in.context", context, (size_t)Bn * Lc * ctx},
                                                                           {"cond.in.boxes", boxes, (size_t)Bn * mo * 4},
                                                                           {"cond.in.masks", masks, (size_t)Bn * mo},
-                                                                          {"cond.in.posemb", pos_emb, (size_t)Bn * mo * cfg.pos_in_dim}};
+                                                                          {"cond.in.posemb", pos_emb, (size_t)Bn * mo * cfg.pos_in_dim},
+                                                                          {"cond.in.tmasks", text_masks, (size_t)Bn * mo},
+                                                                          {"cond.in.imasks", image_masks, (size_t)Bn * mo},
+                                                                          {"cond.in.imgemb", image_emb, (size_t)Bn * mo * cfg.pos_in_dim}};
         for (auto& k : keep) {
+            if (k.src == nullptr) continue;
             float* dst = e->f32(k.tag, k.n);
             CKP(dst);
             if (hipMemcpyAsync(dst, k.src, k.n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
@@ -1286,23 +1376,48 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
 }
 }  // namespace
 
+// the grounding family is a property of the handle: each family has its own conditioning entries
+static int wrong_family(gl_engine* e, const char* entry, int want) {
+    if (e->cfg.grounding == want) return 0;
+    e->err = std::string(entry) + (want == 1 ? ": the handle was created with grounding = 0 (text); use gl_set_conditioning / gl_set_conditioning_hw"
+                                             : ": the handle was created with grounding = 1 (text_image); use gl_set_conditioning_ti");
+    return GL_ERR_BAD_ARG;
+}
+// an axis that is not a multiple of 2^(number of downsamples) comes back shorter than the skip tensor it is concatenated with
+static int check_hw(gl_engine* e, const char* entry, int h, int w) {
+    int f = 1;
+    for (auto& b : e->input_blocks) for (auto& l : b.layers) if (l.kind == DOWN) f *= 2;
+    if (h <= 0 || w <= 0 || (h % f) != 0 || (w % f) != 0) {
+        e->err = std::string(entry) + ": h = " + std::to_string(h) + ", w = " + std::to_string(w) + " must be positive multiples of " + std::to_string(f);
+        return GL_ERR_BAD_ARG;
+    }
+    return 0;
+}
+
 extern "C" int gl_set_conditioning(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
                                    const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t hw, void* stream) {
-    return set_conditioning(e, context, relations, boxes, masks, pos_emb, Bn, Lc, R, hw, hw, stream);
+    if (!e) return GL_ERR_BAD_ARG;
+    CK(wrong_family(e, "gl_set_conditioning", 0));
+    return set_conditioning(e, context, relations, boxes, masks, pos_emb, nullptr, nullptr, nullptr, Bn, Lc, R, hw, hw, stream);
+}
+
+extern "C" int gl_set_conditioning_ti(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
+                                      const float* text_masks, const float* image_masks, const float* text_emb, const float* image_emb, int32_t Bn,
+                                      int32_t Lc, int32_t R, int32_t h, int32_t w, void* stream) {
+    if (!e) return GL_ERR_BAD_ARG;
+    CK(wrong_family(e, "gl_set_conditioning_ti", 1));
+    CK(check_hw(e, "gl_set_conditioning_ti", h, w));
+    return set_conditioning(e, context, relations, boxes, masks, text_emb, text_masks, image_masks, image_emb, Bn, Lc, R, h, w, stream);
 }
 
 extern "C" int gl_set_conditioning_hw(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
                                       const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t h, int32_t w, void* stream) {
     if (!e) return GL_ERR_BAD_ARG;
+    CK(wrong_family(e, "gl_set_conditioning_hw", 0));
     // every DOWN halves both axes and every UP doubles them back: an axis that is not a multiple of 2^(number of downsamples) comes back
     // shorter than the skip tensor it is concatenated with (the reference fails there too) -- rejected here, before anything is launched
-    int f = 1;
-    for (auto& b : e->input_blocks) for (auto& l : b.layers) if (l.kind == DOWN) f *= 2;
-    if (h <= 0 || w <= 0 || (h % f) != 0 || (w % f) != 0) {
-        e->err = "gl_set_conditioning_hw: h = " + std::to_string(h) + ", w = " + std::to_string(w) + " must be positive multiples of " + std::to_string(f);
-        return GL_ERR_BAD_ARG;
-    }
-    return set_conditioning(e, context, relations, boxes, masks, pos_emb, Bn, Lc, R, h, w, stream);
+    CK(check_hw(e, "gl_set_conditioning_hw", h, w));
+    return set_conditioning(e, context, relations, boxes, masks, pos_emb, nullptr, nullptr, nullptr, Bn, Lc, R, h, w, stream);
 }
 
 extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev, float t_host, int32_t reps, float fuser_scale, int32_t sd_conv,
@@ -1416,6 +1531,14 @@ extern "C" int gl_clear_handle_options(gl_engine* e) {
     e->ovr.mask = 0;
     ++e->ovr.epoch;
     return 0;
+}
+
+extern "C" int gl_last_error(const gl_engine* e, char* dst, int32_t bytes) {
+    if (!e || !dst || bytes <= 0) return GL_ERR_BAD_ARG;
+    const size_t n = e->err.size() < (size_t)bytes - 1 ? e->err.size() : (size_t)bytes - 1;
+    memcpy(dst, e->err.data(), n);
+    dst[n] = 0;
+    return (int)e->err.size();
 }
 
 extern "C" int64_t gl_pool_bytes(const gl_engine* e) {

@@ -33,6 +33,80 @@ __global__ __launch_bounds__(256) void posnet_input_kernel(const float* __restri
     }
 }
 
+// text_image_grounding_net.py:48-61.  One block per (b, i) row writes BOTH MLP inputs: out_text row = [text_blend | xyxy_blend], out_image row =
+// [image_blend | xyxy_blend].  The Fourier part is computed once and blended with masks; the embeddings are blended with text_masks /
+// image_masks against their own null features (the operation order of :56-58).
+template <typename OT>
+__global__ __launch_bounds__(256) void posnet_input_ti_kernel(const float* __restrict__ boxes, const float* __restrict__ masks,
+                                                              const float* __restrict__ text_masks, const float* __restrict__ image_masks,
+                                                              const float* __restrict__ text_emb, const float* __restrict__ image_emb,
+                                                              const float* __restrict__ null_text, const float* __restrict__ null_image,
+                                                              const float* __restrict__ null_xyxy, int in_dim, int num_freqs,
+                                                              OT* __restrict__ out_text, OT* __restrict__ out_image) {
+    const int row = blockIdx.x;
+    const float m = masks[row], tm = text_masks[row], im = image_masks[row];
+    const int pos_dim = num_freqs * 8;
+    OT* ot = out_text + (size_t)row * (in_dim + pos_dim);
+    OT* oi = out_image + (size_t)row * (in_dim + pos_dim);
+    for (int c = threadIdx.x; c < in_dim; c += 256) {
+        ot[c] = (OT)(text_emb[(size_t)row * in_dim + c] * tm + (1.0f - tm) * null_text[c]);
+        oi[c] = (OT)(image_emb[(size_t)row * in_dim + c] * im + (1.0f - im) * null_image[c]);
+    }
+    for (int c = threadIdx.x; c < pos_dim; c += 256) {
+        const int j = c / 8;
+        const int r = c - j * 8;
+        const int coord = r & 3;
+        const float freq = powf(100.0f, (float)j / (float)num_freqs);
+        const float arg = freq * boxes[(size_t)row * 4 + coord];
+        const float e = (r < 4) ? sinf(arg) : cosf(arg);
+        const OT v = (OT)(e * m + (1.0f - m) * null_xyxy[c]);
+        ot[in_dim + c] = v;
+        oi[in_dim + c] = v;
+    }
+}
+
+// interface.py:126-129: out = norm * (f P) / || f P ||_2 per image, fp32.  f [n, dim], P [dim, dim] row-major (project(feature, P.T) =
+// feature @ P), one block of 256 threads per image, dim <= 1024: thread t owns output columns t, t + 256, ... (coalesced reads of P's rows).
+// Deliberately one block per image, so a single image streams all of P (2.4 MB at dim 768) through one CU: this runs once per distinct
+// reference image at conditioning time, behind a CLIP vision forward that costs orders of magnitude more.
+__global__ __launch_bounds__(256) void image_ground_feature_kernel(const float* __restrict__ feat, const float* __restrict__ proj, int dim,
+                                                                   float norm, float* __restrict__ out) {
+    __shared__ float f[1024];
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    for (int c = threadIdx.x; c < dim; c += 256) f[c] = feat[(size_t)b * dim + c];
+    __syncthreads();
+    // two-level sum over k (chunks of 32, then the chunk sums): the rounding error grows with sqrt(32) + sqrt(dim / 32) instead of sqrt(dim)
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int k0 = 0; k0 < dim; k0 += 32) {
+        float part[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        const int k1 = k0 + 32 < dim ? k0 + 32 : dim;
+        for (int k = k0; k < k1; ++k) {
+            const float fk = f[k];
+            const float* pr = proj + (size_t)k * dim;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = threadIdx.x + j * 256;
+                if (c < dim) part[j] += fk * pr[c];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += part[j];
+    }
+    float ss = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ss += acc[j] * acc[j];       // (columns >= dim hold 0)
+    ss = wave_sum(ss);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    const float inv = norm / sqrtf(red[0] + red[1] + red[2] + red[3]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = threadIdx.x + j * 256;
+        if (c < dim) out[(size_t)b * dim + c] = acc[j] * inv;
+    }
+}
+
 // util.py:161-181: [cos(t*w) | sin(t*w)], w_k = exp(-ln(10000) * k / half)
 template <typename OT>
 __global__ void timestep_embedding_kernel(const float* __restrict__ t, int dim, OT* __restrict__ out) {
@@ -274,6 +348,39 @@ extern "C" int gl_posnet_input_f32(const float* boxes, const float* masks, const
                                    const float* null_xyxy, int32_t rows, int32_t in_dim, int32_t num_freqs, float* out, void* stream) {
     if (!boxes || !masks || !emb || !null_pos || !null_xyxy || !out || rows <= 0) return GL_ERR_BAD_ARG;
     posnet_input_kernel<float><<<dim3(rows), dim3(256), 0, (hipStream_t)stream>>>(boxes, masks, emb, null_pos, null_xyxy, in_dim, num_freqs, out);
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_posnet_input_ti(const float* boxes, const float* masks, const float* text_masks, const float* image_masks, const float* text_emb,
+                                  const float* image_emb, const float* null_text, const float* null_image, const float* null_xyxy, int32_t rows,
+                                  int32_t in_dim, int32_t num_freqs, void* out_text, void* out_image, void* stream) {
+    if (!boxes || !masks || !text_masks || !image_masks || !text_emb || !image_emb || !null_text || !null_image || !null_xyxy || !out_text ||
+        !out_image || rows <= 0 || in_dim <= 0 || num_freqs <= 0)
+        return GL_ERR_BAD_ARG;
+    posnet_input_ti_kernel<half_t><<<dim3(rows), dim3(256), 0, (hipStream_t)stream>>>(boxes, masks, text_masks, image_masks, text_emb, image_emb, null_text,
+                                                                                      null_image, null_xyxy, in_dim, num_freqs,
+                                                                                      reinterpret_cast<half_t*>(out_text), reinterpret_cast<half_t*>(out_image));
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_posnet_input_ti_f32(const float* boxes, const float* masks, const float* text_masks, const float* image_masks,
+                                      const float* text_emb, const float* image_emb, const float* null_text, const float* null_image,
+                                      const float* null_xyxy, int32_t rows, int32_t in_dim, int32_t num_freqs, float* out_text, float* out_image,
+                                      void* stream) {
+    if (!boxes || !masks || !text_masks || !image_masks || !text_emb || !image_emb || !null_text || !null_image || !null_xyxy || !out_text ||
+        !out_image || rows <= 0 || in_dim <= 0 || num_freqs <= 0)
+        return GL_ERR_BAD_ARG;
+    posnet_input_ti_kernel<float><<<dim3(rows), dim3(256), 0, (hipStream_t)stream>>>(boxes, masks, text_masks, image_masks, text_emb, image_emb, null_text,
+                                                                                     null_image, null_xyxy, in_dim, num_freqs, out_text, out_image);
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_image_ground_feature(const float* feat, const float* proj, int32_t n, int32_t dim, float norm, float* out, void* stream) {
+    if (!feat || !proj || !out || n <= 0 || dim <= 0 || dim > 1024) return GL_ERR_BAD_ARG;
+    image_ground_feature_kernel<<<dim3(n), dim3(256), 0, (hipStream_t)stream>>>(feat, proj, dim, norm, out);
     GL_CHECK_LAUNCH();
     return 0;
 }

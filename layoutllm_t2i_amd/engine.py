@@ -93,11 +93,22 @@ class UNetEngine:
 
     # ------------------------------------------------------------------ conditioning (once per image)
     @torch.no_grad()
-    def set_conditioning(self, context, relations, boxes, masks, positive_embeddings, hw) -> None:
+    def set_conditioning(self, context, relations, boxes, masks, positive_embeddings, hw, text_masks=None, image_masks=None,
+                         image_embeddings=None) -> None:
         """context [Bn,77,ctx], relations [Bn,R,ctx], boxes [Bn,30,4], masks [Bn,30],
         positive_embeddings [Bn,30,in_dim]: fp32 tensors (any device).  Null grounding = zeros
         (text_layout_tokinzer_input.py:47-62).  ``hw`` = latent side (64 for 512x512; gl_set_conditioning), or ``(h, w)`` = latent rows
-        and columns (gl_set_conditioning_hw): each a multiple of 2^(number of downsamples), else ValueError before anything is launched."""
+        and columns (gl_set_conditioning_hw): each a multiple of 2^(number of downsamples), else ValueError before anything is launched.
+
+        A text_image engine (``cfg.grounding == "text_image"``, gl_set_conditioning_ti) takes the phrase embeddings as
+        ``positive_embeddings`` plus ``text_masks`` / ``image_masks`` [Bn,30] and ``image_embeddings`` [Bn,30,in_dim]
+        (text_image_grounding_net.py:41); giving them to a text engine, or leaving them out of a text_image one, raises."""
+        ti = self.cfg.grounding == "text_image"
+        extra = (text_masks, image_masks, image_embeddings)
+        if ti and any(v is None for v in extra):
+            raise ValueError("a text_image model needs text_masks, image_masks and image_embeddings")
+        if not ti and any(v is not None for v in extra):
+            raise ValueError("text_masks / image_masks / image_embeddings given to a text-only model")
         rect = not isinstance(hw, int)
         if rect:
             h, w = (int(v) for v in hw)
@@ -116,6 +127,18 @@ class UNetEngine:
         if not (context.shape[0] == relations.shape[0] == masks.shape[0] == pe.shape[0] == Bn):
             raise ValueError("conditioning batch sizes differ")
         R, Lc = relations.shape[1], context.shape[1]
+        if ti:
+            check_latent_hw(self.cfg, h, w)          # gl_set_conditioning_ti applies the _hw entry's shape rule to squares too
+            tm, im, ie = f32(text_masks), f32(image_masks), f32(image_embeddings)
+            if tuple(tm.shape) != tuple(masks.shape) or tuple(im.shape) != tuple(masks.shape) or tuple(ie.shape) != tuple(pe.shape):
+                raise ValueError("text_masks / image_masks must match masks, image_embeddings must match the text embeddings")
+            with torch.cuda.device(dev):
+                check(self._lib.gl_set_conditioning_ti(self.handle, context.data_ptr(), relations.data_ptr(), boxes.data_ptr(), masks.data_ptr(),
+                                                       tm.data_ptr(), im.data_ptr(), pe.data_ptr(), ie.data_ptr(), Bn, Lc, R, h, w, self._stream()),
+                      "gl_set_conditioning_ti")
+            self._cond_refs = (context, relations, boxes, masks, pe, tm, im, ie)      # read asynchronously by the launched kernels
+            self.cond = dict(Bn=Bn, mo=mo, R=R, Lc=Lc, hw=hw, H=h, W=w)
+            return
         with torch.cuda.device(dev):
             if rect:
                 check(self._lib.gl_set_conditioning_hw(self.handle, context.data_ptr(), relations.data_ptr(), boxes.data_ptr(), masks.data_ptr(),

@@ -11,7 +11,8 @@ App-B#9), so only its entry-point name and argument meaning are kept; semantics 
 a passed ``starting_noise`` [bs, 4, h, w] decides the shape itself (image = 8h x 8w).
 
 ``meta``: ``ckpt`` (path), ``prompt``, ``phrases``, ``locations`` (ltrb, normalised), optional
-``alpha_type``, ``save_folder_name``; ``config``: object/dict with ``batch_size``, ``guidance_scale``,
+``alpha_type``, ``save_folder_name``, ``images`` (one reference image or None per box, for a ``*_box_text_image`` checkpoint; with
+``text_mask`` / ``image_mask`` / ``projection_matrix`` as in interface.prepare_batch); ``config``: object/dict with ``batch_size``, ``guidance_scale``,
 ``no_plms`` (must be False), optional ``folder``.  Images are saved like the reference does
 (gligen_inference.py:437-446) when ``config.folder`` is given.
 
@@ -51,6 +52,10 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     args = dict(batch_size=bs, no_plms=bool(_get(config, "no_plms", False)), guidance_scale=_get(config, "guidance_scale", 7.5))
     m = dict(prompt=meta["prompt"], phrases=meta.get("phrases"), locations=meta["locations"],
              alpha_type=meta.get("alpha_type", [0.3, 0.0, 0.7]), input_image=meta.get("input_image"))
+    # image grounding (a *_box_text_image checkpoint, gligen_inference.py:350-352): one reference image or None per box
+    for k in ("images", "text_mask", "image_mask", "projection_matrix"):
+        if meta.get(k) is not None:
+            m[k] = meta[k]
     if starting_noise is None:
         h, w = interface.latent_hw(_get(config, "height"), _get(config, "width"), all_models[1])
         starting_noise = torch.randn(bs, 4, h, w).to(device)

@@ -34,7 +34,7 @@ import torch
 from . import host
 from .arch import UNetConfig
 from .arch import VAEConfig
-from .model import GroundingNetInput, LatentDiffusion, UNetModel, load_sd_first_conv
+from .model import LatentDiffusion, UNetModel, grounding_input_for, load_sd_first_conv
 from .vae import VAEDecoder
 from .sampler import PLMSSampler
 
@@ -177,7 +177,7 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
 def load_all_models(ckpt, device, strict=None):
     """interface.py:366-373 (``strict``: see load_ckpt)."""
     model, autoencoder, text_encoder, diffusion, config = load_ckpt(ckpt, device, strict=strict)
-    model.grounding_tokenizer_input = GroundingNetInput()
+    model.grounding_tokenizer_input = grounding_input_for(model.cfg)      # text, or text_image for a *_box_text_image checkpoint
     return model, autoencoder, text_encoder, diffusion, config
 
 
@@ -212,13 +212,56 @@ def _hf_text_pooler_output(model, input_ids, attention_mask, device):
     return model(input_ids=input_ids, attention_mask=attention_mask, pixel_values=torch.ones(1, 3, 224, 224).to(device)).text_model_output.pooler_output
 
 
-def get_clip_feature(model, processor, input, device, is_image=False):
-    """interface.py:114-141, text branch ('before' projection = pooler_output).  Image grounding is
-    not on the text_layout path."""
+IMAGE_FEATURE_NORM = 28.7          # interface.py:129
+_PROJECTION_CACHE = {}
+
+
+def load_projection_matrix(meta=None, device=None) -> torch.Tensor:
+    """The CLIP projection matrix of interface.py:128 (``torch.load('projection_matrix')``), fp32 on ``device``.  Looked up in
+    ``meta["projection_matrix"]`` (a tensor or a path), then ``$GLIGEN_PROJECTION_MATRIX``, then a file ``projection_matrix`` in the working
+    directory (where the reference reads it); a file is loaded once per (path, device) and cached.  FileNotFoundError names all three."""
+    src = (meta or {}).get("projection_matrix") if hasattr(meta, "get") else None
+    if torch.is_tensor(src):
+        return src.detach().to(device, torch.float32).contiguous()
+    cands = [src, os.environ.get("GLIGEN_PROJECTION_MATRIX"), os.path.join(os.getcwd(), "projection_matrix")]
+    for c in cands:
+        if c and os.path.exists(c):
+            key = (os.path.abspath(c), str(device))
+            if key not in _PROJECTION_CACHE:
+                _PROJECTION_CACHE[key] = torch.load(c, map_location="cpu").detach().to(device, torch.float32).contiguous()
+            return _PROJECTION_CACHE[key]
+    raise FileNotFoundError("image grounding needs CLIP's projection matrix (interface.py:128); looked at meta['projection_matrix'] "
+                            f"({src!r}), $GLIGEN_PROJECTION_MATRIX ({os.environ.get('GLIGEN_PROJECTION_MATRIX')!r}) and "
+                            f"{os.path.join(os.getcwd(), 'projection_matrix')!r}")
+
+
+def _clip_image_embeds(model, pixel_values, device):
+    """the CLIP image embedding (``outputs.image_embeds`` of interface.py:125-126) from a HuggingFace ``CLIPModel`` or anything with
+    ``get_image_features`` (clip.ClipTowers)"""
+    if not hasattr(model, "get_image_features"):
+        raise TypeError("image grounding needs a CLIP model with get_image_features (a HuggingFace CLIPModel or clip.ClipTowers)")
+    px = torch.as_tensor(np.asarray(pixel_values) if not torch.is_tensor(pixel_values) else pixel_values)
+    out = model.get_image_features(pixel_values=px.to(device))
+    if not torch.is_tensor(out):           # newer transformers return an output object
+        out = out.pooler_output if getattr(out, "pooler_output", None) is not None else out[0]
+    return out
+
+
+def get_clip_feature(model, processor, input, device, is_image=False, projection_matrix=None):
+    """interface.py:114-141.  Text: the 'before' projection feature (pooler_output).  Image ('after_reproject', :118-130): ``input`` is a
+    path or a ``PIL.Image``; ``.convert("RGB")``, the caller's ``processor(images=[image])``, the CLIP image embedding of the caller's
+    model, then ``28.7 * (f @ P) / ||f @ P||`` on the device (gl_image_ground_feature).  ``projection_matrix``: a tensor, a ``meta``
+    dict, or None (see load_projection_matrix)."""
     if input is None:
         return None
     if is_image:
-        raise NotImplementedError("image grounding tokens are not on the text_layout path")
+        from PIL import Image
+        from . import ops
+        image = (input if isinstance(input, Image.Image) else Image.open(input)).convert("RGB")
+        P = projection_matrix if torch.is_tensor(projection_matrix) else load_projection_matrix(projection_matrix, device)
+        inputs = processor(images=[image], return_tensors="pt", padding=True)
+        feat = _clip_image_embeds(model, inputs["pixel_values"], device).detach().to(device, torch.float32).reshape(1, -1).contiguous()
+        return ops.image_ground_feature(feat, P.to(device, torch.float32).contiguous(), IMAGE_FEATURE_NORM)
     inputs = processor(text=input, return_tensors="pt", padding=True)
     return _hf_text_pooler_output(model, inputs["input_ids"].to(device), inputs["attention_mask"].to(device), device)
 
@@ -241,7 +284,27 @@ def get_clip_features_batched(model, processor, phrases, device):
     return {p: pooled[i:i + 1] for i, p in enumerate(uniq)}
 
 
-def _one_sample_grounding(phrases, locations, model, processor, max_objs, device, feature_cache=None):
+def _image_key(im):
+    return im if isinstance(im, (str, os.PathLike)) else id(im)
+
+
+def get_image_features_cached(model, processor, images, device, meta=None, cache=None):
+    """{id of the image object or its path: [1, 768] grounding feature} for the DISTINCT non-None entries of ``images`` (the reference
+    encodes every box's image separately, interface.py:172-174).  The projection matrix is resolved only when there is an image."""
+    cache = {} if cache is None else cache
+    P = None
+    for im in images:
+        if im is None:
+            continue
+        k = _image_key(im)
+        if k not in cache:
+            if P is None:
+                P = load_projection_matrix(meta, device)
+            cache[k] = get_clip_feature(model, processor, im, device, is_image=True, projection_matrix=P)
+    return cache
+
+
+def _one_sample_grounding(phrases, locations, model, processor, max_objs, device, feature_cache=None, images=None, image_cache=None):
     boxes = torch.zeros(max_objs, 4)
     masks = torch.zeros(max_objs)
     text_masks = torch.zeros(max_objs)
@@ -253,19 +316,31 @@ def _one_sample_grounding(phrases, locations, model, processor, max_objs, device
     if feature_cache is None:
         feature_cache = get_clip_features_batched(model, processor, phrases, device)
     feats = [None if ph is None else feature_cache[ph] for ph in phrases]
-    for idx, (box, feat) in enumerate(zip(locations, feats)):
+    if images is None:
+        images = [None] * len(locations)
+    elif len(images) != len(locations):        # (without images the text path keeps zip's silent truncation, like the reference)
+        raise ValueError(f"{len(locations)} boxes with {len(images)} images: one entry (or None) per box")
+    ifeats = [None if im is None else image_cache[_image_key(im)] for im in images]
+    for idx, (box, feat, ifeat) in enumerate(zip(locations, feats, ifeats)):
         boxes[idx] = torch.tensor(box)
         masks[idx] = 1
         if feat is not None:
             text_embeddings[idx] = feat
             text_masks[idx] = 1
+        if ifeat is not None:
+            image_embeddings[idx] = ifeat.detach().float().cpu()
+            image_masks[idx] = 1
     return boxes, masks, text_masks, image_masks, text_embeddings, image_embeddings
 
 
 @torch.no_grad()
 def prepare_batch(meta, model, processor, batch=1, max_objs=MAX_OBJS, device=None):
-    """interface.py:156-193: one layout repeated `batch` times."""
-    boxes, masks, tm, im, te, ie = _one_sample_grounding(meta.get("phrases"), meta["locations"], model, processor, max_objs, device)
+    """interface.py:156-193: one layout repeated `batch` times.  ``meta["images"]``: one reference image (path / PIL.Image) or None per
+    box; ``phrases=None`` with images grounds on the images alone."""
+    images = meta.get("images")
+    icache = get_image_features_cached(model, processor, images, device, meta) if images is not None else None
+    boxes, masks, tm, im, te, ie = _one_sample_grounding(meta.get("phrases"), meta["locations"], model, processor, max_objs, device,
+                                                         images=images, image_cache=icache)
     out = {
         "boxes": boxes.unsqueeze(0).repeat(batch, 1, 1),
         "masks": masks.unsqueeze(0).repeat(batch, 1),
@@ -287,8 +362,17 @@ def prepare_batch_multiple(meta, model, processor, batch=1, max_objs=MAX_OBJS, d
     assert batch == len(phrases_batch)
     cols = [[] for _ in range(6)]
     cache = get_clip_features_batched(model, processor, [ph for phrases in phrases_batch for ph in phrases], device)
+    # meta["images"]: per prompt a list with one reference image (path / PIL.Image) or None per box, or None for a prompt without images;
+    # distinct images are encoded once for the whole batch
+    images_batch = meta.get("images")
+    icache = None
+    if images_batch is not None:
+        if len(images_batch) != len(phrases_batch):
+            raise ValueError(f"images: {len(images_batch)} lists for a batch of {len(phrases_batch)}")
+        icache = get_image_features_cached(model, processor, [im for ims in images_batch if ims is not None for im in ims], device, meta)
     for i, phrases in enumerate(phrases_batch):
-        parts = _one_sample_grounding(phrases, meta["locations"][i], model, processor, max_objs, device, cache)
+        parts = _one_sample_grounding(phrases, meta["locations"][i], model, processor, max_objs, device, cache,
+                                      images=None if images_batch is None else images_batch[i], image_cache=icache)
         parts = list(parts)
         parts[2] = parts[2].unsqueeze(0) * complete_mask(meta.get("text_mask"), max_objs)
         parts[3] = parts[3].unsqueeze(0) * complete_mask(meta.get("image_mask"), max_objs)
@@ -390,9 +474,21 @@ def _check_noise(model, starting_noise) -> None:
         check_latent_hw(model.cfg, int(starting_noise.shape[-2]), int(starting_noise.shape[-1]))
 
 
+def _has_images(images, multiple) -> bool:
+    """any reference image in meta["images"] (a flat list, or per-prompt lists / None with ``multiple``)"""
+    if images is None:
+        return False
+    flat = [im for ims in images if ims is not None for im in ims] if multiple else images
+    return any(im is not None for im in flat)
+
+
 def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple):
     model, autoencoder, text_encoder, diffusion, config = all_models
     _check_noise(model, starting_noise)
+    if _has_images(meta.get("images"), multiple) and getattr(model.cfg, "grounding", "text") != "text_image":
+        # (the reference would prepare image tokens and drop them silently: text_layout_tokinzer_input.py reads three keys)
+        raise ValueError("meta['images'] given to a text-only checkpoint: image grounding needs a *_box_text_image checkpoint "
+                         "(grounding_tokenizer target text_image_grounding_net.PositionNet)")
     config.update(args)                      # mutates the caller's dict, like interface.py:297/484
     cfg = _AttrDict(config)
     if cfg.get("no_plms", False):
@@ -500,7 +596,7 @@ def _unet_facade(packed, cfg, device, allow_missing_sd_conv=False):
     m.cfg, m.device = cfg, torch.device(device)
     m.image_size, m.in_channels, m.out_channels, m.model_channels = cfg.image_size, cfg.in_channels, cfg.out_channels, cfg.model_channels
     m.first_conv_restorable, m.allow_missing_sd_conv, m.first_conv_type = bool(packed.has_sd_conv), bool(allow_missing_sd_conv), "GLIGEN"
-    m.grounding_tokenizer_input = GroundingNetInput()
+    m.grounding_tokenizer_input = grounding_input_for(cfg)
     m.fuser_scale, m.training, m._cond_key = 1.0, False, None
     m.engine = UNetEngine(packed)
     m.strict = False
@@ -521,6 +617,8 @@ def load_all_models_sharded(ckpt, device, src=0, strict=None):
     if rank == src:
         am = load_all_models(ckpt, device, strict=strict)
         model, autoencoder, text_encoder, diffusion, config = am
+        if model.cfg.grounding != "text":
+            raise NotImplementedError("the sharded entry is text-only: a text_image checkpoint runs through load_all_models / run_batch_images")
         if not isinstance(autoencoder, VAEDecoder):
             raise NotImplementedError("the sharded entry broadcasts the HIP VAE decoder's packed weights (unset GLIGEN_REFERENCE_VAE)")
         dcfg = dict(linear_start=diffusion.linear_start, linear_end=diffusion.linear_end, timesteps=diffusion.num_timesteps)

@@ -90,6 +90,38 @@ class GroundingNetInput:
         return {"boxes": boxes, "masks": masks, "positive_embeddings": positive_embeddings}
 
 
+class TextImageGroundingNetInput:
+    """text_image_grounding_tokinzer_input.py:5-61: pass-through of the six grounding tensors of a ``*_box_text_image`` checkpoint, zeros
+    as null.  ``prepare`` also accepts the two-argument call of interface.py:516."""
+    KEYS = ("boxes", "masks", "text_masks", "image_masks", "text_embeddings", "image_embeddings")
+
+    def __init__(self):
+        self.set = False
+
+    def prepare(self, batch, text_encoder=None):
+        self.set = True
+        text_embeddings = batch["text_embeddings"]
+        self.batch, self.max_box, self.in_dim = text_embeddings.shape
+        self.device = text_embeddings.device
+        self.dtype = text_embeddings.dtype
+        return {k: batch[k] for k in self.KEYS}
+
+    def get_null_input(self, batch=None, device=None, dtype=None):
+        assert self.set, "not set yet, cannot call this funcion"
+        batch = self.batch if batch is None else batch
+        device = self.device if device is None else device
+        dtype = self.dtype if dtype is None else dtype
+        z = lambda *shape: torch.zeros(*shape).type(dtype).to(device)
+        return {"boxes": z(batch, self.max_box, 4), "masks": z(batch, self.max_box), "text_masks": z(batch, self.max_box),
+                "image_masks": z(batch, self.max_box), "text_embeddings": z(batch, self.max_box, self.in_dim),
+                "image_embeddings": z(batch, self.max_box, self.in_dim)}
+
+
+def grounding_input_for(cfg: UNetConfig):
+    """the grounding-tokenizer input class that goes with the config's PositionNet"""
+    return TextImageGroundingNetInput() if cfg.grounding == "text_image" else GroundingNetInput()
+
+
 class UNetModel:
     """Callable with the reference's ``input`` dict (keys interface.py:527-535), returns eps [B,4,h,w].
 
@@ -166,8 +198,16 @@ class UNetModel:
         """``hw``: the latent side, or (h, w) for a rectangular latent (UNetEngine.set_conditioning)."""
         if key is not None and key == self._cond_key:
             return
-        self.engine.set_conditioning(context, relations, grounding["boxes"], grounding["masks"],
-                                     grounding["positive_embeddings"], hw)
+        if self.cfg.grounding == "text_image":
+            missing = [k for k in TextImageGroundingNetInput.KEYS if k not in grounding]
+            if missing:
+                raise ValueError(f"a text_image model needs the grounding keys {TextImageGroundingNetInput.KEYS}; missing {missing}")
+            self.engine.set_conditioning(context, relations, grounding["boxes"], grounding["masks"], grounding["text_embeddings"], hw,
+                                         text_masks=grounding["text_masks"], image_masks=grounding["image_masks"],
+                                         image_embeddings=grounding["image_embeddings"])
+        else:
+            self.engine.set_conditioning(context, relations, grounding["boxes"], grounding["masks"],
+                                         grounding["positive_embeddings"], hw)
         self._cond_key = key
 
     @torch.no_grad()

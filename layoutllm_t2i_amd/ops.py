@@ -470,6 +470,48 @@ def posnet_input(boxes, masks, emb, null_pos, null_xyxy, num_freqs, out):
     return out
 
 
+def posnet_input_ti(boxes, masks, text_masks, image_masks, text_emb, image_emb, null_text, null_image, null_xyxy, num_freqs, out_text, out_image):
+    """Both MLP inputs of the text_image PositionNet (gl_posnet_input_ti / _f32 by the outputs' dtype): out_text / out_image
+    [B, n, in_dim + 8 * num_freqs], both fp16 or both fp32."""
+    for t, n in ((boxes, "boxes"), (masks, "masks"), (text_masks, "text_masks"), (image_masks, "image_masks"), (text_emb, "text_emb"),
+                 (image_emb, "image_emb"), (null_text, "null_text"), (null_image, "null_image"), (null_xyxy, "null_xyxy")):
+        _req(t, F32, n, 4)
+        if not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous")
+    rows, in_dim = boxes.shape[0] * boxes.shape[1], text_emb.shape[-1]
+    if masks.numel() != rows or text_masks.numel() != rows or image_masks.numel() != rows or text_emb.numel() != rows * in_dim or \
+            image_emb.shape != text_emb.shape or null_text.numel() != in_dim or null_image.numel() != in_dim or null_xyxy.numel() != 8 * num_freqs:
+        raise ValueError("posnet_input_ti: inconsistent shapes")
+    f32out = out_text.dtype == F32
+    for o, n in ((out_text, "out_text"), (out_image, "out_image")):
+        _req(o, F32 if f32out else F16, n, 4)
+        if not o.is_contiguous() or o.numel() != rows * (in_dim + 8 * num_freqs):
+            raise ValueError(f"{n}: need a contiguous [rows, in_dim + 8 * num_freqs] tensor")
+    fn = _lib.lib().gl_posnet_input_ti_f32 if f32out else _lib.lib().gl_posnet_input_ti
+    check(fn(boxes.data_ptr(), masks.data_ptr(), text_masks.data_ptr(), image_masks.data_ptr(), text_emb.data_ptr(), image_emb.data_ptr(),
+             null_text.data_ptr(), null_image.data_ptr(), null_xyxy.data_ptr(), rows, in_dim, num_freqs, out_text.data_ptr(), out_image.data_ptr(),
+             _stream()), "gl_posnet_input_ti")
+    return out_text, out_image
+
+
+def image_ground_feature(feat: torch.Tensor, proj: torch.Tensor, norm: float = 28.7, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = norm * (feat[i] @ proj) / ||feat[i] @ proj||_2 in fp32 (interface.py:126-129): feat [n, dim], proj [dim, dim], dim <= 1024."""
+    _req(feat, F32, "feat", 4)
+    _req(proj, F32, "proj", 4)
+    if feat.dim() != 2 or tuple(proj.shape) != (feat.shape[1], feat.shape[1]) or not feat.is_contiguous() or not proj.is_contiguous():
+        raise ValueError("image_ground_feature: feat [n, dim] and proj [dim, dim], contiguous")
+    if feat.shape[1] > 1024:
+        raise ValueError("image_ground_feature: dim <= 1024")
+    if out is None:
+        out = torch.empty_like(feat)
+    _req(out, F32, "out", 4)
+    if out.shape != feat.shape or not out.is_contiguous():
+        raise ValueError("image_ground_feature: out must be contiguous with feat's shape")
+    check(_lib.lib().gl_image_ground_feature(feat.data_ptr(), proj.data_ptr(), feat.shape[0], feat.shape[1], float(norm), out.data_ptr(), _stream()),
+          "gl_image_ground_feature")
+    return out
+
+
 def timestep_embedding(t: torch.Tensor, dim: int, out: torch.Tensor):
     _req(t, F32, "t", 4)
     _req(out, F16, "out")

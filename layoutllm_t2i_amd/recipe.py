@@ -138,5 +138,21 @@ def synth_inputs(cfg: UNetConfig, batch: int, hw, n_boxes: int = 8, n_rel: int =
                 bx[b, i] = (g[0] + s, g[1] + s, g[2] - s, g[3] - s)
         masks[b, :n_boxes] = 1.0
     emb[:, :n_boxes] = normal("in.text_embeddings", (batch, n_boxes, cfg.pos_in_dim), seed)
+    if getattr(cfg, "grounding", "text") == "text_image":
+        # the six grounding tensors of a text_image checkpoint (text_image_grounding_net.py:41): box i of sample b is grounded on a phrase,
+        # on a reference image, or on both, in rotation (text only, image only, both), so every blend of the PositionNet is exercised
+        iemb = np.zeros((batch, mo, cfg.pos_in_dim), np.float32)
+        iemb[:, :n_boxes] = normal("in.image_embeddings", (batch, n_boxes, cfg.pos_in_dim), seed)
+        tm = np.zeros((batch, mo), np.float32)
+        im = np.zeros((batch, mo), np.float32)
+        for b in range(batch):
+            for i in range(n_boxes):
+                kind = (b + i) % 3
+                tm[b, i] = 1.0 if kind != 1 else 0.0
+                im[b, i] = 1.0 if kind != 0 else 0.0
+        emb = emb * tm[..., None]            # an ungrounded slot carries zeros (interface.py:166-176), like the padding
+        iemb = iemb * im[..., None]
+        return dict(x=x, context=context, uc=uc, relations=relations, boxes=bx, masks=masks, text_masks=tm, image_masks=im,
+                    text_embeddings=emb, image_embeddings=iemb)
     return dict(x=x, context=context, uc=uc, relations=relations, boxes=bx, masks=masks,
                 positive_embeddings=emb)

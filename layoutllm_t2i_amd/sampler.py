@@ -89,11 +89,11 @@ class PLMSSampler(object):
             gn = model.grounding_tokenizer_input.get_null_input()
             ctx = torch.cat([f32(input["context"]), f32(uc)], 0)
             rel = torch.cat([f32(input["relations"])] * 2, 0)
-            grounding = {k: torch.cat([f32(g[k]), f32(gn[k])], 0) for k in ("boxes", "masks", "positive_embeddings")}
+            grounding = {k: torch.cat([f32(g[k]), f32(gn[k])], 0) for k in gn}      # whatever keys the grounding tokenizer input has (3 for text, 6 for text_image)
             reps = 2
         else:
             ctx, rel = f32(input["context"]), f32(input["relations"])
-            grounding = {k: f32(g[k]) for k in ("boxes", "masks", "positive_embeddings")}
+            grounding = {k: f32(v) for k, v in g.items() if torch.is_tensor(v)}
             reps = 1
         model.set_conditioning(ctx, rel, grounding, H if H == W else (H, W), key=None)      # (H, W): the rectangular entry and its shape check
 

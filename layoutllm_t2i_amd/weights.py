@@ -280,6 +280,14 @@ def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_
     P.emb_total = off
     norm("out.0")
     conv3("out.2")
+    if cfg.grounding == "text_image":
+        W["position_net.null_text"] = g("position_net.null_text_feature").contiguous()
+        W["position_net.null_image"] = g("position_net.null_image_feature").contiguous()
+        W["position_net.null_xyxy"] = g("position_net.null_position_feature").contiguous()
+        for chain in ("linears_text", "linears_image"):
+            for i in (0, 2, 4):
+                lin(f"position_net.{chain}.{i}")
+        return P.to_flat()
     W["position_net.null_pos"] = g("position_net.null_positive_feature").contiguous()
     W["position_net.null_xyxy"] = g("position_net.null_position_feature").contiguous()
     for i in (0, 2, 4):
