@@ -330,6 +330,13 @@ int gl_plms_update(const float* x, const float* e, const float* e1, const float*
                    float sqrt_aprev, float dir_coef, int64_t n, float* x_prev, void* stream);
 int gl_pack_latent(const float* x, int32_t B, int32_t C, int32_t hw, int32_t Cpad, int32_t reps, int32_t split, void* out,
                    void* stream);
+/* gl_pack_latent_extra: gl_pack_latent over the channel concatenation of TWO sources (the first-conv input of an inpaint_mode UNet,
+ * openaimodel.py:439: cat([x, inpainting_extra_input], dim=1)): x fp32 [B, C, hw] and extra fp32 [Bs, Ce, hw], Bs = 1 (one extra for every
+ * sample) or B -> fp16 NHWC [reps*B, hw, Cpad].  With Ct = C + Ce: channels [0, Ct) = fp16 of [x | extra], zero behind; split != 0
+ * (Cpad >= 3 Ct): [0, Ct) = hi, [Ct, 2 Ct) = fp16(v - hi), [2 Ct, 3 Ct) = hi again, zero behind -- the [Whi | Whi | Wlo | 0] first-conv packing
+ * over the 9 concatenated channels.  Additive to ABI 15. */
+int gl_pack_latent_extra(const float* x, const float* extra, int32_t B, int32_t Bs, int32_t C, int32_t Ce, int32_t hw, int32_t Cpad,
+                         int32_t reps, int32_t split, void* out, void* stream);
 
 /*
  * VAE decode stage (AutoencoderKL.decode autoencoder.py:40-44, Decoder.forward model.py:535-568).
@@ -380,6 +387,12 @@ typedef struct gl_unet_config {          /* UNetModel.__init__ arguments (openai
                                     handle is conditioned through gl_set_conditioning_ti.  n_ground = max_objs (0) or 2 * max_objs (1) is the token count
                                     of the gated self-attention (keys N + n_ground); gl_create rejects n_ground > 64.  The relation chain keeps
                                     max_objs boxes. */
+    int32_t inpaint_mode;        /* additive to ABI 15.  0 = the first conv reads the latent alone (a zeroed field keeps the earlier behaviour).  1 = GLIGEN's
+                                    inpainting checkpoints (openaimodel.py:293-299, :436-439): input_blocks.0.0 is [mc, 2 * in_channels + 1, 3, 3] and reads
+                                    cat([x, z0 * mask, mask]); in_channels stays the latent's channel count.  The packed weight keeps its [mc, 9 * 64] slot
+                                    ([Whi | Whi | Wlo | 0] over 3 * 9 = 27 of the 64 padded channels), the table has no sd_first_conv.* entries (the conv is
+                                    not restorable, :296), and every forward needs gl_set_inpaint_extra first.  gl_create rejects
+                                    2 * in_channels + 1 > 64. */
 } gl_unet_config;
 
 typedef struct gl_engine gl_engine;      /* opaque */
@@ -429,8 +442,16 @@ int gl_set_conditioning_hw(gl_engine* e, const float* context, const float* rela
 int gl_set_conditioning_ti(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
                            const float* text_masks, const float* image_masks, const float* text_emb, const float* image_emb, int32_t Bn,
                            int32_t Lc, int32_t R, int32_t h, int32_t w, void* stream);
+/* gl_set_inpaint_extra: the inpainting_extra_input of an inpaint_mode handle (gligen_inference.py:406-407: cat([z0 * mask, mask], dim=1)),
+ * extra fp32 [Bs, in_channels + 1, h, w] on the device, Bs = 1 (one extra for every sample) or the number of samples Bn / reps.  It is copied
+ * (stream-ordered) into a buffer of the handle's pool whose address the captured graphs read at replay time, so a new extra needs no new
+ * capture.  Valid only after a conditioning call has fixed (h, w); a conditioning call with another (h, w) invalidates it.  On an inpaint
+ * handle gl_unet_forward / gl_plms_step return GL_ERR_BAD_ARG (with a gl_last_error message, before anything is launched) while no extra is
+ * set, when Bs is neither 1 nor Bn / reps, and for sd_conv != 0; on any other handle this entry returns GL_ERR_BAD_ARG with a message.
+ * Additive to ABI 15. */
+int gl_set_inpaint_extra(gl_engine* e, const float* extra, int32_t Bs, void* stream);
 /* gl_last_error: the message of the handle's last GL_ERR_BAD_ARG that carries one (a conditioning entry of the wrong grounding family, a
- * latent shape that breaks the shape rule, strict mode without split weights), copied NUL-terminated into dst (at most bytes - 1
+ * latent shape that breaks the shape rule, strict mode without split weights, the inpaint_mode checks of gl_set_inpaint_extra), copied NUL-terminated into dst (at most bytes - 1
  * characters).  Returns the message's full length, 0 when there is none.  Additive to ABI 15. */
 int gl_last_error(const gl_engine* e, char* dst, int32_t bytes);
 /* gl_unet_forward: eps[Bn, out_ch, hw, hw] fp32 = UNet(x, t | conditioning).  x fp32 NCHW [Bn / reps, in_ch, hw, hw]:

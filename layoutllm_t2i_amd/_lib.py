@@ -104,6 +104,7 @@ class UNetConfigC(C.Structure):
         ("max_objs", i32),
         ("split_weights", i32),
         ("grounding", i32),
+        ("inpaint_mode", i32),
     ]
 
 
@@ -170,6 +171,7 @@ PROTOTYPES = {
     "gl_cfg_combine": (i32, [fp, f32, i64, fp, vp]),
     "gl_plms_update": (i32, [fp, fp, fp, fp, fp, f32, f32, f32, f32, f32, f32, f32, f32, f32, i64, fp, vp]),
     "gl_pack_latent": (i32, [fp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "gl_pack_latent_extra": (i32, [fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "gl_latent_affine_pack": (i32, [fp, fp, fp, f32, i32, i32, i32, i32, vp, vp]),
     "gl_softmax_rows": (i32, [vp, i32, i32, i32, f32, vp]),
     "gl_abi_version": (i32, []),
@@ -189,6 +191,7 @@ PROTOTYPES = {
     "gl_posnet_input_ti": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp, vp, vp]),
     "gl_posnet_input_ti_f32": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, fp, fp, vp]),
     "gl_image_ground_feature": (i32, [fp, fp, i32, i32, f32, fp, vp]),
+    "gl_set_inpaint_extra": (i32, [vp, fp, i32, vp]),
     "gl_last_error": (i32, [vp, C.c_char_p, i32]),
     "gl_unet_forward": (i32, [vp, fp, fp, f32, i32, f32, i32, fp, i32, vp]),
     "gl_plms_step": (i32, [vp, C.POINTER(PlmsStepArgs), vp]),
@@ -303,6 +306,7 @@ def unet_config_c(cfg) -> UNetConfigC:
     c.pos_in_dim, c.pos_out_dim, c.fourier_freqs, c.max_objs = cfg.pos_in_dim, cfg.pos_out_dim, cfg.fourier_freqs, cfg.max_objs
     c.split_weights = int(bool(getattr(cfg, "split_weights", False)))
     c.grounding = GROUNDING_IDS[getattr(cfg, "grounding", "text")]
+    c.inpaint_mode = int(bool(getattr(cfg, "inpaint_mode", False)))
     return c
 
 

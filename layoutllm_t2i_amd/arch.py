@@ -38,6 +38,14 @@ class UNetConfig:
     # per box), "text_image" = text_image_grounding_net.PositionNet (GLIGEN's *_box_text_image checkpoints: a text token and an image token
     # per box, gl_unet_config.grounding = 1)
     grounding: str = "text"
+    # GLIGEN's inpainting checkpoints (checkpoint_inpainting_text*.pth; openaimodel.py:293-299, :436-439): the first conv also reads the masked
+    # image latent and the mask, cat([x, z0 * mask, mask]) -- in_channels stays the LATENT's channel count (gl_unet_config.inpaint_mode)
+    inpaint_mode: bool = False
+
+    @property
+    def first_conv_in(self) -> int:
+        """input channels of input_blocks.0.0: the latent, plus the masked latent and the mask of an inpaint_mode model (4 + 4 + 1)"""
+        return self.in_channels + (self.in_channels + 1 if self.inpaint_mode else 0)
 
     @property
     def n_ground(self) -> int:
@@ -53,8 +61,12 @@ class UNetConfig:
         return self.fourier_freqs * 2 * 4
 
     @staticmethod
-    def from_dict(params: dict) -> "UNetConfig":
-        """Accepts the ``config['model']['params']`` dict of a GLIGEN checkpoint."""
+    def from_dict(params: dict, allow_inpaint: bool = False) -> "UNetConfig":
+        """Accepts the ``config['model']['params']`` dict of a GLIGEN checkpoint.
+
+        ``allow_inpaint``: an ``inpaint_mode`` checkpoint (9-channel first conv) shares every parameter name with the layout-to-image UNet but
+        needs ``inpainting_extra_input`` on every forward, so a caller has to say that it supplies one (``interface.load_ckpt`` does); without
+        the flag such a config keeps raising, like the other look-alike variants below."""
         gt = (params.get("grounding_tokenizer") or {}).get("params", {})
         target = (params.get("grounding_tokenizer") or {}).get("target")
         if target is None or target.endswith(".text_grounding_net.PositionNet") or target == "text_grounding_net.PositionNet":
@@ -69,9 +81,11 @@ class UNetConfig:
             raise NotImplementedError(f"fuser_type={params.get('fuser_type')!r}: only 'gatedSA' is on the layout-to-image path")
         if int(params.get("transformer_depth", 1)) != 1:
             raise NotImplementedError("transformer_depth != 1 is not supported")
-        if params.get("inpaint_mode", False):
-            raise NotImplementedError("inpaint_mode checkpoints (9-channel first conv) are not on the layout-to-image path")
+        if params.get("inpaint_mode", False) and not allow_inpaint:
+            raise NotImplementedError("inpaint_mode checkpoints (9-channel first conv) are not on the layout-to-image path: pass "
+                                      "allow_inpaint=True and feed inpainting_extra_input (interface.load_ckpt / run_one_image do)")
         if params.get("grounding_downsampler") is not None:
+            # (together with inpaint_mode the reference itself stops at a breakpoint(), openaimodel.py:437-438)
             raise NotImplementedError("grounding_downsampler is not on the text_layout path")
         if not params.get("use_spatial_transformer", True):
             raise NotImplementedError("use_spatial_transformer=False is not supported")
@@ -89,6 +103,7 @@ class UNetConfig:
             pos_out_dim=int(gt.get("out_dim", 768)),
             fourier_freqs=int(gt.get("fourier_freqs", 8)),
             grounding=grounding,
+            inpaint_mode=bool(params.get("inpaint_mode", False)),
         )
 
 
@@ -275,7 +290,9 @@ def param_shapes(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
     out["time_embed.2.weight"] = (te, te)
     out["time_embed.2.bias"] = (te,)
     for l in plan.all_layers():
-        if l.kind in ("conv_in", "down", "up"):
+        if l.kind == "conv_in":
+            out.update(conv_params(l.prefix, cfg.first_conv_in, l.cout))      # 9 input channels on an inpaint_mode model
+        elif l.kind in ("down", "up"):
             out.update(conv_params(l.prefix, l.cin, l.cout))
         elif l.kind == "res":
             out.update(res_params(l.prefix, l.cin, l.cout, te))

@@ -153,6 +153,9 @@ struct gl_engine {
     // conditioning
     bool cond_set = false;
     int Bn = 0, R = 0, Lc = 0, lat_h = 0, lat_w = 0;     // (lat_h, lat_w): the latent's rows and columns (gl_set_conditioning_hw)
+    // inpaint_mode handles: the inpainting_extra_input [extra_bs, in_channels + 1, lat_h, lat_w] lives in the pool buffer "in.extra" (gl_set_inpaint_extra)
+    bool extra_set = false;
+    int extra_bs = 0;
     // graphs
     std::map<std::tuple<int, int, int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
     float fuser_scale_cur = -1e30f;
@@ -312,7 +315,7 @@ void build_table(gl_engine* e) {
     add_lin(e, "time_embed.0", te, mc);
     add_lin(e, "time_embed.2", te, te);
     add_conv3(e, "input_blocks.0.0", CIN_PAD, mc, false);
-    add_conv3(e, "sd_first_conv", CIN_PAD, mc, false);
+    if (!c.inpaint_mode) add_conv3(e, "sd_first_conv", CIN_PAD, mc, false);       // (an inpaint_mode first conv is not restorable, openaimodel.py:296)
     int off = 0;
     for_all_layers(e, [&](LayerD& l) {
         const std::string& p = l.prefix;
@@ -383,6 +386,8 @@ void build_table(gl_engine* e) {
     add_lin(e, "position_net.linears.4", c.pos_out_dim, 512);
 }
 
+// input channels of input_blocks.0.0: the latent, + the masked latent and the mask of an inpaint_mode handle (openaimodel.py:293-299)
+inline int first_conv_in(const gl_unet_config& c) { return c.in_channels + (c.inpaint_mode ? c.in_channels + 1 : 0); }
 // grounding tokens per sample (the fuser's extra keys): max_objs for the text PositionNet, 2 * max_objs for text_image
 inline int n_ground(const gl_unet_config& c) { return c.grounding == 1 ? 2 * c.max_objs : c.max_objs; }
 
@@ -950,7 +955,16 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
     half_t* xin = e->h16("in.x", (size_t)Bn * sh * sw * CIN_PAD);
     CKP(xin);
     ++r.launches;
-    CK(gl_pack_latent(x_lat, Bn / reps, cfg.in_channels, sh * sw, CIN_PAD, share ? 1 : reps, g_in_split && 3 * cfg.in_channels <= CIN_PAD, xin, st));
+    if (cfg.inpaint_mode) {
+        // cat([x, inpainting_extra_input], dim=1) (openaimodel.py:439) folded into the pack: one launch, like the text handle's.  Both CFG halves
+        // read the same extra (plms.py:118-121), so the shared prefix stays valid.
+        const float* extra = e->f32("in.extra", (size_t)e->extra_bs * (cfg.in_channels + 1) * sh * sw);
+        CKP(extra);
+        CK(gl_pack_latent_extra(x_lat, extra, Bn / reps, e->extra_bs, cfg.in_channels, cfg.in_channels + 1, sh * sw, CIN_PAD, share ? 1 : reps,
+                                g_in_split && 3 * first_conv_in(cfg) <= CIN_PAD, xin, st));
+    } else {
+        CK(gl_pack_latent(x_lat, Bn / reps, cfg.in_channels, sh * sw, CIN_PAD, share ? 1 : reps, g_in_split && 3 * cfg.in_channels <= CIN_PAD, xin, st));
+    }
     const std::string fc = sd_conv ? "sd_first_conv" : "input_blocks.0.0";
     // fp16 copies of stream tensors: only where a down / up conv consumes the tensor (precise mode: every GroupNorm and 1x1 conv
     // reads the fp32 stream), or everywhere in the round-3 fp16-copy mode
@@ -1078,7 +1092,8 @@ extern "C" int gl_create(const gl_unet_config* cfg, gl_engine** out) {
     if (cfg->model_channels % 64 || cfg->context_dim % 64 || cfg->pos_in_dim % 8 || cfg->pos_out_dim != cfg->context_dim) return GL_ERR_UNSUPPORTED;
     if ((cfg->pos_in_dim + 8 * cfg->fourier_freqs) % 64) return GL_ERR_UNSUPPORTED;
     if (cfg->grounding != 0 && cfg->grounding != 1) return GL_ERR_UNSUPPORTED;
-    if (cfg->in_channels > CIN_PAD || cfg->max_objs <= 0 || n_ground(*cfg) > 64) return GL_ERR_UNSUPPORTED;
+    if (cfg->max_objs <= 0 || n_ground(*cfg) > 64) return GL_ERR_UNSUPPORTED;
+    if ((cfg->inpaint_mode != 0 && cfg->inpaint_mode != 1) || first_conv_in(*cfg) > CIN_PAD) return GL_ERR_UNSUPPORTED;
     gl_engine* e = new gl_engine();
     e->cfg = *cfg;
     build_plan(e);
@@ -1122,6 +1137,10 @@ extern "C" int gl_load_weights(gl_engine* e, const void* packed, int64_t bytes, 
     e->device = dev;
     CK(gl_init());
     e->wbase = reinterpret_cast<const char*>(packed);
+    if (has_sd_conv && e->cfg.inpaint_mode) {
+        e->err = "gl_load_weights: an inpaint_mode handle has no sd_first_conv slots (its first conv is not restorable)";
+        return GL_ERR_BAD_ARG;
+    }
     e->has_sd = has_sd_conv != 0;
     e->drop_graphs();
     // the scalar gates tanh(alpha) live in the packed buffer; fetch them once (tiny, synchronous)
@@ -1242,6 +1261,7 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     const int nch = ti ? 2 : 1;
     if (ti && (!text_masks || !image_masks || !image_emb)) return GL_ERR_BAD_ARG;
     if (Bn != e->Bn || Lc != e->Lc || R != e->R || h != e->lat_h || w != e->lat_w) e->drop_graphs();     // shapes are part of the graph keys anyway
+    if (h != e->lat_h || w != e->lat_w) e->extra_set = false;       // the inpainting extra was sized for the previous latent shape
     e->pool_changed = false;
     e->Bn = Bn; e->Lc = Lc; e->R = R; e->lat_h = h; e->lat_w = w;
     Run r{e, st, e->buf("splitk.ws", WS_BYTES)};
@@ -1420,9 +1440,34 @@ extern "C" int gl_set_conditioning_hw(gl_engine* e, const float* context, const 
     return set_conditioning(e, context, relations, boxes, masks, pos_emb, nullptr, nullptr, nullptr, Bn, Lc, R, h, w, stream);
 }
 
+extern "C" int gl_set_inpaint_extra(gl_engine* e, const float* extra, int32_t Bs, void* stream) {
+    if (!e) return GL_ERR_BAD_ARG;
+    if (!e->cfg.inpaint_mode) { e->err = "gl_set_inpaint_extra: the handle was created with inpaint_mode = 0 (its first conv reads the latent alone)"; return GL_ERR_BAD_ARG; }
+    if (!e->cond_set) { e->err = "gl_set_inpaint_extra: no conditioning call has fixed the latent shape yet"; return GL_ERR_BAD_ARG; }
+    if (!extra || Bs < 1 || Bs > e->Bn) { e->err = "gl_set_inpaint_extra: extra must be a device pointer to Bs = 1 or Bn / reps samples"; return GL_ERR_BAD_ARG; }
+    const size_t n = (size_t)Bs * (e->cfg.in_channels + 1) * e->lat_h * e->lat_w;
+    e->pool_changed = false;
+    float* dst = e->f32("in.extra", n);
+    CKP(dst);
+    // the captured graphs hold this buffer's address and the broadcast flag of the pack launch: a moved buffer or another Bs makes them stale
+    if (e->pool_changed || (e->extra_set && Bs != e->extra_bs)) { e->drop_graphs(); e->pool_changed = false; }
+    if (hipMemcpyAsync(dst, extra, n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return GL_ERR_BAD_ARG;
+    e->extra_bs = Bs;
+    e->extra_set = true;
+    return 0;
+}
+
 extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev, float t_host, int32_t reps, float fuser_scale, int32_t sd_conv,
                                float* eps, int32_t use_graph, void* stream) {
     if (!e || !e->cond_set || !x || !eps || reps < 1 || (e->Bn % reps) != 0) return GL_ERR_BAD_ARG;
+    if (e->cfg.inpaint_mode) {              // host-side checks, before anything is launched
+        if (sd_conv) { e->err = "gl_unet_forward: sd_conv != 0 on an inpaint_mode handle (its first conv is not restorable)"; return GL_ERR_BAD_ARG; }
+        if (!e->extra_set) { e->err = "gl_unet_forward: an inpaint_mode handle needs gl_set_inpaint_extra after the conditioning call that fixed (h, w)"; return GL_ERR_BAD_ARG; }
+        if (e->extra_bs != 1 && e->extra_bs != e->Bn / reps) {
+            e->err = "gl_unet_forward: the inpainting extra has " + std::to_string(e->extra_bs) + " samples, the latent " + std::to_string(e->Bn / reps);
+            return GL_ERR_BAD_ARG;
+        }
+    }
     gl_opts_scope opts_scope(e->ovr);       // this handle's option overrides are in effect for the call
     if (sd_conv && !e->has_sd) return GL_ERR_BAD_ARG;
     const gl_unet_config& cfg = e->cfg;

@@ -267,6 +267,30 @@ __global__ void pack_latent_kernel(const float* __restrict__ x, int B, int C, in
     }
 }
 
+// pack_latent_kernel over the channel concatenation of two sources (an inpaint_mode UNet's first-conv input, openaimodel.py:439): x fp32 [B, C, hw]
+// and extra fp32 [Bs, Ce, hw] (Bs = 1: one extra for every sample) -> fp16 [reps*B, hw, Cpad].  Ct = C + Ce: channels [0, Ct) = hi of [x | extra];
+// split: [Ct, 2 Ct) = lo, [2 Ct, 3 Ct) = hi again; zero behind
+__global__ void pack_latent_extra_kernel(const float* __restrict__ x, const float* __restrict__ extra, int B, int Bs, int C, int Ce, int hw,
+                                         int Cpad, int reps, int split, half_t* __restrict__ out) {
+    const int Ct = C + Ce, used = split ? 3 * Ct : Ct;
+    const size_t total = (size_t)reps * B * hw * Cpad;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % Cpad);
+        const size_t t = i / Cpad;
+        const int p = (int)(t % hw);
+        const int rb = (int)(t / hw);
+        const int b = rb % B;
+        half_t o = (half_t)0.0f;
+        if (c < used) {
+            const int part = c / Ct, cc = c - part * Ct;
+            const float v = cc < C ? x[((size_t)b * C + cc) * hw + p] : extra[((size_t)(Bs == 1 ? 0 : b) * Ce + (cc - C)) * hw + p];
+            const half_t hi = (half_t)v;
+            o = part == 1 ? (half_t)(v - (float)hi) : hi;
+        }
+        out[i] = o;
+    }
+}
+
 // Row softmax in place over fp16 [rows, n] (row stride ld): the single-head d = C mid-block attention of
 // the VAE decoder (model.py:180-186) runs as two GEMMs around this kernel because its head dim (512)
 // exceeds the flash kernel's register budget; it runs once per image, not per step.
@@ -437,6 +461,16 @@ extern "C" int gl_pack_latent(const float* x, int32_t B, int32_t C, int32_t hw, 
     if (!x || !out || B <= 0 || C <= 0 || hw <= 0 || Cpad < (split ? 3 * C : C) || reps <= 0) return GL_ERR_BAD_ARG;
     pack_latent_kernel<<<dim3(ew_blocks((size_t)reps * B * hw * Cpad)), dim3(256), 0, (hipStream_t)stream>>>(
         x, B, C, hw, Cpad, reps, split, reinterpret_cast<half_t*>(out));
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_pack_latent_extra(const float* x, const float* extra, int32_t B, int32_t Bs, int32_t C, int32_t Ce, int32_t hw, int32_t Cpad,
+                                    int32_t reps, int32_t split, void* out, void* stream) {
+    if (!x || !extra || !out || B <= 0 || C <= 0 || Ce <= 0 || hw <= 0 || reps <= 0 || (Bs != 1 && Bs != B)) return GL_ERR_BAD_ARG;
+    if (Cpad < (split ? 3 : 1) * (C + Ce)) return GL_ERR_BAD_ARG;
+    pack_latent_extra_kernel<<<dim3(ew_blocks((size_t)reps * B * hw * Cpad)), dim3(256), 0, (hipStream_t)stream>>>(
+        x, extra, B, Bs, C, Ce, hw, Cpad, reps, split, reinterpret_cast<half_t*>(out));
     GL_CHECK_LAUNCH();
     return 0;
 }

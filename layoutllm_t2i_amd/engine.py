@@ -53,6 +53,7 @@ class UNetEngine:
         self._pool: Dict[Tuple, torch.Tensor] = {}
         self.cond: Optional[dict] = None
         self._cond_refs: Tuple = ()
+        self._extra_ref: Optional[torch.Tensor] = None
         self.use_graphs = True
 
     def __del__(self):
@@ -149,6 +150,32 @@ class UNetEngine:
         self._cond_refs = (context, relations, boxes, masks, pe)      # read asynchronously by the launched kernels
         self.cond = dict(Bn=Bn, mo=mo, R=R, Lc=Lc, hw=hw, H=h, W=w)
 
+    @torch.no_grad()
+    def set_inpaint_extra(self, extra: torch.Tensor) -> None:
+        """The ``inpainting_extra_input`` of an inpaint_mode model (gligen_inference.py:406-407: cat([z0 * mask, mask], dim=1)): fp32
+        [1 | samples, in_channels + 1, h, w] at the conditioning's latent shape (gl_set_inpaint_extra).  The engine copies it into a pool
+        buffer that its captured graphs read at replay time; call it after ``set_conditioning``, once per image (not per step)."""
+        if not self.cfg.inpaint_mode:
+            raise ValueError("set_inpaint_extra on a model without inpaint_mode (its first conv reads the latent alone)")
+        c = self.cond
+        if c is None:
+            raise RuntimeError("call set_conditioning() first")
+        extra = torch.as_tensor(extra, dtype=F32).to(self.dev).contiguous()
+        want = (self.cfg.in_channels + 1, c["H"], c["W"])
+        if extra.dim() != 4 or tuple(extra.shape[1:]) != want or not 1 <= extra.shape[0] <= c["Bn"]:
+            raise ValueError(f"inpainting_extra_input {tuple(extra.shape)}: need [1 | samples, {want[0]}, {want[1]}, {want[2]}]")
+        with torch.cuda.device(self.dev):
+            self._check(self._lib.gl_set_inpaint_extra(self.handle, extra.data_ptr(), int(extra.shape[0]), self._stream()), "gl_set_inpaint_extra")
+        self._extra_ref = extra             # read asynchronously by the stream-ordered copy
+
+    def _check(self, code: int, what: str) -> None:
+        """``check`` with the handle's gl_last_error message: the entries of an inpaint_mode handle leave one for every refusal"""
+        if code != 0 and self.cfg.inpaint_mode:
+            msg = _lib.last_error(self.handle)
+            if msg:
+                raise _lib.HipLibraryError(f"{what} failed with code {code}: {msg}")
+        check(code, what)
+
     # ------------------------------------------------------------------ forward
     def _check_x(self, x_lat: torch.Tensor, reps: int):
         c = self.cond
@@ -183,8 +210,8 @@ class UNetEngine:
         else:
             t_host = float(t)
         with torch.cuda.device(self.dev):
-            check(self._lib.gl_unet_forward(self.handle, x_lat.data_ptr(), t_dev, t_host, reps, float(fuser_scale), int(bool(sd_conv)),
-                                            eps_out.data_ptr(), int(self.use_graphs), self._stream()), "gl_unet_forward")
+            self._check(self._lib.gl_unet_forward(self.handle, x_lat.data_ptr(), t_dev, t_host, reps, float(fuser_scale), int(bool(sd_conv)),
+                                                  eps_out.data_ptr(), int(self.use_graphs), self._stream()), "gl_unet_forward")
         return eps_out
 
     @torch.no_grad()
@@ -211,5 +238,5 @@ class UNetEngine:
         if sd_conv and not self.P.has_sd_conv:
             raise RuntimeError("SD first-conv weights were not packed")
         with torch.cuda.device(self.dev):
-            check(self._lib.gl_plms_step(self.handle, C.byref(a), self._stream()), "gl_plms_step")
+            self._check(self._lib.gl_plms_step(self.handle, C.byref(a), self._stream()), "gl_plms_step")
         return x_out

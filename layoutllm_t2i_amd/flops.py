@@ -27,7 +27,7 @@ def unet_forward_flops(cfg: UNetConfig, hw, fuser_on: bool = True, n_ctx: int = 
         n = side[0] * side[1]
         g = 0.0
         if l.kind == "conv_in":
-            g += lin(n, 9 * l.cin, l.cout)
+            g += lin(n, 9 * cfg.first_conv_in, l.cout)      # 4, or 9 input channels on an inpaint_mode model
         elif l.kind == "res":
             g += lin(n, 9 * l.cin, l.cout) + lin(n, 9 * l.cout, l.cout) + lin(1, te, l.cout)
             if l.cin != l.cout:

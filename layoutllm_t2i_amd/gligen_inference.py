@@ -18,8 +18,11 @@ a passed ``starting_noise`` [bs, 4, h, w] decides the shape itself (image = 8h x
 
 ``meta["input_image"]`` (a path or a PIL.Image) inpaints that image inside the layout boxes (gligen_inference.py:393-407): it is
 encoded by the checkpoint's VAE encoder, the mask is 0 inside the boxes, and the PLMS sampler replaces the known region of the
-latent at every step.  The reference asserts a 9-channel ``inpaint_mode`` checkpoint at this point; this package keeps rejecting
-those and runs this latent-blend inpainting on the 4-channel text_layout model instead.
+latent at every step.  The reference asserts a 9-channel ``inpaint_mode`` checkpoint at this point (:398).  Such a checkpoint
+(``checkpoint_inpainting_text.pth`` / ``checkpoint_inpainting_text_image.pth``: ``inpaint_mode: True``, first conv ``[320, 9, 3, 3]``) loads
+here and additionally feeds ``cat([z0 * mask, mask])`` to the first conv on every forward (:406-407, openaimodel.py:436-439); it needs
+``meta["input_image"]`` (ValueError otherwise).  A 4-channel text_layout / text_image checkpoint with ``input_image`` keeps running the
+latent-blend inpainting alone, which the reference refuses.
 """
 from __future__ import annotations
 

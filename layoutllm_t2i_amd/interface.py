@@ -134,22 +134,23 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
     keeps the GLIGEN conv.  ``GLIGEN_ALLOW_NO_SD_CONV=1`` opts out explicitly (first_conv_restorable = False)."""
     saved_ckpt = torch.load(ckpt_path, map_location="cpu")
     config = saved_ckpt["config_dict"]["_content"]
-    cfg = UNetConfig.from_dict(config["model"]["params"])
+    cfg = UNetConfig.from_dict(config["model"]["params"], allow_inpaint=True)      # _run builds the inpainting extra such a model needs
     if strict is None:
         strict = os.environ.get("GLIGEN_STRICT") == "1"
     if strict:
         import dataclasses
         cfg = dataclasses.replace(cfg, split_weights=True)
-    sd_path = find_sd_first_conv(ckpt_path)
+    # (an inpaint_mode checkpoint's 9-channel first conv is not restorable, openaimodel.py:296: the SD conv file is neither looked for nor missed)
+    sd_path = None if cfg.inpaint_mode else find_sd_first_conv(ckpt_path)
     allow_missing = os.environ.get("GLIGEN_ALLOW_NO_SD_CONV") == "1"
-    if sd_path is None and not allow_missing:
+    if sd_path is None and not allow_missing and not cfg.inpaint_mode:
         warnings.warn(
             "SD_input_conv_weight_bias.pth not found (looked at $GLIGEN_SD_FIRST_CONV, next to the checkpoint, $GLIGEN_HOME and "
             "the importable ldm package's GLIGEN directory): the first fuser-scale-0 step will raise, exactly where the reference "
             "fails (openaimodel.py:393-405); schedules without a scale-0 stage run.  GLIGEN_ALLOW_NO_SD_CONV=1 keeps the GLIGEN conv "
             "instead (results then differ from the reference).")
     model = UNetModel(cfg, saved_ckpt["model"], device=device, sd_first_conv=load_sd_first_conv(sd_path),
-                      allow_missing_sd_conv=sd_path is None and allow_missing)
+                      allow_missing_sd_conv=sd_path is None and allow_missing and not cfg.inpaint_mode)
     if strict:
         model.set_strict(True)
     dparams = config["diffusion"].get("params", {})
@@ -449,20 +450,27 @@ def load_input_image(image, side, device=None) -> torch.Tensor:
     return (x.float().unsqueeze(0).to(device) / 255 - 0.5) / 0.5
 
 
+def build_inpainting_extra(z0, mask):
+    """gligen_inference.py:406-407: ``masked_z = z0 * mask``, ``cat([masked_z, mask], dim=1)`` -- what an inpaint_mode UNet's first conv reads
+    next to the latent.  z0 [1|B, 4, h, w] (broadcast over the mask's batch), mask [B, 1, h, w] -> [B, 5, h, w]."""
+    return torch.cat([z0 * mask, mask], dim=1)
+
+
 @torch.no_grad()
 def denoise(all_models, context, uc, relations, grounding_batch, starting_noise, alpha_type=None, guidance_scale=7.5,
-            steps=PLMS_STEPS, mask=None, x0=None):
+            steps=PLMS_STEPS, mask=None, x0=None, inpainting_extra_input=None):
     """The denoising hot path proper, from conditioning tensors to the final latent
     (run_batch_images lines interface.py:505-539 without text/VAE stages).  ``mask`` [1|B, 1, h, w] (1 = keep) and ``x0``
     [1|B, 4, h, w] (the encoded input image): inpainting, plms.py:95-99.  The latent's shape [B, 4, h, w] is ``starting_noise``'s
-    (plms.py:68-71); h != w needs both to be multiples of 2^(number of UNet downsamples) = 8."""
+    (plms.py:68-71); h != w needs both to be multiples of 2^(number of UNet downsamples) = 8.  ``inpainting_extra_input`` [1|B, 5, h, w]: the
+    extra first-conv input of an inpaint_mode model (required there, ignored by every other model)."""
     model, autoencoder, text_encoder, diffusion, config = all_models
     _check_noise(model, starting_noise)
     sampler = PLMSSampler(diffusion, model, alpha_generator_func=partial(alpha_generator, type=alpha_type),
                           set_alpha_scale=set_alpha_scale)
     grounding_input = model.grounding_tokenizer_input.prepare(grounding_batch, text_encoder)
     input = dict(x=starting_noise, timesteps=None, context=context, relations=relations, grounding_input=grounding_input,
-                 inpainting_extra_input=None, grounding_extra_input=None)
+                 inpainting_extra_input=inpainting_extra_input, grounding_extra_input=None)
     shape = tuple(starting_noise.shape)
     return sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=mask, x0=x0)
 
@@ -489,6 +497,11 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
         # (the reference would prepare image tokens and drop them silently: text_layout_tokinzer_input.py reads three keys)
         raise ValueError("meta['images'] given to a text-only checkpoint: image grounding needs a *_box_text_image checkpoint "
                          "(grounding_tokenizer target text_image_grounding_net.PositionNet)")
+    inpaint_model = bool(getattr(model.cfg, "inpaint_mode", False))
+    if inpaint_model and meta.get("input_image") is None:
+        # (the reference would fail inside the first forward, on th.cat([h, None]), openaimodel.py:439)
+        raise ValueError("an inpaint_mode checkpoint needs meta['input_image']: its first conv reads the masked image latent and the mask "
+                         "(layout-to-image without an input image runs on the 4-channel checkpoints)")
     config.update(args)                      # mutates the caller's dict, like interface.py:297/484
     cfg = _AttrDict(config)
     if cfg.get("no_plms", False):
@@ -504,7 +517,7 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
         context = text_encoder.encode([meta["prompt"]] * bs)
         relations = prepare_relation_phrases(meta["prompt"], bs, max_rel, text_encoder, device=device)
     uc = text_encoder.encode([""]).repeat(bs, 1, 1)          # the reference encodes bs copies of "" (interface.py:496)
-    mask = z0 = None
+    mask = z0 = extra = None
     if meta.get("input_image") is not None:
         # inpainting (gligen_inference.py:393-407): encode the input image, regenerate inside the boxes (mask 0), keep the rest
         L = tuple(int(v) for v in starting_noise.shape[-2:])              # latent (h, w); the image is vae_factor times that per axis
@@ -518,9 +531,14 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
             img = load_input_image(ims, side, device)
         z0 = autoencoder.encode(img)
         mask = host.draw_masks_from_boxes(batch["boxes"], L).to(starting_noise.device)
+        if inpaint_model:
+            # an inpaint_mode checkpoint (gligen_inference.py:406-407): the first conv also reads [z0 * mask | mask]; the sampler keeps
+            # replacing the known region as well (:430 passes mask and x0 too).  A 4-channel model runs the latent blend alone.
+            extra = build_inpainting_extra(z0, mask)
     # S is a harness parameter: the reference hard-codes 50 (interface.py:507); ``args["steps"]`` overrides it
     samples = denoise(all_models, context, uc, relations, batch, starting_noise, meta.get("alpha_type"), cfg.guidance_scale,
-                      steps=int(args.get("steps", PLMS_STEPS)), mask=mask, x0=z0)   # steps per call: not sticky through the cached config
+                      steps=int(args.get("steps", PLMS_STEPS)), mask=mask, x0=z0,   # steps per call: not sticky through the cached config
+                      inpainting_extra_input=extra)
     return _postprocess(autoencoder.decode(samples))
 
 
@@ -598,6 +616,7 @@ def _unet_facade(packed, cfg, device, allow_missing_sd_conv=False):
     m.first_conv_restorable, m.allow_missing_sd_conv, m.first_conv_type = bool(packed.has_sd_conv), bool(allow_missing_sd_conv), "GLIGEN"
     m.grounding_tokenizer_input = grounding_input_for(cfg)
     m.fuser_scale, m.training, m._cond_key = 1.0, False, None
+    m.inpaint_mode = bool(getattr(cfg, "inpaint_mode", False))
     m.engine = UNetEngine(packed)
     m.strict = False
     return m
@@ -619,6 +638,9 @@ def load_all_models_sharded(ckpt, device, src=0, strict=None):
         model, autoencoder, text_encoder, diffusion, config = am
         if model.cfg.grounding != "text":
             raise NotImplementedError("the sharded entry is text-only: a text_image checkpoint runs through load_all_models / run_batch_images")
+        if model.cfg.inpaint_mode:
+            raise NotImplementedError("the sharded entry has no input image: an inpaint_mode checkpoint runs through load_all_models / "
+                                      "run_one_image / run_batch_images with meta['input_image']")
         if not isinstance(autoencoder, VAEDecoder):
             raise NotImplementedError("the sharded entry broadcasts the HIP VAE decoder's packed weights (unset GLIGEN_REFERENCE_VAE)")
         dcfg = dict(linear_start=diffusion.linear_start, linear_end=diffusion.linear_end, timesteps=diffusion.num_timesteps)

@@ -138,6 +138,9 @@ class UNetModel:
         self.in_channels = cfg.in_channels
         self.out_channels = cfg.out_channels
         self.model_channels = cfg.model_channels
+        if cfg.inpaint_mode and sd_first_conv is not None:
+            raise ValueError("an inpaint_mode model has no SD first conv: its 9-channel first conv is not restorable (openaimodel.py:296)")
+        self.inpaint_mode = cfg.inpaint_mode
         self.first_conv_restorable = sd_first_conv is not None
         self.allow_missing_sd_conv = allow_missing_sd_conv
         self.first_conv_type = "GLIGEN"
@@ -173,7 +176,13 @@ class UNetModel:
         """openaimodel.py:393-408.  The reference's non-restorable branch exists for inpainting models only; for this
         (non-inpainting) UNet a missing SD conv would silently change 35 of 50 steps, so it is an error unless the
         model was built with ``allow_missing_sd_conv=True`` (then the reference's message is printed)."""
-        if self.first_conv_restorable:
+        if getattr(self, "inpaint_mode", False):
+            # the reference's non-restorable branch (openaimodel.py:406-408): nothing is switched, nothing raises, every step keeps the
+            # checkpoint's 9-channel conv (the reference prints its message on every scale-0 step; here once per model)
+            if not getattr(self, "_told_not_restorable", False):
+                print("First conv layer is not restorable and skipped this process, probably because this is an inpainting model?")
+                self._told_not_restorable = True
+        elif self.first_conv_restorable:
             self.first_conv_type = "SD"
         elif getattr(self, "allow_missing_sd_conv", False):
             print("First conv layer is not restorable and skipped this process, probably because this is an inpainting model?")
@@ -210,13 +219,27 @@ class UNetModel:
                                          grounding["positive_embeddings"], hw)
         self._cond_key = key
 
+    def inpaint_extra_of(self, input: dict) -> Optional[torch.Tensor]:
+        """``input["inpainting_extra_input"]`` (openaimodel.py:436-439): required on an inpaint_mode model, ignored on every other (as the
+        reference ignores it)."""
+        if not getattr(self, "inpaint_mode", False):
+            return None
+        extra = input.get("inpainting_extra_input")
+        if extra is None:
+            raise ValueError("an inpaint_mode model needs input['inpainting_extra_input'] = cat([z0 * mask, mask], dim=1) "
+                             "(gligen_inference.py:406-407)")
+        return extra
+
     @torch.no_grad()
     def __call__(self, input: dict) -> torch.Tensor:
         """UNetModel.forward (openaimodel.py:413-459): one B-sized evaluation."""
         x = input["x"]
+        extra = self.inpaint_extra_of(input)
         g = self.grounding_of(input)
         H, W = (int(v) for v in x.shape[-2:])
         self.set_conditioning(input["context"], input["relations"], g, H if H == W else (H, W), key=None)
+        if extra is not None:
+            self.engine.set_inpaint_extra(extra)
         t = input["timesteps"]
         return self.engine.forward(x.to(self.device, torch.float32).contiguous(), t, self.fuser_scale, self.use_sd_conv, 1).clone()
 

@@ -561,6 +561,22 @@ def pack_latent(x: torch.Tensor, Cpad: int, reps: int, out: torch.Tensor, split:
     return out
 
 
+def pack_latent_extra(x: torch.Tensor, extra: torch.Tensor, Cpad: int, reps: int, out: torch.Tensor, split: bool = False):
+    """x fp32 [B, C, h, w] and extra fp32 [1|B, Ce, h, w] -> out fp16 [reps*B, h*w, Cpad] over cat([x, extra], dim=1) (the first-conv input of an
+    inpaint_mode UNet); ``split``: channels [hi | lo | hi] of the C + Ce concatenated ones."""
+    _req(x, F32, "x")
+    _req(extra, F32, "extra")
+    _req(out, F16, "out")
+    B, Cc, h, w = x.shape
+    if extra.dim() != 4 or tuple(extra.shape[-2:]) != (h, w) or extra.shape[0] not in (1, B):
+        raise ValueError(f"extra {tuple(extra.shape)} does not go with x {tuple(x.shape)}")
+    if out.numel() < reps * B * h * w * Cpad:
+        raise ValueError("out is too small")
+    check(_lib.lib().gl_pack_latent_extra(x.data_ptr(), extra.data_ptr(), B, extra.shape[0], Cc, extra.shape[1], h * w, Cpad, reps, int(split),
+                                          out.data_ptr(), _stream()), "gl_pack_latent_extra")
+    return out
+
+
 def vae_posterior(h: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, noise: torch.Tensor, scale: float, z: torch.Tensor,
                   mean: Optional[torch.Tensor] = None) -> torch.Tensor:
     """h fp32 [B, Cin, h, w] (Encoder.conv_out) -> z fp32 [B, E, h, w] = (mean + exp(clamp(logvar, -30, 20) / 2) * noise) * scale with

@@ -11,6 +11,8 @@ switch on every scale-0 step, step-0 double evaluation, Adams-Bashforth history 
   * the CFG combine and the x_prev update are two tiny fused HIP kernels on fp32 latents, evaluated
     in the reference's operation order (bit-identical to torch fp32 given the same eps);
   * the schedule tables are computed once per S;
+  * an inpaint_mode model's ``input["inpainting_extra_input"]`` (the same tensor for the cond and the uncond pass, plms.py:118-121) is handed
+    to the engine once per ``sample()``, not per step;
   * inpainting (``mask`` / ``x0``, plms.py:95-99): each step first replaces the known region,
     x = q_sample(x0, t) * mask + (1 - mask) * x, as one fused in-place fp32 HIP kernel (gl_latent_blend, bit-identical to
     the torch expression), with the q_sample noise drawn by ``torch.randn_like(x0)`` before the step's own draws.
@@ -80,6 +82,7 @@ class PLMSSampler(object):
         alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
 
         # ---- conditioning, once per image: [cond ; uncond] when CFG is active (plms.py:115-124)
+        extra = model.inpaint_extra_of(input)      # raises on an inpaint_mode model without the extra, before any kernel runs
         cfg_on = uc is not None and guidance_scale != 1
         g = model.grounding_of(input)
         f32 = lambda t: t.to(dev, torch.float32)
@@ -96,6 +99,8 @@ class PLMSSampler(object):
             grounding = {k: f32(v) for k, v in g.items() if torch.is_tensor(v)}
             reps = 1
         model.set_conditioning(ctx, rel, grounding, H if H == W else (H, W), key=None)      # (H, W): the rectangular entry and its shape check
+        if extra is not None:
+            eng.set_inpaint_extra(extra)
 
         ring = [eng.buf(f"plms.e{j}", tuple(x.shape), torch.float32) for j in range(4)]
         x_a = eng.buf("plms.x", tuple(x.shape), torch.float32)    # running latent (the engine copies it per forward)

@@ -61,8 +61,8 @@ def pack_conv3x3(w: torch.Tensor, cin_pad: int | None = None) -> torch.Tensor:
 
 
 def pack_first_conv(w: torch.Tensor, cin_pad: int) -> torch.Tensor:
-    """first conv [Cout, C, 3, 3] fp32 (C = 4 latent channels of 64 padded ones): input channels [Whi | Whi | Wlo | 0] for the latent packed as
-    [hi | lo | hi] (gl_pack_latent split): x.W = xhi.Whi + xlo.Whi + xhi.Wlo at no cost.  The first conv alone carries 7 % of the error of storing
+    """first conv [Cout, C, 3, 3] fp32 (C = 4 latent channels of 64 padded ones; C = 9 on an inpaint_mode model: 27 of 64): input channels
+    [Whi | Whi | Wlo | 0] for the latent packed as [hi | lo | hi] (gl_pack_latent / gl_pack_latent_extra split): x.W = xhi.Whi + xlo.Whi + xhi.Wlo at no cost.  The first conv alone carries 7 % of the error of storing
     the UNet's weights in fp16 (profiles/r4_weight_rounding_attribution.txt)."""
     w = w.float()
     if 3 * w.shape[1] > cin_pad:
@@ -169,6 +169,9 @@ def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_
     for k, shp in need.items():
         if tuple(sd[k].shape) != tuple(shp):
             raise ValueError(f"{k}: shape {tuple(sd[k].shape)} != expected {shp}")
+    if sd_first_conv is not None and getattr(cfg, "inpaint_mode", False):
+        # openaimodel.py:296: first_conv_restorable = False -- the 4-channel SD conv cannot take the 9-channel input
+        raise ValueError("an inpaint_mode model has no SD first conv (its first conv is not restorable, openaimodel.py:296)")
     P = PackedWeights(cfg, plan, device)
     W, S = P.w, P.s
     g = lambda k: _t(sd[k], device)
