@@ -71,6 +71,15 @@ __device__ __forceinline__ void st16(void* p, uint4 v) { *reinterpret_cast<uint4
 
 static inline int gl_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Host-side constants shared by the UNet and the VAE engines (ops.py keeps the Python copy)
+constexpr int64_t GL_WS_BYTES = 96ll << 20;       // split-K workspace: fp32 partial tiles
+// chunks per sample of the GroupNorm statistics pass: min(64, HW / 4) up to 4096 pixels, min(512, HW / 512) above
+static inline int gn_nchunk(int HW) {
+    if (HW <= 4096) { const int c = HW / 4; return c < 1 ? 1 : (c > 64 ? 64 : c); }
+    const int c = HW / 512;
+    return c > 512 ? 512 : c;
+}
+
 #define GL_CHECK_LAUNCH()                                   \
     do {                                                    \
         hipError_t e__ = hipGetLastError();                 \

@@ -27,7 +27,6 @@ namespace {
 
 constexpr int CIN_PAD = 64;              // the 4-channel latent is zero-padded to one 64-channel K block
 constexpr int64_t ALIGN = 256;
-constexpr int64_t WS_BYTES = 96ll << 20; // split-K fp32 partial tiles
 #define g_fuse_merge_ln gl_opt(25)  // default 1;                 // A/B knob (gl_set_option 25): rela_merge also writes LayerNorm(norm2) of its rows
 #define g_fuse_vt gl_opt(21)  // default 1;                       // A/B knob (gl_set_option 21): V^T written by the QKV GEMM epilogue (1) or by gl_transpose_v (0)
 #define g_force_fuser gl_opt(20)  // default 0;                   // test knob (gl_set_option 20): execute the fuser even at scale 0 (zero gates)
@@ -57,6 +56,16 @@ struct WInfo {
     int64_t off, bytes;
     int dtype, ndim;
     int64_t shape[4];
+};
+// everything a captured launch sequence depends on besides the pool addresses and the option generation (which drop every graph)
+struct GraphKey {
+    int Bn, lat_h, lat_w, R, Lc;
+    bool fuser_on, sd_conv;
+    int reps;
+    bool uniform_t;             // one timestep for the whole batch: with reps == 2 the shared cond / uncond prefix
+    int rel_slots;
+    auto tie() const { return std::tie(Bn, lat_h, lat_w, R, Lc, fuser_on, sd_conv, reps, uniform_t, rel_slots); }
+    bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
 };
 
 __global__ void f32_to_f16_kernel(const float* __restrict__ x, half_t* __restrict__ y, size_t n) {
@@ -157,7 +166,7 @@ struct gl_engine {
     bool extra_set = false;
     int extra_bs = 0;
     // graphs
-    std::map<std::tuple<int, int, int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
+    std::map<GraphKey, hipGraphExec_t> graphs;
     float fuser_scale_cur = -1e30f;
     std::vector<float> gate_host;      // the [n_st][4] array last computed
     float* gate_pin[2] = {nullptr, nullptr};           // pinned double buffer the async upload reads from
@@ -399,11 +408,6 @@ inline int vt_ld(int Nk) {
 }
 // the per-resolution conditioning buffers (cond.rects.* / nvalid.* / poison.*) are named by rows x columns: 64x96, 96x64 and 64x64 are three levels
 inline std::string level_tag(int h, int w) { return std::to_string(h) + "x" + std::to_string(w); }
-inline int gn_nchunk(int HW) {
-    if (HW <= 4096) { int c = HW / 4; if (c > 64) c = 64; return c < 1 ? 1 : c; }
-    int c = HW / 512;
-    return c > 512 ? 512 : c;
-}
 
 #define CK(expr)                                     \
     do {                                             \
@@ -422,118 +426,146 @@ struct Run {
     void* ws;
     int launches = 0;
 
+    // Launch operands.  The helpers below take a short positional core that says what the launch is; everything optional is a member of
+    // a small options aggregate, named at the call site with designated initialisers (in declaration order).
+    struct Act { const void* p = nullptr; int ld = 0; bool hilo = false; };       // activation rows; hilo: every row is [hi | lo] (ld >= 2 x width)
+    struct Rows { const void* p = nullptr; int ld = 0; bool f32 = false; };       // fp32-or-fp16 rows: a residual, a normalisation's source
+    template <class T>
+    struct MatT { T* p; int64_t bs; int ld; T* lo = nullptr; };                   // an attention matrix: batch stride, row stride, lo half of a split one
+    using Mat = MatT<const half_t>; using MatOut = MatT<half_t>;
+    struct VtMat { const half_t* p; int ld; const half_t* lo = nullptr; };        // V^T of an attention ([B * H * d] rows of ld keys)
     // the transposed V tail of a fused QKV projection (gl_gemm_args.vt ...; vt_lo with a [hi | lo] output)
     struct VtTail { void* vt; void* vt_lo; int col0, rows, d, ld, H; };
-    int gemm(const void* a, int lda, const std::string& w, int M, void* out, int ldc, int out_mode = GL_OUT_F16_ROWMAJOR,
-             const std::string& bias = "", int epi = GL_EPI_BIAS, const void* res = nullptr, int ldres = 0, int res_f32 = 0,
-             const float* gate = nullptr, void* out2 = nullptr, int ldc2 = 0, const void* a2 = nullptr, int lda2 = 0, int ksplit = 0,
-             bool hilo_a = false, bool wsplit = false, const VtTail* tail = nullptr) {
-        const WInfo* wi = e->wi(w);
+
+    struct GemmOpt {
+        bool bias = true;               // false: a projection without one (q, kv, qkv); true: the layer's p + ".b" must exist
+        int out_mode = GL_OUT_F16_ROWMAJOR, epi = GL_EPI_BIAS;
+        Rows res{};                     // GL_EPI_RES / GL_EPI_GATE_RES
+        const float* gate = nullptr;
+        void* out2 = nullptr; int ldc2 = 0;     // fp16 copy of an fp32 output
+        Act a2{}; int ksplit = 0;               // second A source from K column ksplit on (a folded th.cat)
+        bool wsplit = false;            // an add_lin_split matrix (rows [Whi | Wlo] in every table)
+        const VtTail* tail = nullptr;
+    };
+    // out = epi(a . W(p + ".w")^T + W(p + ".b"))
+    int gemm(Act a, const std::string& p, int M, void* out, int ldc, const GemmOpt& o) {
+        const WInfo* wi = e->wi(p + ".w");
         if (!wi) return GL_ERR_BAD_ARG;
         gl_gemm_args g{};
-        g.a = a; g.lda = lda; g.a2 = a2; g.lda2 = lda2; g.ksplit = ksplit;
-        g.w = e->W(w);
-        g.bias = bias.empty() ? nullptr : e->Wf(bias);
+        g.a = a.p; g.lda = a.ld; g.a2 = o.a2.p; g.lda2 = o.a2.ld; g.ksplit = o.ksplit;
+        g.w = e->W(p + ".w"); g.bias = o.bias ? e->Wf(p + ".b") : nullptr;
+        if (o.bias && !g.bias) return GL_ERR_BAD_ARG;
         g.M = M; g.N = (int)wi->shape[0]; g.K = (int)wi->shape[1];
         const bool strict = g_strict != 0 && e->cfg.split_weights;
-        if (wsplit || e->cfg.split_weights) {           // weight rows [Whi | Wlo] (add_lin_split; every matrix of a split_weights table): the true K is half the stored row
+        if (o.wsplit || e->cfg.split_weights) {         // weight rows [Whi | Wlo] (add_lin_split; every matrix of a split_weights table): the true K is half the stored row
             const int Kc = g.K / 2;
-            g.ldw = g.K; g.K = Kc;
-            if (hilo_a) {       // x.W = xhi.Whi + xlo.Whi (+ xhi.Wlo: third K segment, A from the second source = the hi half again)
+            g.ldw = g.K; g.K = Kc;                      // (fp16 rows: Whi alone, exactly what a compact handle computes)
+            if (a.hilo) {       // x.W = xhi.Whi + xlo.Whi (+ xhi.Wlo: third K segment, A from the second source = the hi half again)
                 g.kwrap = Kc; g.K = 2 * Kc;
                 // default mode: the third pass belongs to the add_lin_split matrices alone (the three kinds of 1x1 conv, key 45) -- on a
                 // split_weights handle every other matrix is read for its Whi half, exactly what a compact handle computes
-                const bool third = strict ? (g_strict_w3 != 0) : (wsplit && g_w3 > 0 && M > (g_w3 < 1024 ? 1024 : g_w3));
+                const bool third = strict ? (g_strict_w3 != 0) : (o.wsplit && g_w3 > 0 && M > (g_w3 < 1024 ? 1024 : g_w3));
                 if (third) {
-                    if (a2 != nullptr) return GL_ERR_BAD_ARG;      // the third pass needs the second-source slot: a two-source A cannot take it
-                    g.K = 3 * Kc; g.a2 = a; g.lda2 = lda; g.ksplit = 2 * Kc;
+                    if (o.a2.p != nullptr) return GL_ERR_BAD_ARG;  // the third pass needs the second-source slot: a two-source A cannot take it
+                    g.K = 3 * Kc; g.a2 = a.p; g.lda2 = a.ld; g.ksplit = 2 * Kc;
                 }
             }
-        } else if (hilo_a) {    // A = [hi | lo] of the activation, both halves against the same weight (gl_gemm_args.kwrap)
+        } else if (a.hilo) {    // A = [hi | lo] of the activation, both halves against the same weight (gl_gemm_args.kwrap)
             g.kwrap = g.K; g.ldw = g.K; g.K = 2 * g.K;
         }
-        g.epi = epi; g.out_mode = out_mode; g.out = out; g.ldc = ldc;
-        g.res = res; g.ldres = ldres; g.res_f32 = res_f32; g.gate = gate;
-        g.out2 = out2; g.ldc2 = ldc2;
-        if (tail) {
-            g.vt = tail->vt; g.vt_lo = tail->vt_lo; g.vt_col0 = tail->col0; g.vt_rows = tail->rows; g.vt_d = tail->d; g.vt_ld = tail->ld; g.vt_H = tail->H;
+        g.epi = o.epi; g.out_mode = o.out_mode; g.out = out; g.ldc = ldc;
+        g.res = o.res.p; g.ldres = o.res.ld; g.res_f32 = o.res.f32; g.gate = o.gate;
+        g.out2 = o.out2; g.ldc2 = o.ldc2;
+        if (o.tail) {
+            const VtTail& t = *o.tail;
+            g.vt = t.vt; g.vt_lo = t.vt_lo; g.vt_col0 = t.col0; g.vt_rows = t.rows; g.vt_d = t.d; g.vt_ld = t.ld; g.vt_H = t.H;
         }
-        g.workspace = ws; g.workspace_bytes = WS_BYTES;
+        g.workspace = ws; g.workspace_bytes = GL_WS_BYTES;
         ++launches;
         return gl_gemm(&g, st);
     }
-    int gemm_vt(const void* a, int lda, const std::string& w, int M, void* out, int ldc, void* vt, int vt_col0, int vt_rows, int vt_d, int vt_ld,
-                int vt_H) {
-        const WInfo* wi = e->wi(w);
+    int gemm(Act a, const std::string& p, int M, void* out, int ldc) { return gemm(a, p, M, out, ldc, GemmOpt{}); }
+
+    struct RowBias { const void* p = nullptr; int ld = 0, rows_per_sample = 0; };   // GL_EPI_ROWBIAS: one bias row per sample (the emb_layers output)
+    struct ConvOpt {
+        int stride = 1, ups = 0, epi = GL_EPI_BIAS;     // ups: nearest-2x upsample folded into the gather
+        Rows res{};
+        RowBias rowbias{};
+        void* out2 = nullptr;           // fp16 copy of an fp32 output
+        int nchw_hw = 0;                // GL_OUT_F32_NCHW: pixels per sample
+    };
+    // 3x3 conv of layer p (weights p + ".w", p + ".b") over in = [B, H, W] pixel rows of in.ld channels ([hi | lo] halves of in.ld / 2 each when in.hilo)
+    int conv(Act in, const std::string& p, int B, int Hin, int Win, void* out, int out_mode, const ConvOpt& o) {
+        const WInfo* wi = e->wi(p + ".w");
         if (!wi) return GL_ERR_BAD_ARG;
-        gl_gemm_args g{};
-        g.a = a; g.lda = lda; g.w = e->W(w);
-        g.M = M; g.N = (int)wi->shape[0]; g.K = (int)wi->shape[1];
-        if (e->cfg.split_weights) { g.ldw = g.K; g.K /= 2; }      // rows [Whi | Wlo]: the default mode reads Whi
-        g.epi = GL_EPI_BIAS; g.out_mode = GL_OUT_F16_ROWMAJOR; g.out = out; g.ldc = ldc;
-        g.vt = vt; g.vt_col0 = vt_col0; g.vt_rows = vt_rows; g.vt_d = vt_d; g.vt_ld = vt_ld; g.vt_H = vt_H;
-        g.workspace = ws; g.workspace_bytes = WS_BYTES;
-        ++launches;
-        return gl_gemm(&g, st);
-    }
-    int conv(const void* in, const std::string& w, const std::string& bias, int B, int Hin, int Win, int Cin, int stride, int ups,
-             void* out, int out_mode, int epi = GL_EPI_BIAS, const void* res = nullptr, int ldres = 0, int res_f32 = 0,
-             const void* rowbias = nullptr, int ld_rowbias = 0, int rows_per_sample = 0, void* out2 = nullptr, int nchw_hw = 0,
-             bool hilo_in = false) {
-        const WInfo* wi = e->wi(w);
-        if (!wi) return GL_ERR_BAD_ARG;
+        const int Cin = in.hilo ? in.ld / 2 : in.ld;
         gl_conv_args a{};
         // weight rows [Whi | Wlo] in a split_weights table (not the first conv, which is split inside its padded channels)
         a.w_split = wi->shape[1] == 18 * (int64_t)Cin;
         // strict: the input pixels are [hi | lo] rows (2 Cin channels); third pass hi.Wlo with key 51
-        a.in_split = hilo_in ? ((a.w_split && g_strict_w3 != 0) ? 3 : 2) : 0;
-        a.in = in; a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = Cin;
-        a.Hout = ups ? 2 * Hin : (Hin + 2 - 3) / stride + 1;
-        a.Wout = ups ? 2 * Win : (Win + 2 - 3) / stride + 1;
-        a.stride = stride; a.upsample2x = ups;
-        a.g.w = e->W(w); a.g.bias = e->Wf(bias); a.g.N = (int)wi->shape[0];
-        a.g.epi = epi; a.g.out_mode = out_mode; a.g.out = out; a.g.ldc = a.g.N; a.g.hw = nchw_hw;
-        a.g.res = res; a.g.ldres = ldres; a.g.res_f32 = res_f32;
-        a.g.rowbias = rowbias; a.g.ld_rowbias = ld_rowbias; a.g.rows_per_sample = rows_per_sample;
-        a.g.rowbias_f32 = rowbias != nullptr && (g_precise != 0 || g_strict != 0);      // precise mode: the emb_layers output stays fp32
-        a.g.out2 = out2; a.g.ldc2 = a.g.N;
-        a.g.workspace = ws; a.g.workspace_bytes = WS_BYTES;
+        a.in_split = in.hilo ? ((a.w_split && g_strict_w3 != 0) ? 3 : 2) : 0;
+        a.in = in.p; a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = Cin;
+        a.Hout = o.ups ? 2 * Hin : (Hin + 2 - 3) / o.stride + 1;
+        a.Wout = o.ups ? 2 * Win : (Win + 2 - 3) / o.stride + 1;
+        a.stride = o.stride; a.upsample2x = o.ups;
+        a.g.w = e->W(p + ".w"); a.g.bias = e->Wf(p + ".b"); a.g.N = (int)wi->shape[0];
+        a.g.epi = o.epi; a.g.out_mode = out_mode; a.g.out = out; a.g.ldc = a.g.N; a.g.hw = o.nchw_hw;
+        a.g.res = o.res.p; a.g.ldres = o.res.ld; a.g.res_f32 = o.res.f32;
+        a.g.rowbias = o.rowbias.p; a.g.ld_rowbias = o.rowbias.ld; a.g.rows_per_sample = o.rowbias.rows_per_sample;
+        a.g.rowbias_f32 = o.rowbias.p != nullptr && (g_precise != 0 || g_strict != 0);      // precise mode: the emb_layers output stays fp32
+        a.g.out2 = o.out2; a.g.ldc2 = a.g.N;
+        a.g.workspace = ws; a.g.workspace_bytes = GL_WS_BYTES;
         ++launches;
         return gl_conv3x3(&a, st);
     }
-    // y_lo: rows written as [hi | lo] (ldy >= 2 C): the split-fp16 operand of the projection that follows (strict mode)
-    int ln(const void* x, int ldx, int x_f32, half_t* y, int ldy, const std::string& p, int B, int rows_in, int rows_out, int row_off,
-           int C, float* stats = nullptr, const void* x2 = nullptr, int rows2 = 0, int x2_f32 = 0, bool y_lo = false) {
+
+    enum LnFlags { LN_X_F32 = 1, LN_X2_F32 = 4, LN_Y_HILO = 8 };     // the flag word of gl_layernorm
+    struct LnOpt {
+        int rows_out = 0;               // rows per sample of y when it has more than x (the [x ; x2 ; pad] rows of the fuser); 0 = rows
+        float* stats = nullptr;         // also writes the per-row (mean, rstd)
+        Rows x2{}; int rows2 = 0;       // rows2 further rows per sample, normalised behind x's
+        bool y_lo = false;              // y rows written as [hi | lo] (ldy >= 2 C): the split-fp16 operand of the projection that follows (strict mode)
+    };
+    // LayerNorm p over the e->Bn samples of x ([rows, C] each) into y.  ln, gn and attn take the batch from the handle: a half-batch section
+    // (the shared cond / uncond prefix) must hold a BnScope around its calls, or they run the full batch
+    int ln(Rows x, half_t* y, int ldy, const std::string& p, int rows, int C, const LnOpt& o) {
+        const int flags = (x.f32 ? LN_X_F32 : 0) | (o.x2.f32 ? LN_X2_F32 : 0) | (o.y_lo ? LN_Y_HILO : 0);
         ++launches;
-        return gl_layernorm(x, ldx, x_f32 | (x2_f32 ? 4 : 0) | (y_lo ? 8 : 0), y, ldy, e->Wf(p + ".g"), e->Wf(p + ".b"), B, rows_in, rows_out, row_off, C,
-                            1e-5f, stats, x2, C, rows2, st);
+        return gl_layernorm(x.p, x.ld, flags, y, ldy, e->Wf(p + ".g"), e->Wf(p + ".b"), e->Bn, rows, o.rows_out ? o.rows_out : rows, 0, C, 1e-5f, o.stats,
+                            o.x2.p, C, o.rows2, st);
     }
+    int ln(Rows x, half_t* y, int ldy, const std::string& p, int rows, int C) { return ln(x, y, ldy, p, rows, C, LnOpt{}); }
     // fp32 rows -> fp16 [hi | lo] rows (strict mode: stream tensors entering a down / up conv, conditioning tensors)
     int split(const float* x, int64_t rows, int C, half_t* y) {
         ++launches;
         return gl_split_f32(x, C, rows, C, y, 2 * C, st);
     }
-    // x_f32: the sources are fp32 stream tensors; out_lo / raw: the split-fp16 side outputs of gl_groupnorm_ex
-    int gn(const void* x1, int C1, const void* x2, int C2, int x_f32, int B, int HW, const std::string& p, float eps, int silu, half_t* out,
-           int ldo = 0, half_t* out_lo = nullptr, half_t* raw = nullptr, int ldraw = 0) {
-        const int nchunk = gn_nchunk(HW);
+    struct GnOpt {
+        const void* x2 = nullptr; int C2 = 0;   // second source of C2 channels, same element type as x (a folded th.cat)
+        int ldo = 0;
+        half_t* out_lo = nullptr;               // out_lo / raw: the split-fp16 side outputs of gl_groupnorm_ex
+        half_t* raw = nullptr; int ldraw = 0;
+    };
+    // GroupNorm p (+ SiLU) over the e->Bn samples of x ([HW, x.ld] each; x.f32: an fp32 stream tensor)
+    int gn(Rows x, int HW, const std::string& p, float eps, int silu, half_t* out, const GnOpt& o) {
+        const int B = e->Bn, nchunk = gn_nchunk(HW);
         float* partial = e->f32("gn.partial", (size_t)B * nchunk * 64);
         CKP(partial);
-        launches += gl_groupnorm_launches_ex(C1 + C2, HW, x_f32);
+        launches += gl_groupnorm_launches_ex(x.ld + o.C2, HW, x.f32);
         gl_gn_args a{};
-        a.x1 = x1; a.C1 = C1; a.x2 = x2; a.C2 = C2; a.x_f32 = x_f32; a.B = B; a.HW = HW;
+        a.x1 = x.p; a.C1 = x.ld; a.x2 = o.x2; a.C2 = o.C2; a.x_f32 = x.f32; a.B = B; a.HW = HW;
         a.gamma = e->Wf(p + ".g"); a.beta = e->Wf(p + ".b"); a.eps = eps; a.silu = silu;
-        a.out = out; a.ldo = ldo; a.out_lo = out_lo; a.raw = raw; a.ldraw = ldraw;
+        a.out = out; a.ldo = o.ldo; a.out_lo = o.out_lo; a.raw = o.raw; a.ldraw = o.ldraw;
         a.partial = partial; a.nchunk = nchunk;
         return gl_groupnorm_ex(&a, st);
     }
-    int attn(const half_t* q, int64_t qb, int ldq, const half_t* k, int64_t kb, int ldk, const half_t* vt, int ldvt, half_t* out,
-             int64_t ob, int ldo, int B, int H, int d, int Nq, int Nk, const half_t* q_lo = nullptr, const half_t* k_lo = nullptr,
-             const half_t* vt_lo = nullptr, half_t* out_lo = nullptr) {
+    int gn(Rows x, int HW, const std::string& p, float eps, int silu, half_t* out) { return gn(x, HW, p, eps, silu, out, GnOpt{}); }
+    // attention of the e->Bn samples' cfg.num_heads heads: q [Nq, H d] against k [Nk, H d] and V^T, split-fp16 where the lo halves are given
+    int attn(Mat q, Mat k, VtMat vt, MatOut out, int d, int Nq, int Nk) {
         gl_attn_args a{};
-        a.q_lo = q_lo; a.k_lo = k_lo; a.vt_lo = vt_lo; a.out_lo = out_lo;
-        a.q = q; a.q_bstride = qb; a.ldq = ldq; a.k = k; a.k_bstride = kb; a.ldk = ldk; a.vt = vt; a.ldvt = ldvt;
-        a.out = out; a.o_bstride = ob; a.ldo = ldo; a.B = B; a.H = H; a.d = d; a.Nq = Nq; a.Nk = Nk;
+        a.q_lo = q.lo; a.k_lo = k.lo; a.vt_lo = vt.lo; a.out_lo = out.lo;
+        a.q = q.p; a.q_bstride = q.bs; a.ldq = q.ld; a.k = k.p; a.k_bstride = k.bs; a.ldk = k.ld; a.vt = vt.p; a.ldvt = vt.ld;
+        a.out = out.p; a.o_bstride = out.bs; a.ldo = out.ld; a.B = e->Bn; a.H = e->cfg.num_heads; a.d = d; a.Nq = Nq; a.Nk = Nk;
         a.scale = 1.0f / sqrtf((float)d);
         a.q_prescaled = 1;      // weights.py folds d^-1/2 * log2(e) into every q projection
         ++launches;
@@ -619,18 +651,16 @@ int self_attention(Run& r, const half_t* src, int rows_per_b, int Nq, int Nk, in
             // the V third leaves the projection's epilogue directly as the two V^T operands (hi, lo) of the split attention (ABI 15); only the
             // 8-wave kernel implements that tail (GL_ERR_UNSUPPORTED otherwise: the transposes below)
             const Run::VtTail tail{vt, vtl, 2 * C, rows_per_b, d, ldvt, H};
-            rc = r.gemm(src, 2 * C, wp + ".qkv.w", Bn * rows_per_b, qkv, 6 * C, GL_OUT_F16_HILO, "", GL_EPI_BIAS, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0,
-                        true, false, &tail);
+            rc = r.gemm({src, 2 * C, true}, wp + ".qkv", Bn * rows_per_b, qkv, 6 * C, {.bias = false, .out_mode = GL_OUT_F16_HILO, .tail = &tail});
             if (rc != 0 && rc != GL_ERR_UNSUPPORTED) return rc;
             if (rc != 0) --r.launches;
         }
         if (rc != 0) {
-            CK(r.gemm(src, 2 * C, wp + ".qkv.w", Bn * rows_per_b, qkv, 6 * C, GL_OUT_F16_HILO, "", GL_EPI_BIAS, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0,
-                      true));
+            CK(r.gemm({src, 2 * C, true}, wp + ".qkv", Bn * rows_per_b, qkv, 6 * C, {.bias = false, .out_mode = GL_OUT_F16_HILO}));
             CK(r.transpose_v(qkv + 2 * C, bs, 6 * C, vt, ldvt, Bn, H, d, Nk));
             CK(r.transpose_v(qkv + 5 * C, bs, 6 * C, vtl, ldvt, Bn, H, d, Nk));
         }
-        CK(r.attn(qkv, bs, 6 * C, qkv + C, bs, 6 * C, vt, ldvt, att, (int64_t)Nq * 2 * C, 2 * C, Bn, H, d, Nq, Nk, qkv + 3 * C, qkv + 4 * C, vtl, att + C));
+        CK(r.attn({qkv, bs, 6 * C, qkv + 3 * C}, {qkv + C, bs, 6 * C, qkv + 4 * C}, {vt, ldvt, vtl}, {att, (int64_t)Nq * 2 * C, 2 * C, att + C}, d, Nq, Nk));
         *out = att;
         return 0;
     }
@@ -639,17 +669,18 @@ int self_attention(Run& r, const half_t* src, int rows_per_b, int Nq, int Nk, in
     half_t* vt = e->h16(tag + ".vt", (size_t)Bn * H * d * ldvt);
     half_t* att = e->h16(tag + ".att", (size_t)Bn * Nq * C);
     CKP(qkv); CKP(vt); CKP(att);
+    const int64_t bs = (int64_t)rows_per_b * 3 * C;
     // fused QKV projection; its V third is written directly as the attention kernel's V^T operand by the GEMM epilogue
     // when the V columns start on an epilogue pass of every tile shape (true for all widths of this UNet), else by the
     // separate transpose kernel
     if (g_fuse_vt && (C % 32) == 0) {
-        CK(r.gemm_vt(src, C, wp + ".qkv.w", Bn * rows_per_b, qkv, 3 * C, vt, 2 * C, rows_per_b, d, ldvt, H));
+        const Run::VtTail tail{vt, nullptr, 2 * C, rows_per_b, d, ldvt, H};
+        CK(r.gemm({src, C}, wp + ".qkv", Bn * rows_per_b, qkv, 3 * C, {.bias = false, .tail = &tail}));
     } else {
-        CK(r.gemm(src, C, wp + ".qkv.w", Bn * rows_per_b, qkv, 3 * C));
-        CK(r.transpose_v(qkv + 2 * C, (int64_t)rows_per_b * 3 * C, 3 * C, vt, ldvt, Bn, H, d, Nk));
+        CK(r.gemm({src, C}, wp + ".qkv", Bn * rows_per_b, qkv, 3 * C, {.bias = false}));
+        CK(r.transpose_v(qkv + 2 * C, bs, 3 * C, vt, ldvt, Bn, H, d, Nk));
     }
-    CK(r.attn(qkv, (int64_t)rows_per_b * 3 * C, 3 * C, qkv + C, (int64_t)rows_per_b * 3 * C, 3 * C, vt, ldvt, att, (int64_t)Nq * C, C, Bn, H, d,
-              Nq, Nk));
+    CK(r.attn({qkv, bs, 3 * C}, {qkv + C, bs, 3 * C}, {vt, ldvt}, {att, (int64_t)Nq * C, C}, d, Nq, Nk));
     *out = att;
     return 0;
 }
@@ -660,9 +691,8 @@ int feed_forward(Run& r, const half_t* xn, const float* res, const std::string& 
         // strict: xn rows are [hi | lo]; the GEGLU rows leave the first projection as [hi (4 C) | lo (4 C)]
         half_t* hg = r.e->h16("ff.h", (size_t)M * 8 * C);
         CKP(hg);
-        CK(r.gemm(xn, 2 * C, p + ".ff1.w", M, hg, 8 * C, GL_OUT_F16_HILO, p + ".ff1.b", GL_EPI_GEGLU, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0, true));
-        return r.gemm(hg, 8 * C, p + ".ff2.w", M, out, ldc, out_mode, p + ".ff2.b", gate ? GL_EPI_GATE_RES : GL_EPI_RES, res, C, 1, gate, nullptr, 0, nullptr, 0,
-                      0, true);
+        CK(r.gemm({xn, 2 * C, true}, p + ".ff1", M, hg, 8 * C, {.out_mode = GL_OUT_F16_HILO, .epi = GL_EPI_GEGLU}));
+        return r.gemm({hg, 8 * C, true}, p + ".ff2", M, out, ldc, {.out_mode = out_mode, .epi = gate ? GL_EPI_GATE_RES : GL_EPI_RES, .res = {res, C, true}, .gate = gate});
     }
     if (gl_ff_fused_applicable(C, M) && !r.e->cfg.split_weights) {
         // narrow / long level: the whole FeedForward in one launch, the [M, 4C] GEGLU intermediate never leaves the CU
@@ -680,8 +710,8 @@ int feed_forward(Run& r, const half_t* xn, const float* res, const std::string& 
     }
     half_t* hg = r.e->h16("ff.h", (size_t)M * 4 * C);
     CKP(hg);
-    CK(r.gemm(xn, C, p + ".ff1.w", M, hg, 4 * C, GL_OUT_F16_ROWMAJOR, p + ".ff1.b", GL_EPI_GEGLU));
-    return r.gemm(hg, 4 * C, p + ".ff2.w", M, out, ldc, out_mode, p + ".ff2.b", gate ? GL_EPI_GATE_RES : GL_EPI_RES, res, C, 1, gate);
+    CK(r.gemm({xn, C}, p + ".ff1", M, hg, 4 * C, {.epi = GL_EPI_GEGLU}));
+    return r.gemm({hg, 4 * C}, p + ".ff2", M, out, ldc, {.out_mode = out_mode, .epi = gate ? GL_EPI_GATE_RES : GL_EPI_RES, .res = {res, C, true}, .gate = gate});
 }
 
 // ResBlock._forward (openaimodel.py:211-231); skip = the popped skip-stack tensor of an output block (th.cat folded in).
@@ -703,30 +733,28 @@ int res_block(Run& r, const LayerD& l, Stream2 h, const Stream2* skip, int skip_
     half_t* split = nullptr;
     if (precise) {
         if (has_skip_conv) { split = e->h16("rb.split", (size_t)M * 2 * l.cin); CKP(split); }
-        CK(r.gn(h.f, c1, skip ? skip->f : nullptr, skip_c, 1, Bn, HW, p + ".in_layers.0", 1e-5f, 1, t, strict ? 2 * l.cin : 0, strict ? t + l.cin : nullptr,
-                split, 2 * l.cin));
+        CK(r.gn({h.f, c1, true}, HW, p + ".in_layers.0", 1e-5f, 1, t,
+                {.x2 = skip ? skip->f : nullptr, .C2 = skip_c, .ldo = strict ? 2 * l.cin : 0, .out_lo = strict ? t + l.cin : nullptr, .raw = split, .ldraw = 2 * l.cin}));
     } else {
         CKP(h.h);
-        CK(r.gn(h.h, c1, skip ? skip->h : nullptr, skip_c, 0, Bn, HW, p + ".in_layers.0", 1e-5f, 1, t));
+        CK(r.gn({h.h, c1, false}, HW, p + ".in_layers.0", 1e-5f, 1, t, {.x2 = skip ? skip->h : nullptr, .C2 = skip_c}));
     }
     const int off = e->emb_off[p];
     void* h1 = h1f ? (void*)e->f32("rb.h1f", (size_t)M * l.cout) : (void*)e->h16("rb.h1", (size_t)M * l.cout);
     CKP(h1);
-    CK(r.conv(t, p + ".in_layers.2.w", p + ".in_layers.2.b", Bn, sh, sw, l.cin, 1, 0, h1, h1f ? GL_OUT_F32_ROWMAJOR : GL_OUT_F16_ROWMAJOR,
-              GL_EPI_ROWBIAS, nullptr, 0, 0,
-              precise ? (const void*)(reinterpret_cast<const float*>(emb_out) + off) : (const void*)(reinterpret_cast<const half_t*>(emb_out) + off),
-              e->emb_total, HW, nullptr, 0, strict));
-    CK(r.gn(h1, l.cout, nullptr, 0, h1f ? 1 : 0, Bn, HW, p + ".out_layers.0", 1e-5f, 1, t2, strict ? 2 * l.cout : 0, strict ? t2 + l.cout : nullptr));
+    const void* emb = precise ? (const void*)(reinterpret_cast<const float*>(emb_out) + off) : (const void*)(reinterpret_cast<const half_t*>(emb_out) + off);
+    CK(r.conv({t, strict ? 2 * l.cin : l.cin, strict}, p + ".in_layers.2", Bn, sh, sw, h1, h1f ? GL_OUT_F32_ROWMAJOR : GL_OUT_F16_ROWMAJOR,
+              {.epi = GL_EPI_ROWBIAS, .rowbias = {emb, e->emb_total, HW}}));
+    CK(r.gn({h1, l.cout, h1f}, HW, p + ".out_layers.0", 1e-5f, 1, t2, {.ldo = strict ? 2 * l.cout : 0, .out_lo = strict ? t2 + l.cout : nullptr}));
     const float* sk = h.f;
     if (has_skip_conv) {
         float* skb = e->f32("rb.skip.f32", (size_t)M * l.cout);
         CKP(skb);
         if (precise) {
-            CK(r.gemm(split, 2 * l.cin, p + ".skip_connection.w", M, skb, l.cout, GL_OUT_F32_ROWMAJOR, p + ".skip_connection.b", GL_EPI_BIAS, nullptr, 0, 0,
-                      nullptr, nullptr, 0, nullptr, 0, 0, true, true));
-        } else {
-            CK(r.gemm(h.h, c1, p + ".skip_connection.w", M, skb, l.cout, GL_OUT_F32_ROWMAJOR, p + ".skip_connection.b", GL_EPI_BIAS, nullptr, 0, 0, nullptr,
-                      nullptr, 0, skip ? skip->h : nullptr, skip_c, skip ? c1 : 0, false, true));
+            CK(r.gemm({split, 2 * l.cin, true}, p + ".skip_connection", M, skb, l.cout, {.out_mode = GL_OUT_F32_ROWMAJOR, .wsplit = true}));
+        } else {                // th.cat([h, skip]) folded in: the K columns from c1 on read the skip tensor
+            CK(r.gemm({h.h, c1}, p + ".skip_connection", M, skb, l.cout,
+                      {.out_mode = GL_OUT_F32_ROWMAJOR, .a2 = {skip ? skip->h : nullptr, skip_c}, .ksplit = skip ? c1 : 0, .wsplit = true}));
         }
         sk = skb;
     } else if (skip) {
@@ -736,8 +764,8 @@ int res_block(Run& r, const LayerD& l, Stream2 h, const Stream2* skip, int skip_
     out->h = need_h ? e->h16(tag, (size_t)M * l.cout) : nullptr;
     CKP(out->f);
     if (need_h) CKP(out->h);
-    return r.conv(t2, p + ".out_layers.3.w", p + ".out_layers.3.b", Bn, sh, sw, l.cout, 1, 0, out->f, GL_OUT_F32_ROWMAJOR, GL_EPI_RES, sk, l.cout, 1,
-                  nullptr, 0, 0, out->h, 0, strict);
+    return r.conv({t2, strict ? 2 * l.cout : l.cout, strict}, p + ".out_layers.3", Bn, sh, sw, out->f, GL_OUT_F32_ROWMAJOR,
+                  {.epi = GL_EPI_RES, .res = {sk, l.cout, true}, .out2 = out->h});
 }
 
 // SpatialTransformer.forward + BasicTransformerBlock._forward (attention.py:436-446, :394-402)
@@ -768,21 +796,19 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, in
         BnScope half(e, B1);              // self_attention reads e->Bn
         if (precise) {
             // Normalize on the fp32 stream, rows written as [hi | lo]; proj_in takes both halves against the same weight
-            CK(r.gn(xin.f, C, nullptr, 0, 1, B1, N, p + ".norm", 1e-6f, 0, g0, 2 * C, g0 + C));
-            CK(r.gemm(g0, 2 * C, p + ".proj_in.w", M1, x, C, GL_OUT_F32_ROWMAJOR, p + ".proj_in.b", GL_EPI_BIAS, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0,
-                      0, true, true));
+            CK(r.gn({xin.f, C, true}, N, p + ".norm", 1e-6f, 0, g0, {.ldo = 2 * C, .out_lo = g0 + C}));
+            CK(r.gemm({g0, 2 * C, true}, p + ".proj_in", M1, x, C, {.out_mode = GL_OUT_F32_ROWMAJOR, .wsplit = true}));
         } else {
             CKP(xin.h);
-            CK(r.gn(xin.h, C, nullptr, 0, 0, B1, N, p + ".norm", 1e-6f, 0, g0));
-            CK(r.gemm(g0, C, p + ".proj_in.w", M1, x, C, GL_OUT_F32_ROWMAJOR, p + ".proj_in.b", GL_EPI_BIAS, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0,
-                      false, true));
+            CK(r.gn({xin.h, C, false}, N, p + ".norm", 1e-6f, 0, g0));
+            CK(r.gemm({g0, C}, p + ".proj_in", M1, x, C, {.out_mode = GL_OUT_F32_ROWMAJOR, .wsplit = true}));
         }
         // --- attn1 (attention.py:395)
         half_t* att1 = nullptr;
-        CK(r.ln(x, C, 1, lnb, lnw, t + ".norm1", B1, N, N, 0, C, nullptr, nullptr, 0, 0, strict));
+        CK(r.ln({x, C, true}, lnb, lnw, t + ".norm1", N, C, {.y_lo = strict}));
         CK(self_attention(r, lnb, N, N, N, C, d, t + ".attn1", "st.sa", &att1));
         float* y = nxt(x);
-        CK(r.gemm(att1, lnw, t + ".attn1.o.w", M1, y, C, GL_OUT_F32_ROWMAJOR, t + ".attn1.o.b", GL_EPI_RES, x, C, 1, nullptr, nullptr, 0, nullptr, 0, 0, strict));
+        CK(r.gemm({att1, lnw, strict}, t + ".attn1.o", M1, y, C, {.out_mode = GL_OUT_F32_ROWMAJOR, .epi = GL_EPI_RES, .res = {x, C, true}}));
         x = y;
         if (share_half) {
             // the uncond half: identical up to here (same latent, t, weights; attention.py:395 is the last op before the conditioning enters)
@@ -802,18 +828,16 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, in
         const int rows = N + ((ng + 7) & ~7);
         half_t* cat = e->h16("st.cat", (size_t)Bn * rows * lnw);
         CKP(cat);
-        if (strict) {
-            CK(r.ln(x, C, 1, cat, lnw, f + ".norm1", Bn, N, rows, 0, C, nullptr, e->f32("hoist.objs32s." + sl, (size_t)Bn * ng * C), ng, 1, true));
-        } else if (precise) {
-            CK(r.ln(x, C, 1, cat, C, f + ".norm1", Bn, N, rows, 0, C, nullptr, e->f32("hoist.objs32." + sl, (size_t)Bn * ng * C), ng, 1));
-        } else {
-            CK(r.ln(x, C, 1, cat, C, f + ".norm1", Bn, N, rows, 0, C, nullptr, e->h16("hoist.objs." + sl, (size_t)Bn * ng * C), ng));
-        }
+        // the hoisted fuser.linear(objs): fp32 from split-fp16 operands (strict), fp32 (precise) or fp16 rows
+        const void* objs = strict    ? (const void*)e->f32("hoist.objs32s." + sl, (size_t)Bn * ng * C)
+                           : precise ? (const void*)e->f32("hoist.objs32." + sl, (size_t)Bn * ng * C)
+                                     : (const void*)e->h16("hoist.objs." + sl, (size_t)Bn * ng * C);
+        CK(r.ln({x, C, true}, cat, lnw, f + ".norm1", N, C, {.rows_out = rows, .x2 = {objs, C, precise}, .rows2 = ng, .y_lo = strict}));
         CK(self_attention(r, cat, rows, N, N + ng, C, d, f + ".attn", "st.fa", &att));
         float* y = nxt(x);
-        CK(r.gemm(att, lnw, f + ".attn.o.w", M, y, C, GL_OUT_F32_ROWMAJOR, f + ".attn.o.b", GL_EPI_GATE_RES, x, C, 1, gates + 0, nullptr, 0, nullptr, 0, 0, strict));
+        CK(r.gemm({att, lnw, strict}, f + ".attn.o", M, y, C, {.out_mode = GL_OUT_F32_ROWMAJOR, .epi = GL_EPI_GATE_RES, .res = {x, C, true}, .gate = gates + 0}));
         x = y;
-        CK(r.ln(x, C, 1, lnb, lnw, f + ".norm2", Bn, N, N, 0, C, nullptr, nullptr, 0, 0, strict));
+        CK(r.ln({x, C, true}, lnb, lnw, f + ".norm2", N, C, {.y_lo = strict}));
         y = nxt(x);
         CK(feed_forward(r, lnb, x, f + ".ff", M, C, y, GL_OUT_F32_ROWMAJOR, gates + 1));
         x = y;
@@ -845,20 +869,20 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, in
             CK(gl_rela_pool_ln3(x, stats, e->Wf(rf + ".norm3.g"), e->Wf(rf + ".norm3.b"), Bn, sh, sw, C, rects, nvalid, poison, mo, ms, feat,
                                 e->Wf(rf + ".norm1.g"), e->Wf(rf + ".norm1.b"), fn, r.st));
         } else {
-            CK(r.ln(x, C, 1, hid, C, rf + ".norm3", Bn, N, N, 0, C, stats));
+            CK(r.ln({x, C, true}, hid, C, rf + ".norm3", N, C, {.stats = stats}));
             ++r.launches;
             CK(gl_rela_pool(hid, Bn, sh, sw, C, rects, nvalid, poison, mo, ms, feat, e->Wf(rf + ".norm1.g"), e->Wf(rf + ".norm1.b"), fn, r.st));
         }
-        CK(r.gemm(fn, C, rf + ".attn.q.w", Mo, q, C));
+        CK(r.gemm({fn, C}, rf + ".attn.q", Mo, q, C, {.bias = false}));
         const half_t* kv = e->h16("hoist.kvrel." + sl, (size_t)Bn * R * 2 * C);
         const int ldvt = vt_ld(R);
         const half_t* vtr = e->h16("hoist.vtrel." + sl, (size_t)Bn * H * d * ldvt);
         CKP(kv); CKP(vtr);
-        CK(r.attn(q, (int64_t)ms * C, C, kv, (int64_t)R * 2 * C, 2 * C, vtr, ldvt, ar, (int64_t)ms * C, C, Bn, H, d, ms, R));
-        CK(r.gemm(ar, C, rf + ".attn.o.w", Mo, f1, C, GL_OUT_F16_ROWMAJOR, rf + ".attn.o.b", GL_EPI_GATE_RES, feat, C, 0, gates + 2));
-        CK(r.ln(f1, C, 0, fn, C, rf + ".norm2", Bn, ms, ms, 0, C));
-        CK(r.gemm(fn, C, rf + ".ff.ff1.w", Mo, hg, 4 * C, GL_OUT_F16_ROWMAJOR, rf + ".ff.ff1.b", GL_EPI_GEGLU));
-        CK(r.gemm(hg, 4 * C, rf + ".ff.ff2.w", Mo, f2, C, GL_OUT_F16_ROWMAJOR, rf + ".ff.ff2.b", GL_EPI_GATE_RES, f1, C, 0, gates + 3));
+        CK(r.attn({q, (int64_t)ms * C, C}, {kv, (int64_t)R * 2 * C, 2 * C}, {vtr, ldvt}, {ar, (int64_t)ms * C, C}, d, ms, R));
+        CK(r.gemm({ar, C}, rf + ".attn.o", Mo, f1, C, {.epi = GL_EPI_GATE_RES, .res = {feat, C, false}, .gate = gates + 2}));
+        CK(r.ln({f1, C, false}, fn, C, rf + ".norm2", ms, C));
+        CK(r.gemm({fn, C}, rf + ".ff.ff1", Mo, hg, 4 * C, {.epi = GL_EPI_GEGLU}));
+        CK(r.gemm({hg, 4 * C}, rf + ".ff.ff2", Mo, f2, C, {.epi = GL_EPI_GATE_RES, .res = {f1, C, false}, .gate = gates + 3}));
         float* y = nxt(x);
         ++r.launches;
         // ... and LayerNorm(norm2) of the merged rows in the same launch (the rows attn2's q projection reads)
@@ -880,19 +904,19 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, in
             const half_t* kv = e->h16("hoist.kvctxs." + sl, (size_t)Bn * Lc * 4 * C);
             const half_t* vtc = e->h16("hoist.vtctxs." + sl, (size_t)2 * Bn * H * d * ldvt);
             CKP(kv); CKP(vtc);
-            CK(r.ln(x, C, 1, lnb, lnw, t + ".norm2", Bn, N, N, 0, C, nullptr, nullptr, 0, 0, true));
-            CK(r.gemm(lnb, lnw, t + ".attn2.q.w", M, q2, lnw, GL_OUT_F16_HILO, "", GL_EPI_BIAS, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0, true));
-            CK(r.attn(q2, (int64_t)N * lnw, lnw, kv, (int64_t)Lc * 4 * C, 4 * C, vtc, ldvt, a2, (int64_t)N * lnw, lnw, Bn, H, d, N, Lc, q2 + C, kv + 2 * C,
-                      vtc + (size_t)Bn * H * d * ldvt, a2 + C));
-            CK(r.gemm(a2, lnw, t + ".attn2.o.w", M, y, C, GL_OUT_F32_ROWMAJOR, t + ".attn2.o.b", GL_EPI_RES, x, C, 1, nullptr, nullptr, 0, nullptr, 0, 0, true));
+            CK(r.ln({x, C, true}, lnb, lnw, t + ".norm2", N, C, {.y_lo = true}));
+            CK(r.gemm({lnb, lnw, true}, t + ".attn2.q", M, q2, lnw, {.bias = false, .out_mode = GL_OUT_F16_HILO}));
+            CK(r.attn({q2, (int64_t)N * lnw, lnw, q2 + C}, {kv, (int64_t)Lc * 4 * C, 4 * C, kv + 2 * C}, {vtc, ldvt, vtc + (size_t)Bn * H * d * ldvt},
+                      {a2, (int64_t)N * lnw, lnw, a2 + C}, d, N, Lc));
+            CK(r.gemm({a2, lnw, true}, t + ".attn2.o", M, y, C, {.out_mode = GL_OUT_F32_ROWMAJOR, .epi = GL_EPI_RES, .res = {x, C, true}}));
         } else {
             const half_t* kv = e->h16("hoist.kvctx." + sl, (size_t)Bn * Lc * 2 * C);
             const half_t* vtc = e->h16("hoist.vtctx." + sl, (size_t)Bn * H * d * ldvt);
             CKP(kv); CKP(vtc);
-            if (!ln2_done) CK(r.ln(x, C, 1, lnb, C, t + ".norm2", Bn, N, N, 0, C));
-            CK(r.gemm(lnb, C, t + ".attn2.q.w", M, q2, C));
-            CK(r.attn(q2, (int64_t)N * C, C, kv, (int64_t)Lc * 2 * C, 2 * C, vtc, ldvt, a2, (int64_t)N * C, C, Bn, H, d, N, Lc));
-            CK(r.gemm(a2, C, t + ".attn2.o.w", M, y, C, GL_OUT_F32_ROWMAJOR, t + ".attn2.o.b", GL_EPI_RES, x, C, 1));
+            if (!ln2_done) CK(r.ln({x, C, true}, lnb, C, t + ".norm2", N, C));
+            CK(r.gemm({lnb, C}, t + ".attn2.q", M, q2, C, {.bias = false}));
+            CK(r.attn({q2, (int64_t)N * C, C}, {kv, (int64_t)Lc * 2 * C, 2 * C}, {vtc, ldvt}, {a2, (int64_t)N * C, C}, d, N, Lc));
+            CK(r.gemm({a2, C}, t + ".attn2.o", M, y, C, {.out_mode = GL_OUT_F32_ROWMAJOR, .epi = GL_EPI_RES, .res = {x, C, true}}));
         }
         x = y;
     }
@@ -900,15 +924,15 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, in
     // (precise: as [hi | lo] rows, proj_out takes both halves against the same weight)
     half_t* x16 = e->h16("st.x6", (size_t)M * C * (precise ? 2 : 1));
     CKP(x16);
-    CK(r.ln(x, C, 1, lnb, lnw, t + ".norm3", Bn, N, N, 0, C, nullptr, nullptr, 0, 0, strict));
+    CK(r.ln({x, C, true}, lnb, lnw, t + ".norm3", N, C, {.y_lo = strict}));
     CK(feed_forward(r, lnb, x, t + ".ff", M, C, x16, precise ? GL_OUT_F16_HILO : GL_OUT_F16_ROWMAJOR, nullptr));
     // --- proj_out + residual (attention.py:444-446)
     out->f = e->f32(tag + ".f32", (size_t)M * C);
     out->h = need_h ? e->h16(tag, (size_t)M * C) : nullptr;
     CKP(out->f);
     if (need_h) CKP(out->h);
-    return r.gemm(x16, precise ? 2 * C : C, p + ".proj_out.w", M, out->f, C, GL_OUT_F32_ROWMAJOR, p + ".proj_out.b", GL_EPI_RES, xin.f, C, 1, nullptr, out->h,
-                  C, nullptr, 0, 0, precise, true);
+    return r.gemm({x16, precise ? 2 * C : C, precise}, p + ".proj_out", M, out->f, C,
+                  {.out_mode = GL_OUT_F32_ROWMAJOR, .epi = GL_EPI_RES, .res = {xin.f, C, true}, .out2 = out->h, .ldc2 = C, .wsplit = true});
 }
 
 int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uniform_t, hipStream_t st, int* n_launches) {
@@ -920,7 +944,7 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
                        !e->input_blocks[1].layers.empty() && e->input_blocks[1].layers[0].kind == RES;
     const int B0 = share ? Bn / 2 : Bn;
     int sh = e->lat_h, sw = e->lat_w;
-    Run r{e, st, e->buf("splitk.ws", WS_BYTES)};
+    Run r{e, st, e->buf("splitk.ws", GL_WS_BYTES)};
     CKP(r.ws);
     const float* x_lat = e->f32("in.xlat", (size_t)(Bn / reps) * cfg.in_channels * sh * sw);
     const float* t_buf = e->f32("in.t", Bn);
@@ -947,10 +971,9 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
         CK(gl_timestep_embedding(t_buf, Bn, mc, te, st));
     }
     const int tom = strict ? GL_OUT_F16_HILO : GL_OUT_F16_ROWMAJOR;
-    CK(r.gemm(te, mc * tw, "time_embed.0.w", Bn, e1, 4 * mc * tw, tom, "time_embed.0.b", GL_EPI_SILU, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0, strict));
-    CK(r.gemm(e1, 4 * mc * tw, "time_embed.2.w", Bn, e2, 4 * mc * tw, tom, "time_embed.2.b", GL_EPI_SILU, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0, strict));
-    CK(r.gemm(e2, 4 * mc * tw, "emb_all.w", Bn, emb_out, e->emb_total, precise ? GL_OUT_F32_ROWMAJOR : GL_OUT_F16_ROWMAJOR, "emb_all.b", GL_EPI_BIAS, nullptr, 0, 0,
-              nullptr, nullptr, 0, nullptr, 0, 0, strict));
+    CK(r.gemm({te, mc * tw, strict}, "time_embed.0", Bn, e1, 4 * mc * tw, {.out_mode = tom, .epi = GL_EPI_SILU}));
+    CK(r.gemm({e1, 4 * mc * tw, strict}, "time_embed.2", Bn, e2, 4 * mc * tw, {.out_mode = tom, .epi = GL_EPI_SILU}));
+    CK(r.gemm({e2, 4 * mc * tw, strict}, "emb_all", Bn, emb_out, e->emb_total, {.out_mode = precise ? GL_OUT_F32_ROWMAJOR : GL_OUT_F16_ROWMAJOR}));
     // first conv on the zero-padded NHWC latent (openaimodel.py:299, :393-405)
     half_t* xin = e->h16("in.x", (size_t)Bn * sh * sw * CIN_PAD);
     CKP(xin);
@@ -965,7 +988,6 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
     } else {
         CK(gl_pack_latent(x_lat, Bn / reps, cfg.in_channels, sh * sw, CIN_PAD, share ? 1 : reps, g_in_split && 3 * cfg.in_channels <= CIN_PAD, xin, st));
     }
-    const std::string fc = sd_conv ? "sd_first_conv" : "input_blocks.0.0";
     // fp16 copies of stream tensors: only where a down / up conv consumes the tensor (precise mode: every GroupNorm and 1x1 conv
     // reads the fp32 stream), or everywhere in the round-3 fp16-copy mode
     auto first_kind = [&](const BlockD* b) { return b && !b->layers.empty() ? b->layers[0].kind : -1; };
@@ -974,7 +996,7 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
     h.f = e->f32("skip.0.f32", (size_t)Bn * sh * sw * mc);
     h.h = wants_h(first_kind(e->input_blocks.size() > 1 ? &e->input_blocks[1] : nullptr)) ? e->h16("skip.0", (size_t)Bn * sh * sw * mc) : nullptr;
     CKP(h.f);
-    CK(r.conv(xin, fc + ".w", fc + ".b", B0, sh, sw, CIN_PAD, 1, 0, h.f, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, nullptr, 0, 0, nullptr, 0, 0, h.h));
+    CK(r.conv({xin, CIN_PAD}, sd_conv ? "sd_first_conv" : "input_blocks.0.0", B0, sh, sw, h.f, GL_OUT_F32_ROWMAJOR, {.out2 = h.h}));
     if (share) {            // skip-stack entry 0 is consumed at full batch by the last output block
         CK(r.dup_rows(h.f, (size_t)B0 * sh * sw * mc * 4));
         if (h.h) CK(r.dup_rows(h.h, (size_t)B0 * sh * sw * mc * 2));
@@ -1008,37 +1030,21 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
             } else if (l.kind == ST) {
                 CK(spatial_transformer(r, l, st_idx++, h, sh, sw, fuser_on, tag, need_h, &o, half_pending));
                 half_pending = false;       // the transformer duplicated its input and its own stream after attn1
-            } else if (l.kind == DOWN) {
-                const int oh = sh / 2, ow = sw / 2;
+            } else if (l.kind == DOWN || l.kind == UP) {
+                const bool up = l.kind == UP;
+                const int oh = up ? sh * 2 : sh / 2, ow = up ? sw * 2 : sw / 2;
                 o.f = e->f32(tag + ".f32", (size_t)Bn * oh * ow * l.cout);
                 o.h = need_h ? e->h16(tag, (size_t)Bn * oh * ow * l.cout) : nullptr;
                 CKP(o.f); CKP(h.h);
                 if (need_h) CKP(o.h);
-                const half_t* cin_ = h.h;
+                Run::Act in{h.h, l.cin};
                 if (strict) {          // the stream tensor itself as [hi | lo] pixel rows
                     half_t* hs = e->h16("conv.split", (size_t)Bn * sh * sw * 2 * l.cin);
                     CKP(hs);
                     CK(r.split(h.f, (int64_t)Bn * sh * sw, l.cin, hs));
-                    cin_ = hs;
+                    in = {hs, 2 * l.cin, true};
                 }
-                CK(r.conv(cin_, l.prefix + ".w", l.prefix + ".b", Bn, sh, sw, l.cin, 2, 0, o.f, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, nullptr, 0, 0, nullptr,
-                          0, 0, o.h, 0, strict));
-                sh = oh; sw = ow;
-            } else if (l.kind == UP) {
-                const int oh = sh * 2, ow = sw * 2;
-                o.f = e->f32(tag + ".f32", (size_t)Bn * oh * ow * l.cout);
-                o.h = need_h ? e->h16(tag, (size_t)Bn * oh * ow * l.cout) : nullptr;
-                CKP(o.f); CKP(h.h);
-                if (need_h) CKP(o.h);
-                const half_t* cin_ = h.h;
-                if (strict) {
-                    half_t* hs = e->h16("conv.split", (size_t)Bn * sh * sw * 2 * l.cin);
-                    CKP(hs);
-                    CK(r.split(h.f, (int64_t)Bn * sh * sw, l.cin, hs));
-                    cin_ = hs;
-                }
-                CK(r.conv(cin_, l.prefix + ".w", l.prefix + ".b", Bn, sh, sw, l.cin, 1, 1, o.f, GL_OUT_F32_ROWMAJOR, GL_EPI_BIAS, nullptr, 0, 0, nullptr,
-                          0, 0, o.h, 0, strict));
+                CK(r.conv(in, l.prefix, Bn, sh, sw, o.f, GL_OUT_F32_ROWMAJOR, {.stride = up ? 1 : 2, .ups = up, .out2 = o.h}));
                 sh = oh; sw = ow;
             } else {
                 return GL_ERR_BAD_ARG;
@@ -1069,16 +1075,10 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
     const int ocl = e->out_channels_last;
     half_t* g = e->h16("fin.gn", (size_t)Bn * sh * sw * ocl * (strict ? 2 : 1));
     CKP(g);
-    if (strict) {
-        CK(r.gn(h.f, ocl, nullptr, 0, 1, Bn, sh * sw, "out.0", 1e-5f, 1, g, 2 * ocl, g + ocl));
-    } else if (precise) {
-        CK(r.gn(h.f, e->out_channels_last, nullptr, 0, 1, Bn, sh * sw, "out.0", 1e-5f, 1, g));
-    } else {
-        CKP(h.h);
-        CK(r.gn(h.h, e->out_channels_last, nullptr, 0, 0, Bn, sh * sw, "out.0", 1e-5f, 1, g));
-    }
-    CK(r.conv(g, "out.2.w", "out.2.b", Bn, sh, sw, e->out_channels_last, 1, 0, eps, GL_OUT_F32_NCHW, GL_EPI_BIAS, nullptr, 0, 0, nullptr, 0, 0, nullptr,
-              sh * sw, strict));
+    if (!precise) CKP(h.h);
+    CK(r.gn({precise ? (const void*)h.f : (const void*)h.h, ocl, precise}, sh * sw, "out.0", 1e-5f, 1, g,
+            {.ldo = strict ? 2 * ocl : 0, .out_lo = strict ? g + ocl : nullptr}));
+    CK(r.conv({g, strict ? 2 * ocl : ocl, strict}, "out.2", Bn, sh, sw, eps, GL_OUT_F32_NCHW, {.nchw_hw = sh * sw}));
     if (n_launches) *n_launches = r.launches;
     return 0;
 }
@@ -1181,7 +1181,7 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
         image_emb = e->f32("cond.in.imgemb", (size_t)Bn * mo * cfg.pos_in_dim);
         CKP(text_masks); CKP(image_masks); CKP(image_emb);
     }
-    Run r{e, st, e->buf("splitk.ws", WS_BYTES)};
+    Run r{e, st, e->buf("splitk.ws", GL_WS_BYTES)};
     CKP(r.ws);
     gl_opts strict_opts = *(tl_gl_opts ? tl_gl_opts : &g_gl_opts);
     strict_opts.v[50] = 1;
@@ -1207,7 +1207,7 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
     }
     CK(r.split(pin32, (int64_t)(nch * rows), pin_dim, pins));
     auto lin = [&](const half_t* a, int k, const std::string& w, void* out, int ldc, int out_mode, int epi, size_t m) {
-        return r.gemm(a, 2 * k, w + ".w", (int)m, out, ldc, out_mode, w + ".b", epi, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0, true);
+        return r.gemm({a, 2 * k, true}, w, (int)m, out, ldc, {.out_mode = out_mode, .epi = epi});
     };
     for (int c = 0; c < nch; ++c) {                  // chain c on rows [c * rows, (c + 1) * rows) of every buffer
         const std::string pw = !ti ? "position_net.linears" : (c == 0 ? "position_net.linears_text" : "position_net.linears_image");
@@ -1237,7 +1237,7 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
         const int ldc_ = vt_ld(Lc);
         half_t* vt = e->h16("hoist.vtctxs." + sl, (size_t)2 * Bn * H * d * ldc_);
         CKP(kv); CKP(vt);
-        CK(r.gemm(ctxs, 2 * ctx, t + ".attn2.kv.w", Bn * Lc, kv, 4 * C, GL_OUT_F16_HILO, "", GL_EPI_BIAS, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, 0, true));
+        CK(r.gemm({ctxs, 2 * ctx, true}, t + ".attn2.kv", Bn * Lc, kv, 4 * C, {.bias = false, .out_mode = GL_OUT_F16_HILO}));
         CK(r.transpose_v(kv + C, (int64_t)Lc * 4 * C, 4 * C, vt, ldc_, Bn, H, d, Lc));
         CK(r.transpose_v(kv + 3 * C, (int64_t)Lc * 4 * C, 4 * C, vt + (size_t)Bn * H * d * ldc_, ldc_, Bn, H, d, Lc));
     }
@@ -1264,7 +1264,7 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     if (h != e->lat_h || w != e->lat_w) e->extra_set = false;       // the inpainting extra was sized for the previous latent shape
     e->pool_changed = false;
     e->Bn = Bn; e->Lc = Lc; e->R = R; e->lat_h = h; e->lat_w = w;
-    Run r{e, st, e->buf("splitk.ws", WS_BYTES)};
+    Run r{e, st, e->buf("splitk.ws", GL_WS_BYTES)};
     CKP(r.ws);
     // --- grounding tokens: PositionNet (text_grounding_net.py:26-43)
     const int pin_dim = cfg.pos_in_dim + 8 * cfg.fourier_freqs;
@@ -1288,9 +1288,9 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     for (int c = 0; c < nch; ++c) {
         const std::string pw = !ti ? "position_net.linears" : (c == 0 ? "position_net.linears_text" : "position_net.linears_image");
         const size_t o = c * crow;
-        CK(r.gemm(pin + o * pin_dim, pin_dim, pw + ".0.w", Bn * mo, h1 + o * 512, 512, GL_OUT_F16_ROWMAJOR, pw + ".0.b", GL_EPI_SILU));
-        CK(r.gemm(h1 + o * 512, 512, pw + ".2.w", Bn * mo, h2 + o * 512, 512, GL_OUT_F16_ROWMAJOR, pw + ".2.b", GL_EPI_SILU));
-        CK(r.gemm(h2 + o * 512, 512, pw + ".4.w", Bn * mo, objs + o * D, D, GL_OUT_F16_ROWMAJOR, pw + ".4.b"));
+        CK(r.gemm({pin + o * pin_dim, pin_dim}, pw + ".0", Bn * mo, h1 + o * 512, 512, {.epi = GL_EPI_SILU}));
+        CK(r.gemm({h1 + o * 512, 512}, pw + ".2", Bn * mo, h2 + o * 512, 512, {.epi = GL_EPI_SILU}));
+        CK(r.gemm({h2 + o * 512, 512}, pw + ".4", Bn * mo, objs + o * D, D));
     }
     if (ti) {               // objs = cat([objs_text, objs_image], dim=1): sample b's ng token rows are [text (mo) | image (mo)]
         half_t* cat = e->h16("pn.objs.cat", (size_t)Bn * ng * D);
@@ -1312,21 +1312,21 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
         half_t* o = e->h16("hoist.objs." + sl, (size_t)Bn * ng * C);
         float* o32 = e->f32("hoist.objs32." + sl, (size_t)Bn * ng * C);
         CKP(o); CKP(o32);
-        CK(r.gemm(objs, D, t + ".fuser.linear.w", Bn * ng, o, C, GL_OUT_F16_ROWMAJOR, t + ".fuser.linear.b"));
-        CK(r.gemm(objs, D, t + ".fuser.linear.w", Bn * ng, o32, C, GL_OUT_F32_ROWMAJOR, t + ".fuser.linear.b"));
+        CK(r.gemm({objs, D}, t + ".fuser.linear", Bn * ng, o, C));
+        CK(r.gemm({objs, D}, t + ".fuser.linear", Bn * ng, o32, C, {.out_mode = GL_OUT_F32_ROWMAJOR}));
         // attn2 K/V of the text context (attention.py:124-125)
         half_t* kv = e->h16("hoist.kvctx." + sl, (size_t)Bn * Lc * 2 * C);
         const int ldc_ = vt_ld(Lc);
         half_t* vt = e->h16("hoist.vtctx." + sl, (size_t)Bn * H * d * ldc_);
         CKP(kv); CKP(vt);
-        CK(r.gemm(ctx16, ctx, t + ".attn2.kv.w", Bn * Lc, kv, 2 * C));
+        CK(r.gemm({ctx16, ctx}, t + ".attn2.kv", Bn * Lc, kv, 2 * C, {.bias = false}));
         CK(r.transpose_v(kv + C, (int64_t)Lc * 2 * C, 2 * C, vt, ldc_, Bn, H, d, Lc));
         // rela_fuse K/V of the relation tokens (attention.py:348-349)
         half_t* kvr = e->h16("hoist.kvrel." + sl, (size_t)Bn * R * 2 * C);
         const int ldr_ = vt_ld(R);
         half_t* vtr = e->h16("hoist.vtrel." + sl, (size_t)Bn * H * d * ldr_);
         CKP(kvr); CKP(vtr);
-        CK(r.gemm(rel16, ctx, t + ".rela_fuse.attn.kv.w", Bn * R, kvr, 2 * C));
+        CK(r.gemm({rel16, ctx}, t + ".rela_fuse.attn.kv", Bn * R, kvr, 2 * C, {.bias = false}));
         CK(r.transpose_v(kvr + C, (int64_t)R * 2 * C, 2 * C, vtr, ldr_, Bn, H, d, R));
     }
     // --- strict mode's hoists: lazily (strict_hoists above).  A split_weights handle keeps the inputs they are computed from; they run now only
@@ -1502,7 +1502,7 @@ extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev,
         e->ovr_epoch = e->ovr.epoch;
     }
     const bool uniform_t = t_dev == nullptr;
-    const auto key = std::make_tuple(Bn, e->lat_h, e->lat_w, e->R, e->Lc, (int)fuser_on, (int)(sd_conv != 0), (int)reps + (uniform_t ? 16 : 0), e->rel_slots);
+    const GraphKey key{Bn, e->lat_h, e->lat_w, e->R, e->Lc, fuser_on, sd_conv != 0, reps, uniform_t, e->rel_slots};
     auto it = e->graphs.find(key);
     if (use_graph && it == e->graphs.end()) {
         // warm-up run allocates every pooled buffer, then the same launch sequence is captured

@@ -110,12 +110,6 @@ void plan_resnet(gl_vae* v, const std::string& p, int cin, int cout) {
 // pool tags of per-resolution buffers carry rows x columns: 8x12 and 12x8 are different levels
 std::string lt(int h, int w) { return std::to_string(h) + "x" + std::to_string(w); }
 
-int gn_nchunk(int HW) {
-    if (HW <= 4096) { int c = HW / 4; return c < 1 ? 1 : (c > 64 ? 64 : c); }
-    const int c = HW / 512;
-    return c > 512 ? 512 : c;
-}
-
 struct VRun {
     gl_vae* v;
     hipStream_t st;
@@ -156,9 +150,9 @@ int v_conv(VRun& r, const half_t* x, int sh, int sw, int cin, const std::string&
     a.g.ldc = out_mode == GL_OUT_F32_NCHW ? 0 : cout;
     a.g.hw = out_mode == GL_OUT_F32_NCHW ? a.Hout * a.Wout : 0;
     a.g.res = res; a.g.ldres = cout;
-    float* ws = v->f32("ws", (size_t)(96ll << 20) / 4);
+    float* ws = v->f32("ws", (size_t)GL_WS_BYTES / 4);
     VCKP(ws);
-    a.g.workspace = ws; a.g.workspace_bytes = 96ll << 20;
+    a.g.workspace = ws; a.g.workspace_bytes = GL_WS_BYTES;
     VCK(down ? gl_conv3x3_pad01(&a, r.st) : gl_conv3x3(&a, r.st));
     r.count();
     return 0;
@@ -170,9 +164,9 @@ int v_gemm(VRun& r, const half_t* a_, int lda, const half_t* w, const float* bia
     memset(&g, 0, sizeof(g));
     g.a = a_; g.lda = lda; g.w = w; g.bias = bias; g.M = M; g.N = N; g.K = K; g.epi = epi;
     g.out_mode = GL_OUT_F16_ROWMAJOR; g.out = out; g.ldc = ldc; g.res = res; g.ldres = N;
-    float* ws = r.v->f32("ws", (size_t)(96ll << 20) / 4);
+    float* ws = r.v->f32("ws", (size_t)GL_WS_BYTES / 4);
     VCKP(ws);
-    g.workspace = ws; g.workspace_bytes = 96ll << 20;
+    g.workspace = ws; g.workspace_bytes = GL_WS_BYTES;
     VCK(gl_gemm(&g, r.st));
     r.count();
     return 0;
