@@ -393,6 +393,12 @@ typedef struct gl_unet_config {          /* UNetModel.__init__ arguments (openai
                                     ([Whi | Whi | Wlo | 0] over 3 * 9 = 27 of the 64 padded channels), the table has no sd_first_conv.* entries (the conv is
                                     not restorable, :296), and every forward needs gl_set_inpaint_extra first.  gl_create rejects
                                     2 * in_channels + 1 > 64. */
+    int32_t no_relation;         /* additive to ABI 15.  0 = every transformer block carries the rela_fuse chain (attention.py:398; a zeroed field keeps the
+                                    earlier behaviour).  1 = the upstream GLIGEN block (attention_original.py:312-316: attn1 -> fuser -> attn2 -> ff), what
+                                    every public GLIGEN checkpoint was trained on: the weight table has no *.rela_fuse.* entries, the conditioning entries
+                                    accept relations == NULL and ignore R (no relation K/V hoists, no box rectangles), and a forward launches nothing of
+                                    the relation chain -- the fuser's output (attn1's at fuser scale 0) goes straight to LayerNorm(norm2) -> attn2.  Any
+                                    other value: gl_create returns GL_ERR_UNSUPPORTED.  Combines with grounding, inpaint_mode and split_weights. */
 } gl_unet_config;
 
 typedef struct gl_engine gl_engine;      /* opaque */
@@ -418,7 +424,9 @@ int gl_load_weights(gl_engine* e, const void* packed, int64_t bytes, int32_t has
  * (PositionNet tokens text_grounding_net.py:26-43, fuser.linear attention.py:228, attn2 / rela_fuse K,V projections
  * attention.py:124-125,348-349, integer box rectangles attention.py:321-346).  fp32 inputs: context [Bn, Lc, ctx],
  * relations [Bn, R, ctx], boxes [Bn, max_objs, 4], masks [Bn, max_objs], pos_emb [Bn, max_objs, pos_in_dim]; null
- * grounding = zeros (text_layout_tokinzer_input.py:47-62).  hw = latent side. */
+ * grounding = zeros (text_layout_tokinzer_input.py:47-62).  hw = latent side.  On a handle created with no_relation = 1 this entry,
+ * _hw and _ti accept relations == NULL and ignore relations and R; on every other handle relations == NULL or R <= 0 is
+ * GL_ERR_BAD_ARG. */
 int gl_set_conditioning(gl_engine* e, const float* context, const float* relations, const float* boxes,
                         const float* masks, const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t hw,
                         void* stream);

@@ -105,6 +105,7 @@ class UNetConfigC(C.Structure):
         ("split_weights", i32),
         ("grounding", i32),
         ("inpaint_mode", i32),
+        ("no_relation", i32),
     ]
 
 
@@ -307,6 +308,7 @@ def unet_config_c(cfg) -> UNetConfigC:
     c.split_weights = int(bool(getattr(cfg, "split_weights", False)))
     c.grounding = GROUNDING_IDS[getattr(cfg, "grounding", "text")]
     c.inpaint_mode = int(bool(getattr(cfg, "inpaint_mode", False)))
+    c.no_relation = int(not getattr(cfg, "relation", True))
     return c
 
 

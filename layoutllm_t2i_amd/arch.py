@@ -41,6 +41,10 @@ class UNetConfig:
     # GLIGEN's inpainting checkpoints (checkpoint_inpainting_text*.pth; openaimodel.py:293-299, :436-439): the first conv also reads the masked
     # image latent and the mask, cat([x, z0 * mask, mask]) -- in_channels stays the LATENT's channel count (gl_unet_config.inpaint_mode)
     inpaint_mode: bool = False
+    # the transformer block: True = LayoutLLM-T2I's (attention.py:394-402, attn1 -> fuser -> rela_fuse -> attn2 -> ff); False = upstream GLIGEN's
+    # (attention_original.py:312-316, no rela_fuse), what every public GLIGEN checkpoint was trained on (gl_unet_config.no_relation).  Not in
+    # the config dict of a checkpoint: interface.load_ckpt sets it from the state dict's keys
+    relation: bool = True
 
     @property
     def first_conv_in(self) -> int:
@@ -257,8 +261,8 @@ def rela_params(p: str, C: int, ctx: int) -> Dict[str, Tuple[int, ...]]:
     return out
 
 
-def block_params(t: str, C: int, ctx: int) -> Dict[str, Tuple[int, ...]]:
-    """BasicTransformerBlock (attention.py:362-384), in module registration order."""
+def block_params(t: str, C: int, ctx: int, relation: bool = True) -> Dict[str, Tuple[int, ...]]:
+    """BasicTransformerBlock (attention.py:362-384), in module registration order; ``relation=False``: upstream's, without rela_fuse."""
     out: Dict[str, Tuple[int, ...]] = {}
     out.update(attn_params(_j(t, "attn1"), C, C))
     out.update(ff_params(_j(t, "ff"), C))
@@ -266,16 +270,17 @@ def block_params(t: str, C: int, ctx: int) -> Dict[str, Tuple[int, ...]]:
     for n in ("norm1", "norm2", "norm3"):
         out.update(norm_params(_j(t, n), C))
     out.update(fuser_params(_j(t, "fuser"), C, ctx))
-    out.update(rela_params(_j(t, "rela_fuse"), C, ctx))
+    if relation:
+        out.update(rela_params(_j(t, "rela_fuse"), C, ctx))
     return out
 
 
-def st_params(p: str, C: int, ctx: int) -> Dict[str, Tuple[int, ...]]:
+def st_params(p: str, C: int, ctx: int, relation: bool = True) -> Dict[str, Tuple[int, ...]]:
     """SpatialTransformer (attention.py:405-434)."""
     out: Dict[str, Tuple[int, ...]] = {}
     out.update(norm_params(_j(p, "norm"), C))
     out.update(conv_params(_j(p, "proj_in"), C, C, 1))
-    out.update(block_params(_j(p, "transformer_blocks.0"), C, ctx))
+    out.update(block_params(_j(p, "transformer_blocks.0"), C, ctx, relation))
     out.update(conv_params(_j(p, "proj_out"), C, C, 1))
     return out
 
@@ -297,7 +302,7 @@ def param_shapes(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
         elif l.kind == "res":
             out.update(res_params(l.prefix, l.cin, l.cout, te))
         elif l.kind == "st":
-            out.update(st_params(l.prefix, l.cin, ctx))
+            out.update(st_params(l.prefix, l.cin, ctx, cfg.relation))
         else:
             raise ValueError(l.kind)
     out.update(norm_params("out.0", plan.out_channels_last))

@@ -64,7 +64,8 @@ struct GraphKey {
     int reps;
     bool uniform_t;             // one timestep for the whole batch: with reps == 2 the shared cond / uncond prefix
     int rel_slots;
-    auto tie() const { return std::tie(Bn, lat_h, lat_w, R, Lc, fuser_on, sd_conv, reps, uniform_t, rel_slots); }
+    bool no_relation;           // a handle without the rela_fuse chain (gl_unet_config.no_relation): another launch sequence
+    auto tie() const { return std::tie(Bn, lat_h, lat_w, R, Lc, fuser_on, sd_conv, reps, uniform_t, rel_slots, no_relation); }
     bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
 };
 
@@ -361,6 +362,7 @@ void build_table(gl_engine* e) {
             add_norm(e, f + ".norm2", C);
             add_w(e, f + ".tanh_attn", 1, {1});
             add_w(e, f + ".tanh_dense", 1, {1});
+            if (c.no_relation) return;      // the upstream block (attention_original.py:312-316) has no rela_fuse
             const std::string r = t + ".rela_fuse";
             add_mat(e, r + ".attn.q.w", C, C);
             add_mat(e, r + ".attn.kv.w", 2 * C, ctx);
@@ -843,8 +845,10 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, in
         x = y;
     }
     // --- relation injection (attention.py:315-359, :398), closed form
+    // (a no_relation handle has no such chain: the fuser's output -- attn1's at fuser scale 0 -- goes straight to LayerNorm(norm2) -> attn2,
+    // attention_original.py:312-316)
     bool ln2_done = false;
-    {
+    if (!cfg.no_relation) {
         const std::string rf = t + ".rela_fuse";
         const std::string ss = level_tag(sh, sw);
         const int* rects = reinterpret_cast<const int*>(e->buf("cond.rects." + ss, (size_t)Bn * mo * 16));
@@ -1093,6 +1097,7 @@ extern "C" int gl_create(const gl_unet_config* cfg, gl_engine** out) {
     if ((cfg->pos_in_dim + 8 * cfg->fourier_freqs) % 64) return GL_ERR_UNSUPPORTED;
     if (cfg->grounding != 0 && cfg->grounding != 1) return GL_ERR_UNSUPPORTED;
     if (cfg->max_objs <= 0 || n_ground(*cfg) > 64) return GL_ERR_UNSUPPORTED;
+    if (cfg->no_relation != 0 && cfg->no_relation != 1) return GL_ERR_UNSUPPORTED;
     if ((cfg->inpaint_mode != 0 && cfg->inpaint_mode != 1) || first_conv_in(*cfg) > CIN_PAD) return GL_ERR_UNSUPPORTED;
     gl_engine* e = new gl_engine();
     e->cfg = *cfg;
@@ -1151,7 +1156,7 @@ extern "C" int gl_load_weights(gl_engine* e, const void* packed, int64_t bytes, 
     for (size_t i = 0; i < n; ++i) {
         const std::string t = e->st_layers[i].prefix + ".transformer_blocks.0";
         const char* names[4] = {".fuser.tanh_attn", ".fuser.tanh_dense", ".rela_fuse.tanh_attn", ".rela_fuse.tanh_dense"};
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < (e->cfg.no_relation ? 2 : 4); ++k)     // (no_relation: slots 2 and 3 keep their place, unused)
             if (hipMemcpy(&e->gate_tanh[i * 4 + k], e->W(t + names[k]), sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return GL_ERR_BAD_ARG;
     }
     e->fuser_scale_cur = -1e30f;
@@ -1252,7 +1257,10 @@ namespace {
 int set_conditioning(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks, const float* pos_emb,
                      const float* text_masks, const float* image_masks, const float* image_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t h,
                      int32_t w, void* stream) {
-    if (!e || !e->wbase || !context || !relations || !boxes || !masks || !pos_emb || Bn <= 0 || Lc <= 0 || R <= 0 || h <= 0 || w <= 0) return GL_ERR_BAD_ARG;
+    if (!e || !e->wbase || !context || !boxes || !masks || !pos_emb || Bn <= 0 || Lc <= 0 || h <= 0 || w <= 0) return GL_ERR_BAD_ARG;
+    const bool rel = e->cfg.no_relation == 0;
+    if (rel && (!relations || R <= 0)) return GL_ERR_BAD_ARG;
+    if (!rel) { relations = nullptr; R = 0; }       // a no_relation handle ignores both (R = 0 in its graph keys)
     gl_opts_scope opts_scope(e->ovr);       // this handle's option overrides are in effect for the call
     const gl_unet_config& cfg = e->cfg;
     hipStream_t st = (hipStream_t)stream;
@@ -1276,8 +1284,9 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     half_t* h2 = e->h16("pn.h2", nch * crow * 512);
     half_t* objs = e->h16("pn.objs", nch * crow * D);
     half_t* ctx16 = e->h16("cond.ctx", (size_t)Bn * Lc * ctx);
-    half_t* rel16 = e->h16("cond.rel", (size_t)Bn * R * ctx);
-    CKP(pin); CKP(h1); CKP(h2); CKP(objs); CKP(ctx16); CKP(rel16);
+    half_t* rel16 = rel ? e->h16("cond.rel", (size_t)Bn * R * ctx) : nullptr;
+    CKP(pin); CKP(h1); CKP(h2); CKP(objs); CKP(ctx16);
+    if (rel) CKP(rel16);
     if (ti) {
         CK(gl_posnet_input_ti(boxes, masks, text_masks, image_masks, pos_emb, image_emb, e->Wf("position_net.null_text"), e->Wf("position_net.null_image"),
                               e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim, cfg.fourier_freqs, pin, pin + crow * pin_dim, st));
@@ -1300,7 +1309,7 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
         objs = cat;
     }
     f32_to_f16_kernel<<<dim3(256), dim3(256), 0, st>>>(context, ctx16, (size_t)Bn * Lc * ctx);
-    f32_to_f16_kernel<<<dim3(64), dim3(256), 0, st>>>(relations, rel16, (size_t)Bn * R * ctx);
+    if (rel) f32_to_f16_kernel<<<dim3(64), dim3(256), 0, st>>>(relations, rel16, (size_t)Bn * R * ctx);
     GL_CHECK_LAUNCH();
     for (size_t li = 0; li < e->st_layers.size(); ++li) {
         const LayerD& l = e->st_layers[li];
@@ -1321,6 +1330,7 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
         CKP(kv); CKP(vt);
         CK(r.gemm({ctx16, ctx}, t + ".attn2.kv", Bn * Lc, kv, 2 * C, {.bias = false}));
         CK(r.transpose_v(kv + C, (int64_t)Lc * 2 * C, 2 * C, vt, ldc_, Bn, H, d, Lc));
+        if (!rel) continue;
         // rela_fuse K/V of the relation tokens (attention.py:348-349)
         half_t* kvr = e->h16("hoist.kvrel." + sl, (size_t)Bn * R * 2 * C);
         const int ldr_ = vt_ld(R);
@@ -1349,8 +1359,9 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
         }
         if (g_strict != 0) CK(strict_hoists(e, st));
     }
-    // --- integer rectangles per transformer resolution (attention.py:321-346)
-    {
+    // --- integer rectangles per transformer resolution (attention.py:321-346); none on a no_relation handle (they feed the relation chain alone)
+    e->rel_slots = 0;
+    if (rel) {
         std::vector<std::pair<int, int>> sides;
         int ch = h, cw = w;
         auto note = [&](int a, int b) { for (auto& v : sides) if (v.first == a && v.second == b) return; sides.push_back({a, b}); };
@@ -1502,7 +1513,7 @@ extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev,
         e->ovr_epoch = e->ovr.epoch;
     }
     const bool uniform_t = t_dev == nullptr;
-    const GraphKey key{Bn, e->lat_h, e->lat_w, e->R, e->Lc, fuser_on, sd_conv != 0, reps, uniform_t, e->rel_slots};
+    const GraphKey key{Bn, e->lat_h, e->lat_w, e->R, e->Lc, fuser_on, sd_conv != 0, reps, uniform_t, e->rel_slots, cfg.no_relation != 0};
     auto it = e->graphs.find(key);
     if (use_graph && it == e->graphs.end()) {
         // warm-up run allocates every pooled buffer, then the same launch sequence is captured

@@ -103,7 +103,16 @@ class UNetEngine:
 
         A text_image engine (``cfg.grounding == "text_image"``, gl_set_conditioning_ti) takes the phrase embeddings as
         ``positive_embeddings`` plus ``text_masks`` / ``image_masks`` [Bn,30] and ``image_embeddings`` [Bn,30,in_dim]
-        (text_image_grounding_net.py:41); giving them to a text engine, or leaving them out of a text_image one, raises."""
+        (text_image_grounding_net.py:41); giving them to a text engine, or leaving them out of a text_image one, raises.
+
+        An engine without the relation chain (``cfg.relation`` False, gl_unet_config.no_relation) takes ``relations=None`` and ignores a
+        given tensor; on every other engine ``None`` raises ValueError before anything is launched."""
+        rel_on = getattr(self.cfg, "relation", True)
+        if not rel_on:
+            relations = None
+        elif relations is None:
+            raise ValueError("this model carries the rela_fuse relation chain: it needs relations [Bn, R, ctx] (only a model loaded from a "
+                             "checkpoint without rela_fuse, UNetConfig.relation = False, runs without)")
         ti = self.cfg.grounding == "text_image"
         extra = (text_masks, image_masks, image_embeddings)
         if ti and any(v is None for v in extra):
@@ -118,23 +127,25 @@ class UNetEngine:
             h = w = hw
         dev = self.dev
         f32 = lambda t: torch.as_tensor(t, dtype=F32).to(dev).contiguous()
-        context, relations = f32(context), f32(relations)
+        context = f32(context)
+        relations = f32(relations) if rel_on else None
         boxes, masks, pe = f32(boxes), f32(masks), f32(positive_embeddings)
         Bn, mo = boxes.shape[0], boxes.shape[1]
         if mo != self.cfg.max_objs:
             raise ValueError(f"{mo} grounding slots, the model was built for {self.cfg.max_objs}")
-        if context.shape[-1] != self.cfg.context_dim or relations.shape[-1] != self.cfg.context_dim or pe.shape[-1] != self.cfg.pos_in_dim:
+        if context.shape[-1] != self.cfg.context_dim or (rel_on and relations.shape[-1] != self.cfg.context_dim) or pe.shape[-1] != self.cfg.pos_in_dim:
             raise ValueError("conditioning feature dims do not match the model config")
-        if not (context.shape[0] == relations.shape[0] == masks.shape[0] == pe.shape[0] == Bn):
+        if not (context.shape[0] == masks.shape[0] == pe.shape[0] == Bn) or (rel_on and relations.shape[0] != Bn):
             raise ValueError("conditioning batch sizes differ")
-        R, Lc = relations.shape[1], context.shape[1]
+        R, Lc = (relations.shape[1] if rel_on else 0), context.shape[1]
+        rel_ptr = relations.data_ptr() if rel_on else None      # NULL on an engine without the relation chain
         if ti:
             check_latent_hw(self.cfg, h, w)          # gl_set_conditioning_ti applies the _hw entry's shape rule to squares too
             tm, im, ie = f32(text_masks), f32(image_masks), f32(image_embeddings)
             if tuple(tm.shape) != tuple(masks.shape) or tuple(im.shape) != tuple(masks.shape) or tuple(ie.shape) != tuple(pe.shape):
                 raise ValueError("text_masks / image_masks must match masks, image_embeddings must match the text embeddings")
             with torch.cuda.device(dev):
-                check(self._lib.gl_set_conditioning_ti(self.handle, context.data_ptr(), relations.data_ptr(), boxes.data_ptr(), masks.data_ptr(),
+                check(self._lib.gl_set_conditioning_ti(self.handle, context.data_ptr(), rel_ptr, boxes.data_ptr(), masks.data_ptr(),
                                                        tm.data_ptr(), im.data_ptr(), pe.data_ptr(), ie.data_ptr(), Bn, Lc, R, h, w, self._stream()),
                       "gl_set_conditioning_ti")
             self._cond_refs = (context, relations, boxes, masks, pe, tm, im, ie)      # read asynchronously by the launched kernels
@@ -142,10 +153,10 @@ class UNetEngine:
             return
         with torch.cuda.device(dev):
             if rect:
-                check(self._lib.gl_set_conditioning_hw(self.handle, context.data_ptr(), relations.data_ptr(), boxes.data_ptr(), masks.data_ptr(),
+                check(self._lib.gl_set_conditioning_hw(self.handle, context.data_ptr(), rel_ptr, boxes.data_ptr(), masks.data_ptr(),
                                                        pe.data_ptr(), Bn, Lc, R, h, w, self._stream()), "gl_set_conditioning_hw")
             else:
-                check(self._lib.gl_set_conditioning(self.handle, context.data_ptr(), relations.data_ptr(), boxes.data_ptr(), masks.data_ptr(),
+                check(self._lib.gl_set_conditioning(self.handle, context.data_ptr(), rel_ptr, boxes.data_ptr(), masks.data_ptr(),
                                                     pe.data_ptr(), Bn, Lc, R, hw, self._stream()), "gl_set_conditioning")
         self._cond_refs = (context, relations, boxes, masks, pe)      # read asynchronously by the launched kernels
         self.cond = dict(Bn=Bn, mo=mo, R=R, Lc=Lc, hw=hw, H=h, W=w)

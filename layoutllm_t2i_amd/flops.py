@@ -44,8 +44,9 @@ def unet_forward_flops(cfg: UNetConfig, hw, fuser_on: bool = True, n_ctx: int = 
                 g += lin(mo, ctx, C)                                     # fuser.linear
                 g += 3 * lin(n + mo, C, C) + attn(n + mo, n + mo, C) + lin(n + mo, C, C)
                 g += lin(n, C, 8 * C) + lin(n, 4 * C, C)                 # fuser.ff
-            g += lin(mo, C, C) + 2 * lin(n_rel, ctx, C) + attn(mo, n_rel, C) + lin(mo, C, C)   # rela_fuse.attn
-            g += lin(mo, C, 8 * C) + lin(mo, 4 * C, C)                   # rela_fuse.ff
+            if cfg.relation:                                             # (a checkpoint without rela_fuse: the upstream block has neither)
+                g += lin(mo, C, C) + 2 * lin(n_rel, ctx, C) + attn(mo, n_rel, C) + lin(mo, C, C)   # rela_fuse.attn
+                g += lin(mo, C, 8 * C) + lin(mo, 4 * C, C)               # rela_fuse.ff
             g += lin(n, C, C) + 2 * lin(n_ctx, ctx, C) + attn(n, n_ctx, C) + lin(n, C, C)      # attn2
             g += lin(n, C, 8 * C) + lin(n, 4 * C, C)                     # ff
         return g

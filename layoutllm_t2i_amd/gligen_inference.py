@@ -13,7 +13,8 @@ a passed ``starting_noise`` [bs, 4, h, w] decides the shape itself (image = 8h x
 ``meta``: ``ckpt`` (path), ``prompt``, ``phrases``, ``locations`` (ltrb, normalised), optional
 ``alpha_type``, ``save_folder_name``, ``images`` (one reference image or None per box, for a ``*_box_text_image`` checkpoint; with
 ``text_mask`` / ``image_mask`` / ``projection_matrix`` as in interface.prepare_batch); ``config``: object/dict with ``batch_size``, ``guidance_scale``,
-``no_plms`` (must be False), optional ``folder``.  Images are saved like the reference does
+``no_plms`` (must be False), optional ``negative_prompt`` (a string encoded for the unconditional pass, gligen_inference.py:379-380; default
+None = the empty prompt), optional ``folder``.  Images are saved like the reference does
 (gligen_inference.py:437-446) when ``config.folder`` is given.
 
 ``meta["input_image"]`` (a path or a PIL.Image) inpaints that image inside the layout boxes (gligen_inference.py:393-407): it is
@@ -23,6 +24,9 @@ latent at every step.  The reference asserts a 9-channel ``inpaint_mode`` checkp
 here and additionally feeds ``cat([z0 * mask, mask])`` to the first conv on every forward (:406-407, openaimodel.py:436-439); it needs
 ``meta["input_image"]`` (ValueError otherwise).  A 4-channel text_layout / text_image checkpoint with ``input_image`` keeps running the
 latent-blend inpainting alone, which the reference refuses.
+
+A checkpoint without ``rela_fuse`` tensors (every public GLIGEN checkpoint) runs on the upstream transformer block it was trained with
+(attention_original.py:312-316): no relation phrases are parsed or encoded for it.
 """
 from __future__ import annotations
 
@@ -53,6 +57,8 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     all_models[0].first_conv_type = "GLIGEN"
     bs = _get(config, "batch_size", 1)
     args = dict(batch_size=bs, no_plms=bool(_get(config, "no_plms", False)), guidance_scale=_get(config, "guidance_scale", 7.5))
+    if _get(config, "negative_prompt") is not None:      # gligen_inference.py:379-380; absent / None = the empty prompt
+        args["negative_prompt"] = _get(config, "negative_prompt")
     m = dict(prompt=meta["prompt"], phrases=meta.get("phrases"), locations=meta["locations"],
              alpha_type=meta.get("alpha_type", [0.3, 0.0, 0.7]), input_image=meta.get("input_image"))
     # image grounding (a *_box_text_image checkpoint, gligen_inference.py:350-352): one reference image or None per box

@@ -120,6 +120,20 @@ def find_sd_first_conv(ckpt_path=None):
     return None
 
 
+def checkpoint_has_relation(state_dict, cfg) -> bool:
+    """Which transformer block a checkpoint's UNet was trained on, read off its keys: no ``*.rela_fuse.*`` tensor at all = upstream GLIGEN's
+    block (attention_original.py:312-316; every public GLIGEN checkpoint) -> False; all of them = LayoutLLM-T2I's (attention.py:394-402) ->
+    True.  Some but not all is a damaged checkpoint: KeyError naming a missing tensor, what packing it raises."""
+    import dataclasses
+    from .arch import param_shapes
+    if not any(".rela_fuse." in k for k in state_dict):
+        return False
+    missing = [k for k in param_shapes(dataclasses.replace(cfg, relation=True)) if ".rela_fuse." in k and k not in state_dict]
+    if missing:
+        raise KeyError(f"state_dict is missing {len(missing)} tensors, e.g. {missing[:3]}")
+    return True
+
+
 def load_ckpt(ckpt_path, device="cuda", strict=None):
     """interface.py:78-101.  The UNet ('model') is built by this package from saved_ckpt['model'];
     autoencoder / text_encoder / grounding tokenizer are instantiated from the checkpoint's config.
@@ -135,10 +149,12 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
     saved_ckpt = torch.load(ckpt_path, map_location="cpu")
     config = saved_ckpt["config_dict"]["_content"]
     cfg = UNetConfig.from_dict(config["model"]["params"], allow_inpaint=True)      # _run builds the inpainting extra such a model needs
+    import dataclasses
+    # a checkpoint without rela_fuse tensors (GLIGEN's own) runs on the upstream block, not on a default-initialised relation chain
+    cfg = dataclasses.replace(cfg, relation=checkpoint_has_relation(saved_ckpt["model"], cfg))
     if strict is None:
         strict = os.environ.get("GLIGEN_STRICT") == "1"
     if strict:
-        import dataclasses
         cfg = dataclasses.replace(cfg, split_weights=True)
     # (an inpaint_mode checkpoint's 9-channel first conv is not restorable, openaimodel.py:296: the SD conv file is neither looked for nor missed)
     sd_path = None if cfg.inpaint_mode else find_sd_first_conv(ckpt_path)
@@ -463,7 +479,8 @@ def denoise(all_models, context, uc, relations, grounding_batch, starting_noise,
     (run_batch_images lines interface.py:505-539 without text/VAE stages).  ``mask`` [1|B, 1, h, w] (1 = keep) and ``x0``
     [1|B, 4, h, w] (the encoded input image): inpainting, plms.py:95-99.  The latent's shape [B, 4, h, w] is ``starting_noise``'s
     (plms.py:68-71); h != w needs both to be multiples of 2^(number of UNet downsamples) = 8.  ``inpainting_extra_input`` [1|B, 5, h, w]: the
-    extra first-conv input of an inpaint_mode model (required there, ignored by every other model)."""
+    extra first-conv input of an inpaint_mode model (required there, ignored by every other model).  ``relations``: None for a model without
+    the relation chain (ignored there); a model with it raises ValueError on None before any kernel runs."""
     model, autoencoder, text_encoder, diffusion, config = all_models
     _check_noise(model, starting_noise)
     sampler = PLMSSampler(diffusion, model, alpha_generator_func=partial(alpha_generator, type=alpha_type),
@@ -508,15 +525,23 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
         raise NotImplementedError("the DDIM path is broken in the reference with this UNet (SURVEY App-B#8); PLMS only")
     bs = cfg.batch_size
     max_rel = cfg.get("max_relations", 10)
+    with_rel = bool(getattr(model.cfg, "relation", True))       # a checkpoint without rela_fuse: no scene-graph parse, no relation phrases
+    relations = None
     if multiple:
         batch = prepare_batch_multiple(meta, clip_model, clip_processor, bs, device=device)
         context = text_encoder.encode(meta["prompts"])
-        relations = prepare_relation_phrases_batch(meta["prompts"], max_rel, text_encoder, device=device)
+        if with_rel:
+            relations = prepare_relation_phrases_batch(meta["prompts"], max_rel, text_encoder, device=device)
     else:
         batch = prepare_batch(meta, clip_model, clip_processor, bs, device=device)
         context = text_encoder.encode([meta["prompt"]] * bs)
-        relations = prepare_relation_phrases(meta["prompt"], bs, max_rel, text_encoder, device=device)
-    uc = text_encoder.encode([""]).repeat(bs, 1, 1)          # the reference encodes bs copies of "" (interface.py:496)
+        if with_rel:
+            relations = prepare_relation_phrases(meta["prompt"], bs, max_rel, text_encoder, device=device)
+    # the reference encodes bs copies of "" (interface.py:496); args["negative_prompt"] (gligen_inference.py:379-380) replaces it, per call
+    neg = args.get("negative_prompt")
+    if neg is not None and not isinstance(neg, str):
+        raise TypeError(f"negative_prompt must be a string or None, got {type(neg).__name__}")
+    uc = text_encoder.encode(["" if neg is None else neg]).repeat(bs, 1, 1)
     mask = z0 = extra = None
     if meta.get("input_image") is not None:
         # inpainting (gligen_inference.py:393-407): encode the input image, regenerate inside the boxes (mask 0), keep the rest
@@ -641,6 +666,9 @@ def load_all_models_sharded(ckpt, device, src=0, strict=None):
         if model.cfg.inpaint_mode:
             raise NotImplementedError("the sharded entry has no input image: an inpaint_mode checkpoint runs through load_all_models / "
                                       "run_one_image / run_batch_images with meta['input_image']")
+        if not getattr(model.cfg, "relation", True):
+            raise NotImplementedError("the sharded entry prepares and scatters relation phrases: a checkpoint without rela_fuse runs through "
+                                      "load_all_models / run_one_image / run_batch_images")
         if not isinstance(autoencoder, VAEDecoder):
             raise NotImplementedError("the sharded entry broadcasts the HIP VAE decoder's packed weights (unset GLIGEN_REFERENCE_VAE)")
         dcfg = dict(linear_start=diffusion.linear_start, linear_end=diffusion.linear_end, timesteps=diffusion.num_timesteps)

@@ -204,7 +204,10 @@ class UNetModel:
         return self.grounding_tokenizer_input.get_null_input()
 
     def set_conditioning(self, context, relations, grounding: dict, hw, key=None) -> None:
-        """``hw``: the latent side, or (h, w) for a rectangular latent (UNetEngine.set_conditioning)."""
+        """``hw``: the latent side, or (h, w) for a rectangular latent (UNetEngine.set_conditioning).  ``relations``: None on a model without
+        the relation chain (a given tensor is ignored there); None on any other model raises ValueError before the engine is touched."""
+        if getattr(self.cfg, "relation", True) and relations is None:
+            self.relations_of({})
         if key is not None and key == self._cond_key:
             return
         if self.cfg.grounding == "text_image":
@@ -218,6 +221,18 @@ class UNetModel:
             self.engine.set_conditioning(context, relations, grounding["boxes"], grounding["masks"],
                                          grounding["positive_embeddings"], hw)
         self._cond_key = key
+
+    def relations_of(self, input: dict):
+        """``input["relations"]``: required on a model with the rela_fuse chain (ValueError before any kernel runs); a model loaded from a
+        checkpoint without it (``cfg.relation`` False, the upstream GLIGEN block) takes no relations -- the upstream ``input`` dict has no such
+        key -- and ignores a given tensor."""
+        if not getattr(self.cfg, "relation", True):
+            return None
+        rel = input.get("relations")
+        if rel is None:
+            raise ValueError("this model carries the rela_fuse relation chain: input['relations'] [B, R, ctx] is required (only a checkpoint "
+                             "without rela_fuse tensors, UNetConfig.relation = False, runs without relations)")
+        return rel
 
     def inpaint_extra_of(self, input: dict) -> Optional[torch.Tensor]:
         """``input["inpainting_extra_input"]`` (openaimodel.py:436-439): required on an inpaint_mode model, ignored on every other (as the
@@ -235,9 +250,10 @@ class UNetModel:
         """UNetModel.forward (openaimodel.py:413-459): one B-sized evaluation."""
         x = input["x"]
         extra = self.inpaint_extra_of(input)
+        rel = self.relations_of(input)
         g = self.grounding_of(input)
         H, W = (int(v) for v in x.shape[-2:])
-        self.set_conditioning(input["context"], input["relations"], g, H if H == W else (H, W), key=None)
+        self.set_conditioning(input["context"], rel, g, H if H == W else (H, W), key=None)
         if extra is not None:
             self.engine.set_inpaint_extra(extra)
         t = input["timesteps"]

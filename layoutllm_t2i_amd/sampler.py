@@ -83,6 +83,7 @@ class PLMSSampler(object):
 
         # ---- conditioning, once per image: [cond ; uncond] when CFG is active (plms.py:115-124)
         extra = model.inpaint_extra_of(input)      # raises on an inpaint_mode model without the extra, before any kernel runs
+        rel_in = model.relations_of(input)         # None on a model without the relation chain; raises where the chain needs them
         cfg_on = uc is not None and guidance_scale != 1
         g = model.grounding_of(input)
         f32 = lambda t: t.to(dev, torch.float32)
@@ -91,11 +92,11 @@ class PLMSSampler(object):
                 raise RuntimeError("model.grounding_tokenizer_input is not set (interface.py:370)")
             gn = model.grounding_tokenizer_input.get_null_input()
             ctx = torch.cat([f32(input["context"]), f32(uc)], 0)
-            rel = torch.cat([f32(input["relations"])] * 2, 0)
+            rel = torch.cat([f32(rel_in)] * 2, 0) if rel_in is not None else None
             grounding = {k: torch.cat([f32(g[k]), f32(gn[k])], 0) for k in gn}      # whatever keys the grounding tokenizer input has (3 for text, 6 for text_image)
             reps = 2
         else:
-            ctx, rel = f32(input["context"]), f32(input["relations"])
+            ctx, rel = f32(input["context"]), (f32(rel_in) if rel_in is not None else None)
             grounding = {k: f32(v) for k, v in g.items() if torch.is_tensor(v)}
             reps = 1
         model.set_conditioning(ctx, rel, grounding, H if H == W else (H, W), key=None)      # (H, W): the rectangular entry and its shape check

@@ -271,6 +271,8 @@ def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_
             norm(f + ".norm2")
             S[f + ".tanh_attn"] = math.tanh(float(g(f + ".alpha_attn")))
             S[f + ".tanh_dense"] = math.tanh(float(g(f + ".alpha_dense")))
+            if not getattr(cfg, "relation", True):
+                continue                                # the upstream block (attention_original.py:312-316): no rela_fuse entries in the table either
             r = t + ".rela_fuse"
             cross_attn(r + ".attn", l.d_head)
             ff(r + ".ff")
