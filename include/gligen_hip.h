@@ -670,7 +670,13 @@ int gl_sizeof_gn_args(void);
  * key 52 = three-pass split-fp16 products xhi.Whi + xlo.Whi + xhi.Wlo (gl_gemm with K = 3 * kwrap whose second source is the first one again;
  * gl_conv3x3 with in_split = 3) run the DEDICATED three-pass main loop of the 8-wave kernel (1 default; csrc/gemm8.hip S3: a ring stage holds
  * one 32-wide k slice of {xhi, xlo, Whi, Wlo} and feeds three MFMA groups, so no operand is staged twice); 0 = the K-walk over
- * [xhi | xlo | xhi] x [Whi | Whi | Wlo].  Same products, other fp32 summation order. */
+ * [xhi | xlo | xhi] x [Whi | Whi | Wlo].  Same products, other fp32 summation order.
+ * key 54 = kx-reuse main loop of the 8-wave 3x3 conv (csrc/gemm8.hip KXR): the input rows of one (channel block, ky) are staged ONCE for the
+ * three kx taps, which read their fragments at LDS rows shifted by kx (33 instead of 96 A staging units per three K-tiles).  Eligible launches:
+ * 256-row tiles of the plain fp16 loop, stride 1, no upsample, no pad01 window, no split input, (channel block, tap) K order (key 33 = 0),
+ * K slices of whole channel blocks (a multiple of 9 K-tiles); every other launch takes the plain loop whatever the value.  0 = never,
+ * 1 = every eligible launch, 2 (default) = the eligible shapes on which it measured faster (profiles/kxreuse_shapes.txt).  Same bits as the
+ * plain loop: same MFMA sequence on the same operand values. */
 int gl_set_option(int key, int value);
 /* gl_set_option writes the PROCESS defaults (op-level calls and every handle without an override see them).  A handle can
  * override individual keys for itself: while one of ITS entry points (gl_set_conditioning / gl_unet_forward / gl_plms_step,
@@ -687,7 +693,8 @@ int gl_vae_set_option(gl_vae* v, int key, int value);
  * what = 10 copies ten uint64: the gl_attention calls this process has served per kernel form -- [0] software-pipelined split-fp16
  * kernel, [1] 8-wave split-fp16 kernel, [2] 4-wave split-fp16 kernel, double-buffered, [3] 4-wave split-fp16 kernel, single buffer set,
  * [4..6] single-fp16 8-wave kernel with the running max on the FMA path / in the accumulator init / in the padding column (PRE 0 / 1 / 2),
- * [7..9] single-fp16 4-wave kernel, PRE 0 / 1 / 2 (tests/test_gpu_attention_layouts.py asserts which form took each launch). */
+ * [7..9] single-fp16 4-wave kernel, PRE 0 / 1 / 2 (tests/test_gpu_attention_layouts.py asserts which form took each launch);
+ * what = 11 copies one uint64: the gl_conv3x3 calls this process has served with the kx-reuse loop of the 8-wave kernel (key 54). */
 int gl_debug_read(int what, void* dst, int64_t bytes);
 /* one-time per-process setup (raises dynamic-LDS limits of the tiled kernels); idempotent */
 int gl_init(void);

@@ -31,6 +31,7 @@
 #include "gligen_hip.h"
 #include "gemm_shared.h"
 #include "opts.h"
+#include <atomic>
 #include <type_traits>
 
 #ifndef G8_S3_PHASES
@@ -63,6 +64,21 @@ struct G8 {
     static_assert(STAGE % 128 == 0, "stage alignment (the k-half XOR of the fragment offsets relies on it)");
 };
 
+// LDS image of the kx-reuse conv loop (KXR, BM = 256): two A buffers of 264 pixel rows x 128 B (33 one-KiB staging units), each followed by
+// one 128-byte row of zeros (the target of horizontally masked fragment reads; one per buffer so that a fragment offset is the same number in
+// both buffers), then the three B stages.
+template <int BN>
+struct G8X {
+    static constexpr int A_UNITS = 33;
+    static constexpr int A_BYTES = A_UNITS * 1024;     // 264 rows
+    static constexpr int A_STRIDE = A_BYTES + 128;     // + the zero row
+    static constexpr int B_BYTES = BN * 64 * 2;
+    static constexpr int B_BASE = 2 * A_STRIDE;
+    static constexpr int LDS = B_BASE + 3 * B_BYTES;   // 129280 / 116992 bytes
+    static_assert(A_STRIDE % 128 == 0 && B_BASE % 128 == 0, "the k-half XOR of the fragment offsets stays inside a 128-byte row");
+    static_assert(LDS >= 8 * 32 * (BN / 2 + 4) * 4, "the epilogue restages through the ring memory");
+};
+
 template <int N>
 __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -93,7 +109,25 @@ __device__ unsigned long long g8_stamps[4 * 4096];
 // for the staging work of 40, every staged byte used 1.5-2 x.  Three phases per stage: [read Ahi, Whi] hi.hi, [read Alo] lo.hi,
 // [read Wlo] hi.lo.  Arguments as for the K-walk (p.kwrap = the true K; A rows [hi | lo] with lo p.kwrap columns to the right, for a
 // conv cg.Cin / 2 channels to the right; weight rows [Whi | Wlo], Wlo p.kwrap columns to the right); kt_per_split counts 32-wide tiles.
-template <int BM, int BN, bool CONV, int DBG = 0, bool S3 = false>
+//
+// KXR: the kx-reuse main loop of a stride-1 3x3 conv (fp16 loop, BM = 256, (channel block, tap) order, whole (channel block) runs of 9 K-tiles
+// per slice).  The three kx taps of one ky read the same run of input pixels shifted by -1 / 0 / +1 rows of the NHWC matrix, so the A operand
+// is staged once per (channel block, ky) -- a "super K-tile" of three K-tiles -- as 264 pixel rows (LDS row j = the input pixel
+// m0 - 1 + j + (ky - 1) * Win), and tap kx of output row r reads its fragment from LDS row r + kx: 33 A units per three K-tiles instead of 96.
+//   staging-time validity (v_bfi select to the zero page, as above): what is a property of the staged pixel -- with m_c = m0 - 1 + j the
+//     output pixel whose kx = 1 tap the row is, 0 <= m_c < M and oy(m_c) + ky - 1 inside the map;
+//   read-time validity: ox(r) + kx - 1 inside the map, a property of the READING row -- three K-invariant sets of per-lane fragment offsets,
+//     in which a masked lane's offset is that of the zero row behind the buffer (kx = 1 is never masked: one register + immediates).
+//   schedule: B exactly as above (K-tile t+2 issued during K-tile t into a three-stage ring); the A image of super K-tile s+1 is issued
+//     during the kx = 0 and kx = 1 K-tiles of super K-tile s into the other A buffer (kx = 2 issues none: its instructions would not be
+//     covered by that K-tile's counted wait, which precedes the first read of the new buffer).  Per wave and K-tile, (phase 0 | phase 1):
+//     kx 0: A0 A1 B0 | B1 [B2];  kx 1: A2 A3 B0 | B1 [B2] [A4];  kx 2: B0 B1 | [B2] -- [.] = wave-uniform extras issued behind the cluster
+//     (B2: group-0 waves of the 160-wide tile; A4 = unit 32: wave 4).  Counted wait = the phase-0 count: vmcnt(3 / 3 / 2).
+//   hazards: the A buffer of super K-tile s+1 held super K-tile s-1, last read in phase 1 of its kx = 2 K-tile, and is refilled from the
+//     phase-0 cluster of the next K-tile on -- the timing of a B stage, whose WAR argument above applies; RAW: the last A instructions go out
+//     in K-tile 3s+1 and are retired by every wave's counted wait in phase 1 of K-tile 3s+2, >= 1 barrier before K-tile 3s+3 reads them.
+//   The MFMA sequence per output element (channel block, ky, kx, k half) and every operand value are those of the loop above: same bits.
+template <int BM, int BN, bool CONV, int DBG = 0, bool S3 = false, bool KXR = false>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom cg, int splitk, int kt_per_split, int order_flags) {
     using C = G8<BM, BN>;
     constexpr int KT = S3 ? 32 : 64;                   // k columns of the product one ring stage covers
@@ -334,19 +368,197 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[mi][ni][r] = 0.0f;
 
-    // ---- prologue: K-tiles 0 and 1 in flight, K-tile 0 landed
-    issue_all(0);
-    if (nkt > 1) {
-        issue_all(1);
-        if (C::NI0 == C::NI1 || grp == 0) wait_vm<C::NI0>();
-        else wait_vm<C::NI1>();
-    } else {
-        wait_vm<0>();
-    }
-    G8_SBAR();
-    if (grp == 1) G8_SBAR();               // stagger: group 1 runs one barrier interval behind group 0
+    if constexpr (KXR) {
+        static_assert(CONV && !S3 && BM == 256 && C::NB1 >= 2, "kx-reuse loop: plain fp16 conv loop on 256-row tiles");
+        using X = G8X<BN>;
+        constexpr int NMF = MI * TN;
+        const int hw = cg.Hout * cg.Wout;
+        const bool pow2 = ((cg.Wout & (cg.Wout - 1)) | (hw & (hw - 1))) == 0;
+        auto pix = [&](const int m, int& oy, int& ox) __attribute__((always_inline)) {      // m >= 0
+            if (pow2) {
+                const int rr = m & (hw - 1);
+                oy = rr >> __builtin_ctz(cg.Wout);
+                ox = rr & (cg.Wout - 1);
+            } else {
+                const int rr = m % hw;
+                oy = rr / cg.Wout;
+                ox = rr - oy * cg.Wout;
+            }
+        };
+        // staging: A unit U = LDS rows 8 U .. 8 U + 7 of the buffer; wave w owns units 4 w .. 4 w + 3 (ids 0..3), wave 4 also unit 32 (id 4)
+        constexpr int XA = 5;
+        const half_t* xptr[XA];
+        unsigned xrb = 0u;                 // 3 bits per unit: valid ky of this lane's staged pixel
+#pragma unroll
+        for (int u = 0; u < XA; ++u) {
+            const int j = 8 * (u < 4 ? 4 * wave + u : 32) + srow;
+            const int mc = m0 - 1 + j;
+            xptr[u] = zsrc;
+            if (mc >= 0 && mc < M) {
+                int oy, ox;
+                pix(mc, oy, ox);
+                xrb |= ((oy >= 1 ? 1u : 0u) | 2u | (oy + 1 < cg.Hin ? 4u : 0u)) << (3 * u);
+                xptr[u] = cg.in + (size_t)mc * cg.Cin + ((sslot ^ ((j >> 1) & 7)) << 3);
+            }
+        }
+        // fragment offsets inside an A buffer, per kx: output row r reads LDS row r + kx; the zero row where ox(r) + kx - 1 leaves the map
+        const int xrow = 64 * wm + lr;
+        auto xfrag = [&](const int j) __attribute__((always_inline)) -> int { return j * 128 + ((lq ^ ((j >> 1) & 7)) << 4); };
+        const int xzero = X::A_BYTES + (lq << 4);
+        const int xo1 = xfrag(xrow + 1);   // + mi * 2048: the swizzle term depends on (lr + kx) only
+        int xo0[MI], xo2[MI];
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+            int oy, ox;
+            pix(m0 + xrow + 16 * mi, oy, ox);
+            xo0[mi] = ox == 0 ? xzero : xfrag(xrow + 16 * mi);
+            xo2[mi] = ox == cg.Win - 1 ? xzero : xfrag(xrow + 16 * mi + 2);
+        }
+        const int xb_off = (PW * grp + lr) * 128 + fsw;
+        if (tid < 16) *reinterpret_cast<uint4*>(smem + (tid >> 3) * X::A_STRIDE + X::A_BYTES + ((tid & 7) << 4)) = make_uint4(0u, 0u, 0u, 0u);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the zero rows are written before the prologue's barrier
 
-    if constexpr (DBG & 1) ts1 = __builtin_readcyclecounter();
+        // issue state: (ky, channel block) of the super K-tile whose A image is being issued; index of the K-tile whose B tile is
+        int xa_ky = 0, xa_cb = kt_begin / 9, xb_kt = kt_begin;
+        int xa_off = -cg.Win * cg.Cin + (xa_cb << 6);
+        int xa_rd = 0, xa_is = 0, xb_rd = 0, xb_is = 0;
+        auto xa_advance = [&]() __attribute__((always_inline)) {
+            if (++xa_ky == 3) { xa_ky = 0; ++xa_cb; }
+            xa_off = (xa_ky - 1) * cg.Win * cg.Cin + (xa_cb << 6);
+        };
+        // LDS-DMA instruction ids: 0..4 = this wave's A units, 8 + j = its B unit j
+        auto x_src = [&](const int id) __attribute__((always_inline)) -> const half_t* {
+            const half_t* src;
+            if (id < 8) {
+                const uint64_t a = reinterpret_cast<uint64_t>(xptr[id < XA ? id : 0] + xa_off), z = reinterpret_cast<uint64_t>(zsrc);
+                const uint64_t keep = (uint64_t)0 - (uint64_t)((xrb >> (3 * id + xa_ky)) & 1u);
+                src = reinterpret_cast<const half_t*>((a & keep) | (z & ~keep));
+                if constexpr (DBG & 2) src = zsrc;
+            } else {
+                const int j = id - 8 < C::NB0 ? id - 8 : 0;
+                src = ((bmask >> j) & 1u) ? bptr[j] + (xb_kt << 6) : zsrc;
+                if constexpr (DBG & 4) src = zsrc;
+            }
+            return src;
+        };
+        auto x_fire = [&](const int id, const half_t* src) __attribute__((always_inline)) {
+            if (id < 8) glds16(src, reinterpret_cast<half_t*>(smem + xa_is * X::A_STRIDE + (id < 4 ? 4 * wave + id : 32) * 1024));
+            else glds16(src, reinterpret_cast<half_t*>(smem + X::B_BASE + xb_is * X::B_BYTES + (bunit0 + id - 8) * 1024));
+        };
+        const bool has_a4 = wave == 4;
+        const bool has_b2 = C::NB0 > 2 && nb > 2;
+
+        // prologue: the A image of super K-tile 0 and B tiles 0 and 1 in flight, all but B tile 1 landed
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x_fire(u, x_src(u));
+        if (has_a4) x_fire(4, x_src(4));
+        xa_advance();
+        xa_is = 1;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            x_fire(8, x_src(8));
+            x_fire(9, x_src(9));
+            if (has_b2) x_fire(10, x_src(10));
+            ++xb_kt;
+            ++xb_is;
+        }
+        if (C::NB0 == C::NB1 || grp == 0) wait_vm<C::NB0>();
+        else wait_vm<C::NB1>();
+        G8_SBAR();
+        if (grp == 1) G8_SBAR();           // stagger, as below
+
+        if constexpr (DBG & 1) ts1 = __builtin_readcyclecounter();
+        // one K-tile (kx of a super K-tile).  MA: a further super K-tile exists (its A image is issued during kx 0 / 1); K-tile t+2, whose B tile
+        // is issued here, exists when MA or kx == 0.
+        auto xtile = [&](auto kx_c, auto ma_c) __attribute__((always_inline)) {
+            constexpr int KX = decltype(kx_c)::value;
+            constexpr bool MA = decltype(ma_c)::value;
+            constexpr bool MB = MA || KX == 0;
+            const unsigned char* abase = smem + xa_rd * X::A_STRIDE;
+            const unsigned char* bbase = smem + X::B_BASE + xb_rd * X::B_BYTES;
+            half8_t af[MI], bf[TN];
+            auto phase = [&](auto kk_c) __attribute__((always_inline)) {
+                constexpr int kk = decltype(kk_c)::value;
+                // pinned LDS-DMA instructions of this phase (between the MFMAs) and the wave-uniform extras behind the cluster
+                constexpr bool AHERE = MA && KX < 2;
+                constexpr int cnt = !MB ? 0 : (kk == 0 ? (AHERE ? 3 : 2) : (AHERE ? 1 : 0));
+                constexpr int id0 = kk == 1 ? 9 : (AHERE ? 2 * KX : 8);
+                constexpr int id1 = AHERE ? 2 * KX + 1 : 9;
+                constexpr int id2 = 8;
+                constexpr bool XB2 = MB && kk == 1 && C::NB0 > 2;
+                constexpr bool XA4 = MA && KX == 1 && kk == 1;
+                constexpr int GP = NMF / (cnt + 1);
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi) {
+                    const int o = KX == 0 ? xo0[mi] : (KX == 2 ? xo2[mi] : xo1 + mi * 2048);
+                    af[mi] = *reinterpret_cast<const half8_t*>(abase + (o ^ (kk << 6)));
+                }
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni)
+                    bf[ni] = *reinterpret_cast<const half8_t*>(bbase + ((xb_off ^ (kk << 6)) + ni * 2048));
+                const half_t* nsrc[5] = {zsrc, zsrc, zsrc, zsrc, zsrc};
+                if constexpr (cnt > 0) nsrc[0] = x_src(id0);
+                if constexpr (cnt > 1) nsrc[1] = x_src(id1);
+                if constexpr (cnt > 2) nsrc[2] = x_src(id2);
+                if constexpr (XB2) nsrc[3] = x_src(10);
+                if constexpr (XA4) nsrc[4] = x_src(4);
+                if constexpr (kk == 1) wait_vm<(!MB ? 0 : (AHERE ? 3 : 2))>();      // everything but this K-tile's phase-0 instructions has landed
+                G8_SBAR();
+                __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+                for (int i = 0; i < NMF; ++i) {
+                    const int mi = i / TN, ni = i % TN;
+                    acc[mi][ni] = mfma16(bf[ni], af[mi], acc[mi][ni]);
+                    if constexpr (cnt > 0) { if (i == GP - 1) x_fire(id0, nsrc[0]); }
+                    if constexpr (cnt > 1) { if (i == 2 * GP - 1) x_fire(id1, nsrc[1]); }
+                    if constexpr (cnt > 2) { if (i == 3 * GP - 1) x_fire(id2, nsrc[2]); }
+                }
+                if constexpr (cnt > 0) {
+                    if constexpr (cnt > 0) { __builtin_amdgcn_sched_group_barrier(0x008, GP, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
+                    if constexpr (cnt > 1) { __builtin_amdgcn_sched_group_barrier(0x008, GP, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
+                    if constexpr (cnt > 2) { __builtin_amdgcn_sched_group_barrier(0x008, GP, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); }
+                    __builtin_amdgcn_sched_group_barrier(0x008, NMF - cnt * GP, 0);
+                }
+                if constexpr (XB2) { if (has_b2) x_fire(10, nsrc[3]); }
+                if constexpr (XA4) { if (has_a4) x_fire(4, nsrc[4]); }
+                __builtin_amdgcn_s_setprio(0);
+                if constexpr (kk == 1) {
+                    if constexpr (MB) ++xb_kt;
+                    if constexpr (XA4) xa_advance();
+                }
+                G8_SBAR();
+            };
+            phase(std::integral_constant<int, 0>{});
+            phase(std::integral_constant<int, 1>{});
+            xb_rd = (xb_rd == 2) ? 0 : xb_rd + 1;
+            xb_is = (xb_is == 2) ? 0 : xb_is + 1;
+            if constexpr (KX == 2) { xa_rd ^= 1; xa_is ^= 1; }
+        };
+        const int nsup = nkt / 3;
+        for (int s = 0; s + 1 < nsup; ++s) {
+            xtile(std::integral_constant<int, 0>{}, std::true_type{});
+            xtile(std::integral_constant<int, 1>{}, std::true_type{});
+            xtile(std::integral_constant<int, 2>{}, std::true_type{});
+        }
+        xtile(std::integral_constant<int, 0>{}, std::false_type{});
+        xtile(std::integral_constant<int, 1>{}, std::false_type{});
+        xtile(std::integral_constant<int, 2>{}, std::false_type{});
+    }
+    // ---- prologue: K-tiles 0 and 1 in flight, K-tile 0 landed
+    if constexpr (!KXR) {
+        issue_all(0);
+        if (nkt > 1) {
+            issue_all(1);
+            if (C::NI0 == C::NI1 || grp == 0) wait_vm<C::NI0>();
+            else wait_vm<C::NI1>();
+        } else {
+            wait_vm<0>();
+        }
+        G8_SBAR();
+        if (grp == 1) G8_SBAR();           // stagger: group 1 runs one barrier interval behind group 0
+    }
+
+    if constexpr ((DBG & 1) && !KXR) ts1 = __builtin_readcyclecounter();
     // Loop invariants at the top of iteration t: K-tile t has landed (every wave waited for its share one phase ago and
     // two barriers have passed since), K-tile t+1 is in flight, stage (t+2) % 3 is free.
     // Phase kk (the two 32-wide k halves of the K-tile): [read 4 A + TN B fragments] barrier [4*TN MFMAs, with the LDS-DMA
@@ -494,7 +706,9 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
         st_is = (st_is == 2) ? 0 : st_is + 1;
     };
     int t = 0;
-    if constexpr (S3) {
+    if constexpr (KXR) {
+        // (the kx-reuse loop has run above)
+    } else if constexpr (S3) {
         for (; t + 2 < nkt; ++t) ktile3(std::true_type{});
         for (; t < nkt; ++t) ktile3(std::false_type{});
     } else {
@@ -689,6 +903,14 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
 }
 
 #define g8_dbg gl_opt(32)   // measurement instantiation selector (process default 0)
+#define g8_kxr gl_opt(54)   // kx-reuse conv loop: 0 = never, 1 = wherever eligible, 2 (default) = kxr_default()
+
+std::atomic<uint64_t> g8_kxr_launches{0};    // launches served by the kx-reuse loop (tests read it: gl_debug_read(11))
+
+// Default rule of key 54 = 2: the shapes on which the kx-reuse loop measured faster than the plain loop by more than the spread of the
+// repeated runs.  Every eligible stride-1 shape of a config-2 forward (2B = 8; 64x64 .. 16x16 maps, unsplit and in split-K slices of 45 .. 135
+// K-tiles) and of the VAE decode (64x64 .. 512x512 maps, 128-wide tiles) did, by 9-21 % (profiles/kxreuse_shapes.txt): no shape is excluded.
+static bool kxr_default(const gl_gemm_args&, const ConvGeom&, int /*bn*/, int /*zs*/) { return true; }
 
 constexpr int G8_MAX_DEVICES = 64;
 const half_t* g8_zero_page[G8_MAX_DEVICES] = {};   // per DEVICE: address of this translation unit's zero page on that device (gl8_init; __device__ symbols are per device)
@@ -703,6 +925,23 @@ int launch8(const gl_gemm_args& g, const ConvGeom& cg_in, int zs, int kper, int 
     const int mt = gl_cdiv(g.M, BM), nt = gl_cdiv(g.N, BN);
     dim3 grid(mt * nt, 1, zs);
     bool done = false;
+    // kx-reuse loop (key 54: 0 = never, 1 = wherever eligible, 2 = default rule): stride-1 plain fp16 convs on 256-row tiles whose slices
+    // are whole (channel block) runs of nine K-tiles in (channel block, tap) order
+    if constexpr (CONV && !S3 && BM == 256) {
+        const bool eligible = cg.stride == 1 && !cg.ups && cg.shift == 0 && g.kwrap == 0 && cg.cwrap == 0 && !(order_m & 2) && kper > 0 &&
+                              (kper % 9) == 0 && cg.Hin == cg.Hout && cg.Win == cg.Wout && g.K == 9 * cg.Cin && g.a2 == nullptr;
+        if (eligible && (g8_kxr == 1 || (g8_kxr == 2 && kxr_default(g, cg, BN, zs)))) {
+            void (*k)(gl_gemm_args, ConvGeom, int, int, int) = gemm8_kernel<BM, BN, true, 0, false, true>;
+            if constexpr (BN == 160) {
+                if (g8_dbg == 1) k = gemm8_kernel<BM, BN, true, 1, false, true>;
+                if (g8_dbg == 3) k = gemm8_kernel<BM, BN, true, 3, false, true>;
+            }
+            k<<<grid, dim3(512), G8X<BN>::LDS, st>>>(g, cg, zs, kper, order_m);
+            GL_CHECK_LAUNCH();
+            g8_kxr_launches.fetch_add(1, std::memory_order_relaxed);
+            return 0;
+        }
+    }
     if constexpr (S3) {
         gemm8_kernel<BM, BN, CONV, 0, true><<<grid, dim3(512), G8<BM, BN>::LDS, st>>>(g, cg, zs, kper, order_m);
         done = true;
@@ -724,6 +963,13 @@ template <int BM, int BN, bool CONV>
 int set_attr8() {
     hipError_t e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, G8<BM, BN>::LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, CONV, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8<BM, BN>::LDS);
+    if constexpr (CONV && BM == 256) {
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, true, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8X<BN>::LDS);
+        if constexpr (BN == 160) {
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, true, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8X<BN>::LDS);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, true, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8X<BN>::LDS);
+        }
+    }
     if constexpr (BN == 160 && BM == 256) {
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, CONV, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, G8<BM, BN>::LDS);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, CONV, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, G8<BM, BN>::LDS);
@@ -780,6 +1026,8 @@ int gl8_init(void) {
     if ((e = set_attr8<128, 128, true>())) return e;
     return 0;
 }
+
+uint64_t gl8_kxr_launch_count(void) { return g8_kxr_launches.load(std::memory_order_relaxed); }
 
 // measurement hooks (tools/g8_probe.py): option 32 selects the timestamping instantiation of the 160-wide kernel
 int gl8_read_stamps(void* dst, int64_t bytes) {

@@ -973,9 +973,9 @@ int gl_attn_read_launch_counts(void* dst, int64_t bytes);       // attention.hip
 extern "C" int gl_debug_read(int what, void* dst, int64_t bytes) {
     if (what == 8) return gl8_read_stamps(dst, bytes);
     if (what == 10) return gl_attn_read_launch_counts(dst, bytes);
-    if (what == 9) {
+    if (what == 9 || what == 11) {
         if (!dst || bytes < (int64_t)sizeof(uint64_t)) return GL_ERR_BAD_ARG;
-        const uint64_t n = g8_launches.load(std::memory_order_relaxed);
+        const uint64_t n = what == 9 ? g8_launches.load(std::memory_order_relaxed) : gl8_kxr_launch_count();
         memcpy(dst, &n, sizeof n);
         return 0;
     }

@@ -134,3 +134,4 @@ int gl8_supported(const gl_gemm_args& g, bool conv, int* bn_out);
 int gl8_launch(const gl_gemm_args& g, const ConvGeom& cg, bool conv, int bm, int bn, int zs, int kper, int order_m, hipStream_t st, bool s3 = false);
 int gl8_init(void);
 int gl8_read_stamps(void* dst, int64_t bytes);
+uint64_t gl8_kxr_launch_count(void);       // launches served by the kx-reuse conv loop (gl_debug_read(11))

@@ -641,6 +641,14 @@ def gemm8_launch_count() -> int:
     return int(n.value)
 
 
+def kxreuse_launch_count() -> int:
+    """gl_conv3x3 calls this process has served with the kx-reuse loop of the 8-wave kernel (gl_debug_read(11), option key 54)."""
+    import ctypes
+    n = ctypes.c_uint64(0)
+    check(_lib.lib().gl_debug_read(11, ctypes.byref(n), 8), "gl_debug_read")
+    return int(n.value)
+
+
 ATTN_FORMS = ("split_pipe", "split_8w", "split_4w_dbuf", "split_4w_single", "f16_8w_pre0", "f16_8w_pre1", "f16_8w_pre2", "f16_4w_pre0",
               "f16_4w_pre1", "f16_4w_pre2")
 

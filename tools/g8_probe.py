@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B probe of the 8-wave deep-pipelined GEMM / conv kernel (csrc/gemm8.hip) against the 4-wave kernels (GPU box).
 
-    python tools/g8_probe.py [check] [time] [race]
+    python tools/g8_probe.py [check] [time] [race] [stamps] [kxr]
 
 check : every epilogue / operand form through gl_gemm / gl_conv3x3 with option 30 = 2 (8-wave kernel wherever it applies)
         against option 30 = 0 (the parity-tested 4-wave kernels) on the same inputs; the two differ only in fp32 summation
@@ -9,6 +9,10 @@ check : every epilogue / operand form through gl_gemm / gl_conv3x3 with option 3
 time  : per-shape time of both, interleaved in one process (median of rounds).
 race  : repeats each 8-wave launch on fresh data and requires bitwise-identical results across repeats of the same data
         (a staged buffer read before its DMA landed shows up as run-to-run differences).
+kxr   : the stride-1 conv shapes of a config-2 forward (2B = 8) and of the VAE decode (B = 4) under the default dispatch with the kx-reuse
+        loop off and on (option 54 = 0 / 1), interleaved in one process: median and spread of G8_ROUNDS (5) rounds of G8_ITERS (20) launches,
+        whether the launch was eligible (served by the kx-reuse loop) and whether both give the same bits.  G8_KXR=0/1 pins option 54 for
+        the other modes (stamps, spin, race).
 """
 import math
 import os
@@ -124,6 +128,15 @@ def cases():
             g(f"gemm {M}x320x320 bias", M, 320, 320)
             g(f"gemm {M}x320x320 res f32+o16", M, 320, 320, "res", f32=True, out16=True)
         return c
+    if os.environ.get("G8_KXR_SHAPES"):
+        for side, pairs in ((64, ((320, 320), (640, 320), (960, 320))), (32, ((320, 640), (640, 640), (960, 640), (1280, 640), (1920, 640))),
+                            (16, ((640, 1280), (1280, 1280), (1920, 1280), (2560, 1280))), (8, ((1280, 1280), (2560, 1280)))):
+            for cin, cout in pairs:
+                v(f"conv 8x{side}^2 {cin}->{cout}", 8, side, cin, cout)
+        v("conv 8x64^2 320->320 res f32", 8, 64, 320, 320, epi="res", f32=True)
+        for side, cin, cout in ((64, 512, 512), (128, 512, 512), (256, 512, 256), (256, 256, 256), (512, 256, 128), (512, 128, 128)):
+            v(f"conv 4x{side}^2 {cin}->{cout} (VAE)", 4, side, cin, cout)
+        return c
     if os.environ.get("G8_QUICK"):
         g("gemm 4096x320x320 bias", 4096, 320, 320)
         v("conv 2x32^2 320->320", 2, 32, 320, 320)
@@ -192,6 +205,37 @@ def main():
     if only:
         cs = [c for c in cs if only in c[0]]
     allok = True
+    if os.environ.get("G8_KXR"):
+        ops.set_option(54, int(os.environ["G8_KXR"]))
+    if "kxr" in which:
+        iters, rounds = int(os.environ.get("G8_ITERS", "20")), int(os.environ.get("G8_ROUNDS", "5"))
+        print(f"== kx-reuse loop, option 54 = 0 | 1 (default dispatch otherwise): us median [min..max] of {rounds} rounds x {iters} launches")
+        for name, alloc, launch, fl in cs:
+            o0, o1 = alloc(), alloc()
+            ops.set_option(54, 0)
+            launch(o0)
+            n = ops.kxreuse_launch_count()
+            ops.set_option(54, 1)
+            launch(o1)
+            torch.cuda.synchronize()
+            served = ops.kxreuse_launch_count() - n
+            same = all(torch.equal(a, b) for a, b in zip(o0, o1) if a is not None)
+            allok &= same
+            if not served:
+                print(f"  {name:40s} not eligible under the default plan")
+                continue
+            ts = [[], []]
+            for _ in range(rounds):
+                for k in (0, 1):
+                    ops.set_option(54, k)
+                    ts[k].append(timeit(lambda: launch(o0), iters) * 1e6)
+            med = [sorted(v)[len(v) // 2] for v in ts]
+            spread = max(max(v) - min(v) for v in ts)
+            d = med[0] - med[1]
+            verdict = "win" if d > spread else ("loss" if -d > spread else "tie")
+            print(f"  {name:40s} {med[0]:8.1f} [{min(ts[0]):.1f}..{max(ts[0]):.1f}] | {med[1]:8.1f} [{min(ts[1]):.1f}..{max(ts[1]):.1f}]  "
+                  f"{100 * d / med[0]:+5.1f} %  spread {spread:.1f}  {verdict}  {'same bits' if same else 'BITS DIFFER'}")
+        ops.set_option(54, 2)
     if "spin" in which:         # for rocprofv3: 20 launches of each case with the default dispatch
         for name, alloc, launch, _ in cs:
             o = alloc()

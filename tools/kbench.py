@@ -177,7 +177,8 @@ def class_summary(iters=8, peak_tflops=2500.0, strict=False):
 def main():
     which = set(sys.argv[1:]) or {"gemm", "conv", "attn", "norm"}
     init_device()
-    # KB_OPTS="22=1,13=2": gl_set_option knobs for A/B runs (see include/gligen_hip.h)
+    # KB_OPTS="22=1,13=2": gl_set_option knobs for A/B runs (see include/gligen_hip.h); KB_OPTS="54=0" / "54=1" times the conv shapes
+    # with the kx-reuse loop of the 8-wave kernel off / on (tools/g8_probe.py kxr does both in one process)
     for kv in filter(None, os.environ.get("KB_OPTS", "").split(",")):
         k, v = kv.split("=")
         ops.set_option(int(k), int(v))
