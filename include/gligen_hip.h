@@ -131,6 +131,12 @@ int gl_sizeof_ff_args(void);
  *   stride 1            : ResBlock convs openaimodel.py:158,184; conv_in :299; out conv :388
  *   stride 2            : Downsample.op openaimodel.py:105-107,:114
  *   upsample2x != 0     : F.interpolate(nearest, x2) + conv, openaimodel.py:82-84 (input is Hout/2 x Wout/2)
+ *   upsample2x == 2     : the same layer with FOLDED weights: after nearest upsampling the nine taps of output pixel (2y + py, 2x + px) touch
+ *                         only the 2 x 2 source pixels (y + py - 1 + a, x + px - 1 + b), so per output parity it is a 2x2 conv on the source
+ *                         grid.  g.w is [4 Cout, 4 Cin]: rows (parity py * 2 + px, Cout), K = (64-channel block, tap a * 2 + b, channel), with
+ *                         Wf[py,px][:, :, a, b] = sum of W[:, :, ky, kx] over ky in S(py, a), kx in S(px, b); S(0,0) = {0}, S(0,1) = {1,2},
+ *                         S(1,0) = {0,1}, S(1,1) = {2}.  g.N stays Cout and must be the PACKED Cout (parity p's rows start at row p * g.N).  Needs stride 1, in_split 0, w_split 0 and a row-major output
+ *                         (GL_OUT_F16_ROWMAJOR or GL_OUT_F32_ROWMAJOR, with or without out2); GL_ERR_BAD_ARG otherwise.  8-wave kernel only.
  * Epilogue fields are those of gl_gemm (the `g` member; g.a/g.K/g.M are ignored and derived here).
  */
 typedef struct gl_conv_args {
@@ -138,7 +144,7 @@ typedef struct gl_conv_args {
     int32_t B, Hin, Win, Cin;
     int32_t Hout, Wout;
     int32_t stride;        /* 1 or 2 */
-    int32_t upsample2x;    /* 0 or 1 (stride must be 1) */
+    int32_t upsample2x;    /* 0, 1, or 2 = folded weights (stride must be 1) */
     gl_gemm_args g;        /* w, bias, N, epi, out_mode, out, ldc, res, ldres, rowbias..., hw */
     /* split-fp16 operands (ABI 14; strict mode).  in_split = 2: the input pixels are [hi | lo] rows of 2 Cin channels
      * (hi = fp16(x), lo = fp16(x - hi), e.g. gl_groupnorm_ex's out / out_lo with ldo = 2 Cin) and the K walk visits both halves against
@@ -676,8 +682,18 @@ int gl_sizeof_gn_args(void);
  * 256-row tiles of the plain fp16 loop, stride 1, no upsample, no pad01 window, no split input, (channel block, tap) K order (key 33 = 0),
  * K slices of whole channel blocks (a multiple of 9 K-tiles); every other launch takes the plain loop whatever the value.  0 = never,
  * 1 = every eligible launch, 2 (default) = the eligible shapes on which it measured faster (profiles/kxreuse_shapes.txt).  Same bits as the
- * plain loop: same MFMA sequence on the same operand values. */
+ * plain loop: same MFMA sequence on the same operand values.
+ * key 55 = upsample convs (nearest-2x + 3x3) as four folded 2x2 convs, one per output parity, 4/9 of the matrix work (csrc/gemm8.hip UPF): 1
+ * = the weight table of a handle holds [4 Cout, 4 Cin] folded kernels for every upsample conv (weights.pack_conv_upfold; a host that
+ * fills the table by gl_weight_at has to fold) and the handle launches gl_conv3x3 with upsample2x = 2; 0 = [Cout, 9 Cin] rows and
+ * upsample2x = 1; 2 (default) = for gl_create / gl_vae_create the same as 0 -- a host that creates a handle without knowing the fold gets the table
+ * it always got -- while the Python packers (weights.pack_state_dict, vae.VAEDecoder) fold the configs whose up convs measured faster folded
+ * (weights.fold_up_rule: profiles/upfold_shapes.txt) and create their handle under 1.  Read ONCE, when the handle is created (gl_create, gl_vae_create), and kept in it: a later change affects only handles created
+ * afterwards, so one process can hold a folded and an unfolded engine.  A split_weights handle never folds.  Results differ from the 9-tap
+ * form by the rounding of the summed weights (same distance to the exact conv). */
 int gl_set_option(int key, int value);
+/* the process default of `key` as gl_set_option left it (GL_ERR_BAD_ARG for a key out of range) */
+int gl_get_option(int key);
 /* gl_set_option writes the PROCESS defaults (op-level calls and every handle without an override see them).  A handle can
  * override individual keys for itself: while one of ITS entry points (gl_set_conditioning / gl_unet_forward / gl_plms_step,
  * gl_vae_decode) runs, lookups on that thread see the defaults with the handle's overrides applied, so two hosts in one
@@ -694,7 +710,9 @@ int gl_vae_set_option(gl_vae* v, int key, int value);
  * kernel, [1] 8-wave split-fp16 kernel, [2] 4-wave split-fp16 kernel, double-buffered, [3] 4-wave split-fp16 kernel, single buffer set,
  * [4..6] single-fp16 8-wave kernel with the running max on the FMA path / in the accumulator init / in the padding column (PRE 0 / 1 / 2),
  * [7..9] single-fp16 4-wave kernel, PRE 0 / 1 / 2 (tests/test_gpu_attention_layouts.py asserts which form took each launch);
- * what = 11 copies one uint64: the gl_conv3x3 calls this process has served with the kx-reuse loop of the 8-wave kernel (key 54). */
+ * what = 11 copies one uint64: the gl_conv3x3 calls this process has served with the kx-reuse loop of the 8-wave kernel (key 54);
+ * what = 12 copies one uint64: the gl_conv3x3 calls served as folded upsample convs (upsample2x = 2); those always run on the 8-wave
+ * kernel and are NOT part of what = 9, which counts the launches the dispatcher chose that kernel for. */
 int gl_debug_read(int what, void* dst, int64_t bytes);
 /* one-time per-process setup (raises dynamic-LDS limits of the tiled kernels); idempotent */
 int gl_init(void);

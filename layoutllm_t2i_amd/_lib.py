@@ -211,6 +211,7 @@ PROTOTYPES = {
     "gl_resample_h_u8": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
     "gl_resample_v_norm": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "gl_set_option": (i32, [i32, i32]),
+    "gl_get_option": (i32, [i32]),
     "gl_set_handle_option": (i32, [vp, i32, i32]),
     "gl_clear_handle_options": (i32, [vp]),
     "gl_vae_set_option": (i32, [vp, i32, i32]),
@@ -312,16 +313,60 @@ def unet_config_c(cfg) -> UNetConfigC:
     return c
 
 
-def create_engine(cfg) -> int:
-    """gl_create: returns the opaque handle (an int address).  Needs no GPU."""
+OPT_FOLD_UP = 55      # upsample convs as four folded 2x2 convs: read when a handle is created (include/gligen_hip.h)
+
+
+def fold_up_option() -> int:
+    """The process value of option key 55: 0 = never fold, 1 = fold, 2 (default) = handles keep 9-tap rows, the packers fold by their rule."""
+    return int(lib().gl_get_option(OPT_FOLD_UP))
+
+
+def fold_up_default() -> bool:
+    """What a handle created now would use: gl_create / gl_vae_create fold exactly under key 55 = 1."""
+    return fold_up_option() == 1
+
+
+def resolve_fold_up(fold_up, rule: bool) -> bool:
+    """A packer's ``fold_up`` argument -> bool: given values stand; None follows option key 55, whose default (2) means ``rule``,
+    the packer's measured per-config rule."""
+    if fold_up is not None:
+        return bool(fold_up)
+    v = fold_up_option()
+    return bool(rule) if v == 2 else v == 1
+
+
+class _fold_up_scope:
+    """Creates handles under a given value of key 55 (None: the current one) and puts the process value back.  NOT thread-safe with respect to
+    key 55: between enter and exit the PROCESS value is the requested one (another thread creating a handle in that window gets it too) and
+    the option generation moves twice, so every engine re-captures its graphs on its next forward.  Create handles from one thread."""
+
+    def __init__(self, fold_up):
+        self.want = None if fold_up is None else int(bool(fold_up))
+
+    def __enter__(self):
+        self.old = lib().gl_get_option(OPT_FOLD_UP)
+        self.changed = self.want is not None and self.want != self.old
+        if self.changed:
+            check(lib().gl_set_option(OPT_FOLD_UP, self.want), "gl_set_option")
+
+    def __exit__(self, *exc):
+        if self.changed:
+            check(lib().gl_set_option(OPT_FOLD_UP, self.old), "gl_set_option")
+
+
+def create_engine(cfg, fold_up=None) -> int:
+    """gl_create: returns the opaque handle (an int address).  Needs no GPU.  ``fold_up``: the value of option key 55 the handle is
+    created under (None = the process value)."""
     h = vp()
     cc = unet_config_c(cfg)
-    check(lib().gl_create(C.byref(cc), C.byref(h)), "gl_create")
+    with _fold_up_scope(fold_up):
+        check(lib().gl_create(C.byref(cc), C.byref(h)), "gl_create")
     return h.value
 
 
-def create_vae(cfg, encoder: bool = False) -> int:
-    """gl_vae_create (``encoder``: gl_vae_encoder_create) from an arch.VAEConfig: returns the opaque handle.  Needs no GPU."""
+def create_vae(cfg, encoder: bool = False, fold_up=None) -> int:
+    """gl_vae_create (``encoder``: gl_vae_encoder_create) from an arch.VAEConfig: returns the opaque handle.  Needs no GPU.
+    ``fold_up``: as for create_engine (the decoder's upsample convs)."""
     cc = VaeConfigC()
     cc.ch, cc.n_mult, cc.num_res_blocks, cc.z_channels, cc.out_ch = cfg.ch, len(cfg.ch_mult), cfg.num_res_blocks, cfg.z_channels, cfg.out_ch
     for i, m in enumerate(cfg.ch_mult):
@@ -331,7 +376,8 @@ def create_vae(cfg, encoder: bool = False) -> int:
     if encoder:
         check(lib().gl_vae_encoder_create(C.byref(cc), C.byref(h)), "gl_vae_encoder_create")
     else:
-        check(lib().gl_vae_create(C.byref(cc), C.byref(h)), "gl_vae_create")
+        with _fold_up_scope(fold_up):
+            check(lib().gl_vae_create(C.byref(cc), C.byref(h)), "gl_vae_create")
     return h.value
 
 

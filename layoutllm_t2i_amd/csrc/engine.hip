@@ -139,6 +139,7 @@ __global__ void rela_rects_kernel(const float* __restrict__ boxes, const float* 
 }  // namespace
 
 struct gl_engine {
+    bool fold_up = false;              // upsample convs stored as four folded 2x2 kernels [4 Cout, 4 Cin]: key 55 at gl_create, never on a split_weights handle
     bool strict_hoists_ok = false;     // the strict-mode conditioning hoists match the current conditioning ...
     int strict_hoists_w3 = -1;         // ... and were computed under this value of key 51
     gl_unet_config cfg;
@@ -329,7 +330,11 @@ void build_table(gl_engine* e) {
     int off = 0;
     for_all_layers(e, [&](LayerD& l) {
         const std::string& p = l.prefix;
-        if (l.kind == DOWN || l.kind == UP) {
+        if (l.kind == UP && e->fold_up) {
+            // nearest-2x + 3x3 as one 2x2 conv per output parity (weights.pack_conv_upfold): rows (parity, Cout), K = (channel block, tap, channel)
+            add_w(e, p + ".w", 0, {4 * (int64_t)l.cout, 4 * (int64_t)l.cin});
+            add_w(e, p + ".b", 1, {l.cout});
+        } else if (l.kind == DOWN || l.kind == UP) {
             add_conv3(e, p, l.cin, l.cout);
         } else if (l.kind == RES) {
             add_norm(e, p + ".in_layers.0", l.cin);
@@ -509,8 +514,10 @@ struct Run {
         a.in = in.p; a.B = B; a.Hin = Hin; a.Win = Win; a.Cin = Cin;
         a.Hout = o.ups ? 2 * Hin : (Hin + 2 - 3) / o.stride + 1;
         a.Wout = o.ups ? 2 * Win : (Win + 2 - 3) / o.stride + 1;
-        a.stride = o.stride; a.upsample2x = o.ups;
-        a.g.w = e->W(p + ".w"); a.g.bias = e->Wf(p + ".b"); a.g.N = (int)wi->shape[0];
+        // an upsample conv of a folded table ([4 Cout, 4 Cin] rows, gl_engine.fold_up) takes the folded form of the kernel
+        const bool folded = o.ups && wi->shape[1] == 4 * (int64_t)Cin;
+        a.stride = o.stride; a.upsample2x = folded ? 2 : o.ups;
+        a.g.w = e->W(p + ".w"); a.g.bias = e->Wf(p + ".b"); a.g.N = (int)(folded ? wi->shape[0] / 4 : wi->shape[0]);
         a.g.epi = o.epi; a.g.out_mode = out_mode; a.g.out = out; a.g.ldc = a.g.N; a.g.hw = o.nchw_hw;
         a.g.res = o.res.p; a.g.ldres = o.res.ld; a.g.res_f32 = o.res.f32;
         a.g.rowbias = o.rowbias.p; a.g.ld_rowbias = o.rowbias.ld; a.g.rows_per_sample = o.rowbias.rows_per_sample;
@@ -1101,6 +1108,7 @@ extern "C" int gl_create(const gl_unet_config* cfg, gl_engine** out) {
     if ((cfg->inpaint_mode != 0 && cfg->inpaint_mode != 1) || first_conv_in(*cfg) > CIN_PAD) return GL_ERR_UNSUPPORTED;
     gl_engine* e = new gl_engine();
     e->cfg = *cfg;
+    e->fold_up = gl_opt(55) == 1 && !cfg->split_weights;      // read ONCE: the table (and every rank's layout built from it) follows
     build_plan(e);
     build_table(e);
     *out = e;

@@ -127,7 +127,17 @@ __device__ unsigned long long g8_stamps[4 * 4096];
 //     phase-0 cluster of the next K-tile on -- the timing of a B stage, whose WAR argument above applies; RAW: the last A instructions go out
 //     in K-tile 3s+1 and are retired by every wave's counted wait in phase 1 of K-tile 3s+2, >= 1 barrier before K-tile 3s+3 reads them.
 //   The MFMA sequence per output element (channel block, ky, kx, k half) and every operand value are those of the loop above: same bits.
-template <int BM, int BN, bool CONV, int DBG = 0, bool S3 = false, bool KXR = false>
+//
+// UPF: the FOLDED nearest-2x-upsample + 3x3 conv (gl_conv_args.upsample2x == 2; plain fp16 loop).  After nearest upsampling the nine taps of
+// output pixel (2y + py, 2x + px) touch only the 2 x 2 source pixels (y + py - 1 + a, x + px - 1 + b), a, b in {0, 1}: per output parity
+// (py, px) the layer is a 2x2 conv on the SOURCE grid with weights summed at pack time (weights.pack_conv_upfold), K = 4 Cin instead of 9 Cin.
+//   M    four segments of Ms = B * Hin * Win source pixels, one per parity; a tile never mixes parities (grid: 4 * cdiv(Ms, BM) row tiles,
+//        parity outermost), rows past Ms inside a tile are masked; the tile's parity selects its Cout weight rows out of [4 Cout, 4 Cin];
+//   K    (64-channel block, tap a * 2 + b, channel): four K-tiles per channel block; per row the source pixel's address and a 4-bit validity
+//        set, the tap's offset ((py - 1 + a) * Win + (px - 1 + b)) * Cin is block-uniform; masked taps read the zero page (v_bfi select);
+//   out  tile row (b, y, x) is output row (b * 2 Hin + 2 y + py) * 2 Win + 2 x + px wherever a row index turns into an address (bias / row
+//        bias / residual loads, the stores incl. out2, the split-K partial store: the workspace is in output-row order for the reduction).
+template <int BM, int BN, bool CONV, int DBG = 0, bool S3 = false, bool KXR = false, bool UPF = false>
 __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom cg, int splitk, int kt_per_split, int order_flags) {
     using C = G8<BM, BN>;
     constexpr int KT = S3 ? 32 : 64;                   // k columns of the product one ring stage covers
@@ -154,11 +164,17 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
         const int xcd = bid & 7, local = bid >> 3;
         tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
     }
-    const int mt_ = (M + C::BM - 1) / C::BM;
+    static_assert(!UPF || (CONV && !S3 && !KXR), "folded upsample conv: plain fp16 conv loop");
+    const int Ms = UPF ? cg.B * cg.Hin * cg.Win : 0;       // UPF: source pixels = rows per parity segment
+    const int mtp = UPF ? (Ms + C::BM - 1) / C::BM : 0;
+    const int mt_ = UPF ? 4 * mtp : (M + C::BM - 1) / C::BM;
+    const int Mrows = UPF ? Ms : M;                        // bound of the tile's row index m0 + r
     const int order_m = order_flags & 1;
-    const bool tap_major = CONV && (order_flags & 2);      // conv K order: (tap, channel block) instead of (channel block, tap)
+    const bool tap_major = CONV && !UPF && (order_flags & 2);      // conv K order: (tap, channel block) instead of (channel block, tap)
     const int tmi = order_m ? tile % mt_ : tile / nt;
-    const int m0 = tmi * C::BM;
+    const int par = UPF ? tmi / mtp : 0;                   // UPF: output parity py * 2 + px of this tile
+    const int py = par >> 1, px = par & 1;
+    const int m0 = (UPF ? tmi - par * mtp : tmi) * C::BM;
     const int n0 = (order_m ? tile / mt_ : tile - tmi * nt) * BN;
     const int kt_begin = blockIdx.z * kt_per_split;
     const int kt_end = min(K / KT, kt_begin + kt_per_split);
@@ -192,9 +208,29 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
         const int r = trow0 + srow;
         const int gc = chunk_off(sslot ^ ((r >> 1) & 7), a_lo);
         const int m = m0 + r;
-        const bool rowok = m < M;
+        const bool rowok = m < Mrows;
         aptr[u] = zsrc; cmask[u] = 0u;
-        if constexpr (CONV) {
+        if constexpr (UPF) {
+            if (rowok) {
+                // (y, x) of the SOURCE pixel m; tap (a, b) reads source (y + py - 1 + a, x + px - 1 + b): 4-bit validity set, bit a * 2 + b
+                const int hw = cg.Hin * cg.Win;
+                int y, x;
+                if (((cg.Win & (cg.Win - 1)) | (hw & (hw - 1))) == 0) {
+                    const int rr = m & (hw - 1);
+                    y = rr >> __builtin_ctz(cg.Win);
+                    x = rr & (cg.Win - 1);
+                } else {
+                    const int rr = m % hw;
+                    y = rr / cg.Win;
+                    x = rr - y * cg.Win;
+                }
+                const int y0 = y + py - 1, x0 = x + px - 1;
+                const unsigned rb = (y0 >= 0 ? 1u : 0u) | (y0 + 1 < cg.Hin ? 2u : 0u);
+                const unsigned cb = (x0 >= 0 ? 1u : 0u) | (x0 + 1 < cg.Win ? 2u : 0u);
+                cmask[u] = ((rb & 1u) ? cb : 0u) | ((rb & 2u) ? (cb << 2) : 0u);
+                aptr[u] = cg.in + (size_t)m * cg.Cin + gc;
+            }
+        } else if constexpr (CONV) {
             if (rowok) {
                 // (sample, oy, ox) of the output pixel: shifts when the map sides are powers of two (every UNet level), else divisions
                 int b, oy, ox;
@@ -244,15 +280,15 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
         const int gc = chunk_off(sslot ^ ((r >> 1) & 7), p.kwrap);
         const int n = n0 + r;
         const bool ok = (j < nb) && (r < BN) && (n < N);
-        bptr[j] = ok ? (Wg + (size_t)n * p.ldw + gc) : zsrc;       // + the K-tile's offset at issue time (gl_conv3x3 sets ldw too)
+        bptr[j] = ok ? (Wg + (size_t)(UPF ? par * N + n : n) * p.ldw + gc) : zsrc;       // + the K-tile's offset at issue time (gl_conv3x3 sets ldw too)
         if (ok) bmask |= 1u << j;
     }
 
     // conv: (channel block, tap) of the K-tile the next issue refers to
-    const int ncblk = CONV ? K / 576 : 1;          // channel blocks the K walk visits (a split-fp16 input walks [hi | lo (| hi)])
+    const int ncblk = UPF ? K / 256 : (CONV ? K / 576 : 1);          // channel blocks the K walk visits (a split-fp16 input walks [hi | lo (| hi)])
     // K-tile visiting order as (outer, inner) counters: inner = tap (9) with channel blocks outside, or inner = channel block
     // with taps outside (tap-major: consecutive K-tiles then touch DIFFERENT 128-byte lines of the input pixels)
-    const int in_lim = tap_major ? ncblk : 9;
+    const int in_lim = UPF ? 4 : (tap_major ? ncblk : 9);
     int is_out = 0, is_in = 0;
     int is_cblk = 0, is_tap = 0;           // of the K-tile being issued (set by issue_begin)
     if constexpr (CONV) {
@@ -277,6 +313,11 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
             is_boff = ((is_cblk * 9 + is_tap) << 6) + ((is_kt & 1) << 5);
         } else if constexpr (S3) {
             is_boff = is_kt << 5;
+        } else if constexpr (UPF) {
+            is_tap = is_in;
+            is_cblk = is_out;
+            is_off = ((py - 1 + (is_tap >> 1)) * cg.Win + (px - 1 + (is_tap & 1))) * cg.Cin + (is_cblk << 6);
+            is_boff = (is_cblk * 4 + is_tap) << 6;
         } else if constexpr (CONV) {
             is_tap = tap_major ? is_out : is_in;
             is_cblk = tap_major ? is_in : is_out;
@@ -310,7 +351,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
             if constexpr (CONV) {
                 // masked taps (the halo) read the zero page: branch-free 64-bit select (v_bfi), no exec games
                 int off = is_off;
-                if (cg.ups) {        // wave-uniform; this runs in the read section, outside the MFMA stream
+                if (!UPF && cg.ups) {        // wave-uniform; this runs in the read section, outside the MFMA stream
                     const int ry = (is_ky - 1 + (int)((cmask[u] >> 9) & 1u)) >> 1, rx = (is_kx - 1 + (int)((cmask[u] >> 10) & 1u)) >> 1;
                     off = (ry * cg.Win + rx) * cg.Cin + (is_acb << (S3 ? 5 : 6));
                 }
@@ -740,6 +781,19 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
     constexpr int NQ = ITEMS / 64;
     const bool vt_wave = p.vt != nullptr && nbase >= p.vt_col0;
     const bool generic = splitk == 1 && !vt_wave && epi != GL_EPI_GEGLU;
+    // UPF: tile row m (source pixel of this tile's parity) -> row of the output matrix
+    auto orow = [&](const int m) __attribute__((always_inline)) -> int {
+        if constexpr (UPF) {
+            const int hw = cg.Hin * cg.Win;
+            const int b = m / hw;
+            const int rr = m - b * hw;
+            const int y = rr / cg.Win;
+            const int x = rr - y * cg.Win;
+            return (b * cg.Hout + 2 * y + py) * cg.Wout + 2 * x + px;
+        } else {
+            return m;
+        }
+    };
     Fin8Aux aux[MH][NQ];
     if (generic) {
 #pragma unroll
@@ -749,7 +803,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
                 const int idx = lane + 64 * q;
                 const int r = idx / CG8, c = (idx - r * CG8) * 8;
                 const int m = m0 + (BM / 4) * wm + 32 * h + r, n = nbase + c;
-                if (m < M && n < N) fin8_load(p, m, n, aux[h][q]);
+                if (m < Mrows && n < N) fin8_load(p, orow(m), n, aux[h][q]);
             }
     }
     float vt_bias[2] = {0.0f, 0.0f};
@@ -793,8 +847,8 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
                 const int idx = lane + 64 * q;
                 const int r = idx / CG8, c = (idx - r * CG8) * 8;
                 const int m = mbase + r, n = nbase + c;
-                if (m < M && n < N) {
-                    float* o = ws + (size_t)m * N + n;
+                if (m < Mrows && n < N) {
+                    float* o = ws + (size_t)orow(m) * N + n;
                     *reinterpret_cast<float4*>(o) = *reinterpret_cast<const float4*>(stage + r * EPS + c);
                     *reinterpret_cast<float4*>(o + 4) = *reinterpret_cast<const float4*>(stage + r * EPS + c + 4);
                 }
@@ -883,11 +937,11 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
                 const int idx = lane + 64 * q;
                 const int r = idx / CG8, c = (idx - r * CG8) * 8;
                 const int m = mbase + r, n = nbase + c;
-                if (m < M && n < N) {
+                if (m < Mrows && n < N) {
                     const float4 a0 = *reinterpret_cast<const float4*>(stage + r * EPS + c);
                     const float4 a1 = *reinterpret_cast<const float4*>(stage + r * EPS + c + 4);
                     float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                    fin8_store(p, gate, m, n, v, aux[h][q]);
+                    fin8_store(p, gate, orow(m), n, v, aux[h][q]);
                 }
             }
         }
@@ -906,6 +960,7 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(gl_gemm_args p, ConvGeom 
 #define g8_kxr gl_opt(54)   // kx-reuse conv loop: 0 = never, 1 = wherever eligible, 2 (default) = kxr_default()
 
 std::atomic<uint64_t> g8_kxr_launches{0};    // launches served by the kx-reuse loop (tests read it: gl_debug_read(11))
+std::atomic<uint64_t> g8_upf_launches{0};    // launches served by the folded upsample conv (gl_debug_read(12))
 
 // Default rule of key 54 = 2: the shapes on which the kx-reuse loop measured faster than the plain loop by more than the spread of the
 // repeated runs.  Every eligible stride-1 shape of a config-2 forward (2B = 8; 64x64 .. 16x16 maps, unsplit and in split-K slices of 45 .. 135
@@ -925,6 +980,18 @@ int launch8(const gl_gemm_args& g, const ConvGeom& cg_in, int zs, int kper, int 
     const int mt = gl_cdiv(g.M, BM), nt = gl_cdiv(g.N, BN);
     dim3 grid(mt * nt, 1, zs);
     bool done = false;
+    if (cg.ups == 2) {
+        // folded upsample conv (UPF): four parity segments of B * Hin * Win rows each
+        if constexpr (CONV && !S3) {
+            grid.x = 4 * gl_cdiv(cg.B * cg.Hin * cg.Win, BM) * nt;
+            gemm8_kernel<BM, BN, true, 0, false, false, true><<<grid, dim3(512), G8<BM, BN>::LDS, st>>>(g, cg, zs, kper, order_m);
+            GL_CHECK_LAUNCH();
+            g8_upf_launches.fetch_add(1, std::memory_order_relaxed);
+            return 0;
+        } else {
+            return GL_ERR_UNSUPPORTED;
+        }
+    }
     // kx-reuse loop (key 54: 0 = never, 1 = wherever eligible, 2 = default rule): stride-1 plain fp16 convs on 256-row tiles whose slices
     // are whole (channel block) runs of nine K-tiles in (channel block, tap) order
     if constexpr (CONV && !S3 && BM == 256) {
@@ -963,6 +1030,9 @@ template <int BM, int BN, bool CONV>
 int set_attr8() {
     hipError_t e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, G8<BM, BN>::LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, CONV, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8<BM, BN>::LDS);
+    if constexpr (CONV) {
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, true, 0, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8<BM, BN>::LDS);
+    }
     if constexpr (CONV && BM == 256) {
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm8_kernel<BM, BN, true, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G8X<BN>::LDS);
         if constexpr (BN == 160) {
@@ -981,9 +1051,9 @@ int set_attr8() {
 
 // What the 8-wave kernel implements: row-major outputs, every epilogue (GEGLU only on the 128-wide tile, whose wave owns
 // whole [x | gate] pairs), the V^T tail when it starts on a wave's column range.
-int gl8_supported(const gl_gemm_args& g, bool conv, int* bn_out) {
+int gl8_supported(const gl_gemm_args& g, bool conv, int* bn_out, bool upfold) {
     if (g.out_mode == GL_OUT_F32_NCHW) return 0;
-    if ((g.K % 64) != 0 || (g.N % 8) != 0 || g.M < 256) return 0;
+    if ((g.K % 64) != 0 || (g.N % 8) != 0 || (g.M < 256 && !upfold)) return 0;     // (a folded upsample conv has no other kernel: any M)
     int bn = 128;
     if (g.epi != GL_EPI_GEGLU && (g.N % 160) == 0) bn = 160;
     if (g.vt != nullptr && (g.vt_col0 % (bn / 2)) != 0) {
@@ -1028,6 +1098,7 @@ int gl8_init(void) {
 }
 
 uint64_t gl8_kxr_launch_count(void) { return g8_kxr_launches.load(std::memory_order_relaxed); }
+uint64_t gl8_upf_launch_count(void) { return g8_upf_launches.load(std::memory_order_relaxed); }
 
 // measurement hooks (tools/g8_probe.py): option 32 selects the timestamping instantiation of the 160-wide kernel
 int gl8_read_stamps(void* dst, int64_t bytes) {

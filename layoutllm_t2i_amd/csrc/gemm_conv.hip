@@ -802,9 +802,13 @@ int dispatch(const gl_gemm_args& g, const ConvGeom& cg, hipStream_t st) {
         int bn_ = 0;
         if (!g_opt_g8 || !gl8_supported(g, CONV, &bn_)) return GL_ERR_UNSUPPORTED;
     }
-    if (g_opt_g8) {
+    // folded upsample conv (gl_conv_args.upsample2x == 2): the 8-wave kernel is the only one that knows the form, whatever key 30 says.  Its M
+    // is four parity segments of M / 4 source pixels and a tile never mixes parities: 4 * cdiv(M / 4, bm) row tiles under the same plan
+    const bool upf = CONV && cg.ups == 2;
+    auto mtiles = [&](const int bm_) { return upf ? 4 * gl_cdiv(g.M / 4, bm_) : gl_cdiv(g.M, bm_); };
+    if (g_opt_g8 || upf) {
         int bn = 0;
-        if (gl8_supported(g, CONV, &bn)) {
+        if (gl8_supported(g, CONV, &bn, upf)) {
             const int nk = g.K / 64;
             // One block per CU: when the 256-row grid underfills the chip (32x32 levels and below), K is cut into slices up to ONE
             // round of blocks (256), never below g_opt_g8_minkt K-tiles per slice (prologue + epilogue cost ~4 K-tiles of time).
@@ -819,7 +823,7 @@ int dispatch(const gl_gemm_args& g, const ConvGeom& cg, hipStream_t st) {
                 return sk;
             };
             int bm = 256;
-            int tiles = gl_cdiv(g.M, 256) * gl_cdiv(g.N, bn);
+            int tiles = mtiles(256) * gl_cdiv(g.N, bn);
             int splitk = plan_split(tiles);
             // Half-height (128-row) tiles where the 256-row grid covers at most half the chip (32x32 maps and below at 2B = 8): twice the
             // blocks, so half the K slices (none at 32x32) and a smaller or no reduction.  The 128-row main loop issues the same B-side
@@ -831,7 +835,7 @@ int dispatch(const gl_gemm_args& g, const ConvGeom& cg, hipStream_t st) {
                 const bool want = CONV ? ((g_opt_g8_bm128 & 4) || ((g_opt_g8_bm128 & 1) && nk / splitk <= 16)) : ((g_opt_g8_bm128 & 2) != 0);
                 if (want) {
                     bm = 128;
-                    tiles = gl_cdiv(g.M, 128) * gl_cdiv(g.N, bn);
+                    tiles = mtiles(128) * gl_cdiv(g.N, bn);
                     splitk = plan_split(tiles);
                 }
             }
@@ -861,7 +865,7 @@ int dispatch(const gl_gemm_args& g, const ConvGeom& cg, hipStream_t st) {
                 const bool full_rounds = g_opt_g8_shortk && blocks * 5 >= ((blocks + 255) / 256) * 256 * 4;
                 enough = nk >= 16 || blocks <= 256 || (g.epi == GL_EPI_GEGLU && (nk >= 10 || full_rounds)) || (full_rounds && blocks <= 2048);
             }
-            if (g_opt_g8 == 2 || enough || need8) {
+            if (g_opt_g8 == 2 || enough || need8 || upf) {
                 // the three-pass product xhi.Whi + xlo.Whi + xhi.Wlo in its K-walk description (K = 3 * kwrap; GEMM: the third A segment is
                 // the first one again; conv: in_split == 3) -> the dedicated three-pass loop: same slices, counted in 32-wide stages of kwrap
                 const bool s3 = g_opt_g8_s3 != 0 && g.kwrap != 0 && g.K == 3 * g.kwrap &&
@@ -872,7 +876,9 @@ int dispatch(const gl_gemm_args& g, const ConvGeom& cg, hipStream_t st) {
                 const int order_m = g_opt_order == 1 ? ((CONV ? 9L : 1L) * g.N > (long)g.M) : (g_opt_order == 2);
                 const int e = gl8_launch(g, cg, CONV, bm, bn, zs, kper, order_m | (CONV && g_opt_g8_tapmajor ? 2 : 0), st, s3);
                 if (e) return e;
-                g8_launches.fetch_add(1, std::memory_order_relaxed);
+                // (a folded upsample conv has no other kernel: it is counted by gl_debug_read(12) alone, so that what = 9 keeps telling
+                // where the DISPATCHER chose the 8-wave kernel)
+                if (!upf) g8_launches.fetch_add(1, std::memory_order_relaxed);
                 if (zs > 1) {
                     const size_t total = (size_t)g.M * (g.N / 8);
                     int nblk = (int)((total + 255) / 256);
@@ -884,6 +890,7 @@ int dispatch(const gl_gemm_args& g, const ConvGeom& cg, hipStream_t st) {
             }
         }
     }
+    if (upf) return GL_ERR_UNSUPPORTED;
     if constexpr (!CONV) {
         if (g_opt_geglu32 && g.epi == GL_EPI_GEGLU && g.K <= 640 && g.a2 == nullptr) return dispatch_shape<false, 32>(g, cg, st);
     }
@@ -910,7 +917,13 @@ int conv3x3_entry(const gl_conv_args* a, int shift, void* stream) {
     if (!a || !a->in || !a->g.w || !a->g.out) return GL_ERR_BAD_ARG;
     if ((a->Cin % 64) != 0) return GL_ERR_BAD_ARG;
     if (a->stride != 1 && a->stride != 2) return GL_ERR_BAD_ARG;
+    if (a->upsample2x < 0 || a->upsample2x > 2) return GL_ERR_BAD_ARG;
     if (a->upsample2x && (a->stride != 1 || a->Hout != 2 * a->Hin || a->Wout != 2 * a->Win)) return GL_ERR_BAD_ARG;
+    // folded weights [4 Cout, 4 Cin] (weights.pack_conv_upfold): plain fp16 operands, row-major output, bias / row-bias / residual epilogues
+    const bool upf = a->upsample2x == 2;
+    if (upf && (shift != 0 || a->in_split != 0 || a->w_split != 0 || a->g.out_mode == GL_OUT_F32_NCHW || a->g.out_mode == GL_OUT_F16_HILO ||
+                a->g.epi == GL_EPI_GEGLU || a->g.vt != nullptr || a->g.vt_lo != nullptr))
+        return GL_ERR_BAD_ARG;
     if (a->B >= 2048 || a->Hout >= 1024 || a->Wout >= 1024) return GL_ERR_BAD_ARG;     // packed (b, oy, ox) row coordinates
     if (a->in_split != 0 && a->in_split != 2 && a->in_split != 3) return GL_ERR_BAD_ARG;
     if (a->in_split == 3 && !a->w_split) return GL_ERR_BAD_ARG;      // the third pass multiplies by Wlo
@@ -922,6 +935,7 @@ int conv3x3_entry(const gl_conv_args* a, int shift, void* stream) {
     g.K = 9 * a->Cin * (a->in_split ? a->in_split : 1);
     g.ldw = 9 * a->Cin * (a->w_split ? 2 : 1);
     g.kwrap = a->in_split ? 9 * a->Cin : 0;
+    if (upf) g.K = g.ldw = 4 * a->Cin;       // per parity a 2x2 conv on the source grid
     ConvGeom cg{reinterpret_cast<const half_t*>(a->in), a->B, a->Hin, a->Win, a->Cin * (a->in_split ? 2 : 1), a->Hout, a->Wout, a->stride,
                 a->upsample2x, nullptr, a->in_split == 3 ? 2 * (a->Cin >> 6) : 0, shift};
     return dispatch<true>(g, cg, (hipStream_t)stream);
@@ -973,9 +987,9 @@ int gl_attn_read_launch_counts(void* dst, int64_t bytes);       // attention.hip
 extern "C" int gl_debug_read(int what, void* dst, int64_t bytes) {
     if (what == 8) return gl8_read_stamps(dst, bytes);
     if (what == 10) return gl_attn_read_launch_counts(dst, bytes);
-    if (what == 9 || what == 11) {
+    if (what == 9 || what == 11 || what == 12) {
         if (!dst || bytes < (int64_t)sizeof(uint64_t)) return GL_ERR_BAD_ARG;
-        const uint64_t n = what == 9 ? g8_launches.load(std::memory_order_relaxed) : gl8_kxr_launch_count();
+        const uint64_t n = what == 9 ? g8_launches.load(std::memory_order_relaxed) : (what == 11 ? gl8_kxr_launch_count() : gl8_upf_launch_count());
         memcpy(dst, &n, sizeof n);
         return 0;
     }

@@ -10,7 +10,7 @@ static __device__ uint4 g_zero16[4];
 
 struct ConvGeom {
     const half_t* in;
-    int B, Hin, Win, Cin, Hout, Wout, stride, ups;
+    int B, Hin, Win, Cin, Hout, Wout, stride, ups;      // ups: gl_conv_args.upsample2x (2 = folded weights, gemm8.hip UPF)
     const half_t* zero;        // gemm8.hip: device address of 16 zero bytes (filled by its launcher)
     int cwrap;                 // split-fp16 input with a third pass (gl_conv_args.in_split == 3): channel blocks >= cwrap read the input's block
                                // (cblk - cwrap), i.e. the K walk [hi | lo | hi] over pixel rows that hold [hi | lo]; 0 = no wrap.  Cin above is the
@@ -129,9 +129,10 @@ __device__ __forceinline__ void finish8(const gl_gemm_args& p, float gate, int m
 // gemm8.hip: 8-wave, 256 x {160,128} tile, 3-stage LDS ring filled by LDS-DMA with counted vmcnt and raw s_barrier.
 // Returns < 0 (GL_ERR_UNSUPPORTED) when the problem is outside what it implements; the caller then uses the 4-wave kernels.
 // zs > 1: fp32 partial tiles go to g.workspace[z][M][N] and the caller runs the reduction.
-int gl8_supported(const gl_gemm_args& g, bool conv, int* bn_out);
+int gl8_supported(const gl_gemm_args& g, bool conv, int* bn_out, bool upfold = false);
 // s3: the dedicated three-pass main loop for the split-fp16 product (g in its K-walk form, K = 3 * kwrap; kper in 32-wide stages of kwrap)
 int gl8_launch(const gl_gemm_args& g, const ConvGeom& cg, bool conv, int bm, int bn, int zs, int kper, int order_m, hipStream_t st, bool s3 = false);
 int gl8_init(void);
 int gl8_read_stamps(void* dst, int64_t bytes);
 uint64_t gl8_kxr_launch_count(void);       // launches served by the kx-reuse conv loop (gl_debug_read(11))
+uint64_t gl8_upf_launch_count(void);       // launches served by the folded upsample conv (gl_debug_read(12))

@@ -537,6 +537,8 @@ static gl_opts make_default_opts() {
     o.v[50] = 0;       // strict mode (handles created with split_weights)
     o.v[51] = 1;       // ... with the third pass x.Wlo
     o.v[52] = 1;       // three-pass products on the dedicated three-pass loop of the 8-wave kernel (gemm8.hip S3; 0 = K-walk)
+    o.v[55] = 2;       // upsample convs as four folded 2x2 convs (gemm8.hip UPF), read when a handle is CREATED (it decides the weight table): 0 / 2 = a handle
+                       // keeps [Cout, 9 Cin] rows, 1 = folded [4 Cout, 4 Cin]; 2 (default) tells the Python packers to fold by their measured rule
     o.v[54] = 2;       // kx-reuse loop of the 8-wave 3x3 conv (gemm8.hip KXR): 0 never, 1 wherever eligible, 2 = the measured shapes
     return o;
 }
@@ -547,7 +549,7 @@ int g_gl_option_epoch = 0;
 bool gl_opts_put(gl_opts& t, int key, int value) {
     switch (key) {
         case 2: case 3: case 4: case 6: case 7: case 8: case 10: case 13: case 17: case 20: case 21: case 23: case 24: case 25:
-        case 27: case 29: case 30: case 31: case 32: case 33: case 35: case 37: case 38: case 41: case 42: case 43: case 44: case 45: case 46: case 47: case 50: case 51: case 52: case 53: case 54:
+        case 27: case 29: case 30: case 31: case 32: case 33: case 35: case 37: case 38: case 41: case 42: case 43: case 44: case 45: case 46: case 47: case 50: case 51: case 52: case 53: case 54: case 55:
             t.v[key] = value;
             return true;
         case 5:                                  // < 0: the built-in thresholds (plain GEMM 300 tiles, conv 450)
@@ -558,6 +560,11 @@ bool gl_opts_put(gl_opts& t, int key, int value) {
         case 34: t.v[34] = value < 1 ? 1 : value; return true;
         default: return false;
     }
+}
+
+extern "C" int gl_get_option(int key) {
+    if (key < 0 || key >= GL_OPT_MAX) return GL_ERR_BAD_ARG;
+    return g_gl_opts.v[key];
 }
 
 extern "C" int gl_set_option(int key, int value) {

@@ -50,6 +50,7 @@ struct gl_vae {
     int opt_epoch = 0;
     int ovr_epoch = 0;
     gl_opt_overrides ovr;              // per-handle option overrides (gl_vae_set_option)
+    bool fold_up = false;              // decoder: upsample convs stored as four folded 2x2 kernels [4 C, 4 C] (key 55 at gl_vae_create; gemm8.hip UPF)
     bool encoder = false;              // gl_vae_encoder_create: encode-stage plan (gl_vae_encode), else decode-stage (gl_vae_decode)
 
     void add(const std::string& n, int dtype, std::initializer_list<int64_t> shp) {
@@ -140,7 +141,7 @@ int v_conv(VRun& r, const half_t* x, int sh, int sw, int cin, const std::string&
     a.B = r.B; a.Hin = sh; a.Win = sw; a.Cin = cin;
     a.Hout = up ? 2 * sh : (down ? sh / 2 : sh);
     a.Wout = up ? 2 * sw : (down ? sw / 2 : sw);
-    a.stride = down ? 2 : 1; a.upsample2x = up;
+    a.stride = down ? 2 : 1; a.upsample2x = up ? (v->fold_up ? 2 : 1) : 0;
     a.g.w = v->W<half_t>(p + ".w");
     a.g.bias = v->W<float>(p + ".b");
     a.g.N = cout;
@@ -371,6 +372,7 @@ extern "C" int gl_vae_create(const gl_vae_config* cfg, gl_vae** out) {
         return GL_ERR_BAD_ARG;
     gl_vae* v = new gl_vae();
     v->cfg = *cfg;
+    v->fold_up = gl_opt(55) == 1;      // read ONCE: the weight table follows
     const int nres = cfg->n_mult;
     int ch = cfg->ch * cfg->ch_mult[nres - 1];
     v->add("post_quant_conv.w", 1, {cfg->z_channels, cfg->embed_dim > 0 ? cfg->embed_dim : cfg->z_channels});
@@ -389,7 +391,8 @@ extern "C" int gl_vae_create(const gl_vae_config* cfg, gl_vae** out) {
             ch = cout;
         }
         if (lvl != 0) {
-            v->add("decoder.up." + std::to_string(lvl) + ".upsample.conv.w", 0, {ch, 9 * (int64_t)ch});
+            if (v->fold_up) v->add("decoder.up." + std::to_string(lvl) + ".upsample.conv.w", 0, {4 * (int64_t)ch, 4 * (int64_t)ch});
+            else v->add("decoder.up." + std::to_string(lvl) + ".upsample.conv.w", 0, {ch, 9 * (int64_t)ch});
             v->add("decoder.up." + std::to_string(lvl) + ".upsample.conv.b", 1, {ch});
         }
     }

@@ -33,12 +33,12 @@ def flatten_packed(P: PackedWeights) -> Tuple[torch.Tensor, dict]:
     host-side facts the receivers need."""
     if P.flat is None:
         P.to_flat()
-    return P.flat, dict(total=int(P.flat.numel()), has_sd_conv=bool(P.has_sd_conv))
+    return P.flat, dict(total=int(P.flat.numel()), has_sd_conv=bool(P.has_sd_conv), fold_up=P.fold_up)
 
 
 def unflatten_packed(flat: torch.Tensor, manifest: dict, cfg: UNetConfig, device) -> PackedWeights:
     assert manifest["total"] == flat.numel()
-    return PackedWeights.from_flat(flat, cfg, device, manifest["has_sd_conv"])
+    return PackedWeights.from_flat(flat, cfg, device, manifest["has_sd_conv"], manifest.get("fold_up"))
 
 
 def broadcast_packed(P: Optional[PackedWeights], cfg: UNetConfig, device, src: int = 0) -> PackedWeights:

@@ -46,7 +46,7 @@ class UNetEngine:
         self.W, self.S = packed.w, packed.s
         init_device(self.dev.index)
         self._lib = _lib.lib()
-        self.handle = _lib.create_engine(self.cfg)
+        self.handle = _lib.create_engine(self.cfg, getattr(packed, "fold_up", None))      # the table the buffer was laid out by
         with torch.cuda.device(self.dev):
             check(self._lib.gl_load_weights(self.handle, packed.flat.data_ptr(), packed.flat.numel(), int(packed.has_sd_conv), self._stream()),
                   "gl_load_weights")

@@ -180,6 +180,7 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, B: int, Hin: in
             rows_per_sample: int = 0, nchw_hw: int = 0, n_valid: Optional[int] = None, out16=None, in_split: int = 0,
             w_split: bool = False, pad01: bool = False) -> torch.Tensor:
     """x [B*Hin*Win, Cin] fp16 NHWC; w [Cout, 9*Cin] fp16 (tap-major, channel-minor).
+    ``upsample2x`` with w [4*Cout, 4*Cin] (weights.pack_conv_upfold): the folded form of the layer (gl_conv_args.upsample2x = 2).
     ``pad01`` (stride 2): the VAE encoder's Downsample, F.pad(x, (0, 1, 0, 1)) + pad-0 conv (gl_conv3x3_pad01), Hout = Hin // 2.
     ``in_split`` = 2: x is [B*Hin*Win, 2 Cin] = [hi | lo] pixel rows of a split-fp16 activation, both halves against the same weight;
     3 (with ``w_split``): plus the third pass hi.Wlo.  ``w_split``: w is [Cout, 18 Cin] = rows [Whi | Wlo] (gl_conv_args)."""
@@ -191,8 +192,15 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, B: int, Hin: in
     if in_split:
         Cin //= 2
     N, K, _ = _rows(w, "w")
-    if K != (18 if w_split else 9) * Cin:
-        raise ValueError("w must be [Cout, 9*Cin] ([Cout, 18*Cin] with w_split)")
+    folded = bool(upsample2x) and K == 4 * Cin and not w_split
+    if folded:
+        if n_valid is not None:         # the kernel finds parity p's rows at p * g.N: g.N must be the packed Cout
+            raise ValueError("n_valid does not go with folded upsample weights")
+        if N % 4:
+            raise ValueError("folded upsample weights must be [4*Cout, 4*Cin]")
+        N //= 4
+    elif K != (18 if w_split else 9) * Cin:
+        raise ValueError("w must be [Cout, 9*Cin] ([Cout, 18*Cin] with w_split; [4*Cout, 4*Cin] folded upsample weights)")
     if upsample2x:
         Hout, Wout = 2 * Hin, 2 * Win
     elif pad01:
@@ -202,7 +210,7 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, B: int, Hin: in
     a = ConvArgs()
     a.inp = x.data_ptr()
     a.B, a.Hin, a.Win, a.Cin, a.Hout, a.Wout = B, Hin, Win, Cin, Hout, Wout
-    a.stride, a.upsample2x = stride, int(upsample2x)
+    a.stride, a.upsample2x = stride, (2 if folded else int(bool(upsample2x)))
     a.in_split, a.w_split = int(in_split), int(bool(w_split))
     a.g.w = w.data_ptr()
     a.g.N = N if n_valid is None else n_valid
@@ -646,6 +654,14 @@ def kxreuse_launch_count() -> int:
     import ctypes
     n = ctypes.c_uint64(0)
     check(_lib.lib().gl_debug_read(11, ctypes.byref(n), 8), "gl_debug_read")
+    return int(n.value)
+
+
+def upfold_launch_count() -> int:
+    """gl_conv3x3 calls this process has served as folded upsample convs (gl_debug_read(12), gl_conv_args.upsample2x = 2)."""
+    import ctypes
+    n = ctypes.c_uint64(0)
+    check(_lib.lib().gl_debug_read(12, ctypes.byref(n), 8), "gl_debug_read")
     return int(n.value)
 
 

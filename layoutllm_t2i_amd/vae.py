@@ -31,7 +31,7 @@ import torch
 from . import ops
 from ._lib import EPI_BIAS, EPI_RES, init_device
 from .arch import VAEConfig, vae_decoder_param_shapes, vae_encoder_param_shapes
-from .weights import CIN_PAD, _h, _t, pack_conv3x3
+from .weights import CIN_PAD, _h, _t, pack_conv3x3, pack_conv_upfold
 
 F16, F32 = torch.float16, torch.float32
 _FP32_1X1 = ("post_quant_conv", "quant_conv")      # 1x1 convs on the 4 / 8-channel latent side: kept in fp32
@@ -45,10 +45,28 @@ def _pack_kind(p: str, shp: Tuple[int, ...]) -> str:
     return "f32_1x1" if p in _FP32_1X1 else "gemm"
 
 
-def packed_shapes(param_shapes: Mapping[str, Tuple[int, ...]]) -> Dict[str, Tuple[Tuple[int, ...], torch.dtype]]:
+# narrowest upsample conv (channels) of a decoder whose up convs are folded under the default of option key 55 (2): the full decoder's 256- and
+# 512-channel layers run in 0.46-0.54 of the 9-tap time at B = 4 (-1.6 ms per decode); a test-size decoder (128 channels, -7 us) keeps its pack
+# unless fold_up=True or key 55 = 1 asks for the fold (profiles/upfold_shapes.txt)
+VAE_UPFOLD_MIN_CHANNELS = 256
+
+
+def _fold(fold_up, cfg) -> bool:
+    from . import _lib
+    ups = [shp[0] for n, shp in vae_decoder_param_shapes(cfg).items() if n.endswith(".upsample.conv.weight")]
+    return _lib.resolve_fold_up(fold_up, bool(ups) and min(ups) >= VAE_UPFOLD_MIN_CHANNELS)
+
+
+def _is_upsample(p: str) -> bool:
+    return p.startswith("decoder.up.") and p.endswith(".upsample.conv")
+
+
+def packed_shapes(param_shapes: Mapping[str, Tuple[int, ...]], fold_up: bool = False) -> Dict[str, Tuple[Tuple[int, ...], torch.dtype]]:
     """CPU-side: the engine-table entries {name: (shape, dtype)} the packer makes from reference-named ``param_shapes``
     (3x3 convs fp16 [Cout, 9 * Cin] with Cin < 64 padded to CIN_PAD, 1x1 convs fp16 [N, K] except the fp32 (post_)quant_conv,
-    norm affine and biases fp32)."""
+    norm affine and biases fp32; with ``fold_up`` (a handle created under option key 55 = 1) the decoder's upsample convs fp16
+    [4 * Cout, 4 * Cin])."""
+    fold = bool(fold_up)
     out: Dict[str, Tuple[Tuple[int, ...], torch.dtype]] = {}
     for name, shp in param_shapes.items():
         if not name.endswith(".weight"):
@@ -57,7 +75,9 @@ def packed_shapes(param_shapes: Mapping[str, Tuple[int, ...]]) -> Dict[str, Tupl
         if kind == "norm":
             out[p + ".g"], out[p + ".b"] = ((shp[0],), F32), ((shp[0],), F32)
             continue
-        if kind == "conv3x3":
+        if kind == "conv3x3" and fold and _is_upsample(p):
+            out[p + ".w"] = ((4 * shp[0], 4 * shp[1]), F16)
+        elif kind == "conv3x3":
             out[p + ".w"] = ((shp[0], 9 * (CIN_PAD if shp[1] < 64 else shp[1])), F16)
         else:
             out[p + ".w"] = ((shp[0], shp[1]), F32 if kind == "f32_1x1" else F16)
@@ -65,8 +85,9 @@ def packed_shapes(param_shapes: Mapping[str, Tuple[int, ...]]) -> Dict[str, Tupl
     return out
 
 
-def _pack(state_dict: Mapping[str, object], need: Mapping[str, Tuple[int, ...]], device) -> Dict[str, torch.Tensor]:
-    """Reference-named tensors -> the engine's packed forms (``packed_shapes``); C^-0.5 folded into mid.attn_1.q."""
+def _pack(state_dict: Mapping[str, object], need: Mapping[str, Tuple[int, ...]], device, fold_up=False) -> Dict[str, torch.Tensor]:
+    """Reference-named tensors -> the engine's packed forms (``packed_shapes``); C^-0.5 folded into mid.attn_1.q; with ``fold_up`` the
+    decoder's upsample convs as folded 2x2 kernels (weights.pack_conv_upfold)."""
     g = lambda k: _t(state_dict[k], device)
     W: Dict[str, torch.Tensor] = {}
     for name, shp in need.items():
@@ -78,6 +99,9 @@ def _pack(state_dict: Mapping[str, object], need: Mapping[str, Tuple[int, ...]],
         kind = _pack_kind(p, shp)
         if kind == "norm":
             W[p + ".g"], W[p + ".b"] = w.contiguous(), b.contiguous()
+        elif kind == "conv3x3" and fold_up and _is_upsample(p):
+            W[p + ".w"] = pack_conv_upfold(w)
+            W[p + ".b"] = b.contiguous()
         elif kind == "conv3x3":
             W[p + ".w"] = pack_conv3x3(w, CIN_PAD if shp[1] < 64 else None)
             W[p + ".b"] = b.contiguous()
@@ -110,7 +134,7 @@ class _VAEStage:
     def _bind_engine(self):
         """Moves the packed tensors into the C engine's flat layout (gl_vae_weight_at) and rebinds ``W`` to views of it."""
         from . import _lib
-        self.handle = _lib.create_vae(self.cfg, encoder=self._encoder_stage)
+        self.handle = _lib.create_vae(self.cfg, encoder=self._encoder_stage, fold_up=getattr(self, "fold_up", None))
         table, total = _lib.vae_weight_table(self.handle)
         flat = torch.zeros(total, dtype=torch.uint8, device=self.device)
         views = {}
@@ -197,17 +221,20 @@ class _VAEStage:
 
 
 class VAEDecoder(_VAEStage):
-    def __init__(self, state_dict: Mapping[str, object], cfg: VAEConfig = VAEConfig(), device="cuda:0"):
+    def __init__(self, state_dict: Mapping[str, object], cfg: VAEConfig = VAEConfig(), device="cuda:0", fold_up=None):
+        """``fold_up``: the upsample convs as folded 2x2 kernels (None: the current value of option key 55, whose default folds decoders
+        whose up convs have at least VAE_UPFOLD_MIN_CHANNELS channels)."""
         if not torch.cuda.is_available():
             raise RuntimeError("VAEDecoder needs a GPU: there is no CPU fallback")
         init_device()
         self.cfg, self.device = cfg, torch.device(device)
         self.scale_factor = cfg.scale_factor
+        self.fold_up = _fold(fold_up, cfg)
         need = vae_decoder_param_shapes(cfg)
         missing = [k for k in need if k not in state_dict]
         if missing:
             raise KeyError(f"autoencoder state_dict is missing {len(missing)} decoder tensors, e.g. {missing[:3]}")
-        self.W = _pack(state_dict, need, self.device)
+        self.W = _pack(state_dict, need, self.device, self.fold_up)
         self._pool: Dict[tuple, torch.Tensor] = {}
         self._bind_engine()
         # the encode stage, when the state dict carries it (real GLIGEN checkpoints do); self.W stays decoder-only
@@ -226,6 +253,9 @@ class VAEDecoder(_VAEStage):
         self = cls.__new__(cls)
         self.cfg, self.device, self.scale_factor = cfg, torch.device(device), cfg.scale_factor
         self.W = {k: v.to(self.device) for k, v in W.items()}
+        # folded or 9-tap upsample convs: what the packed tensors are ([4 C, 4 C] against [C, 9 C])
+        ups = [v for k, v in self.W.items() if k.endswith(".w") and _is_upsample(k[:-2])]
+        self.fold_up = bool(ups) and all(v.shape[0] == v.shape[1] for v in ups)
         self._pool = {}
         self._bind_engine()
         self.encoder = None

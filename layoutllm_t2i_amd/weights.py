@@ -6,6 +6,8 @@ layout work only (no arithmetic beyond dtype casts and tanh of the scalar gates)
   * Linear / 1x1-conv weights  [N, K]            -> fp16 [N, K]
   * 3x3 conv weights [Cout, Cin, 3, 3]          -> fp16 [Cout, 9*Cin], K = (64-channel block, tap, channel) (NHWC implicit GEMM);
                                                    the 4-channel first conv is zero-padded to Cin = 64
+  * Upsample conv weights [Cout, Cin, 3, 3]     -> fp16 [4*Cout, 4*Cin]: one 2x2 kernel per output parity, summed in fp32 (pack_conv_upfold;
+                                                   option key 55, not in a split_weights table)
   * GEGLU proj [8C, C] (x rows | gate rows)      -> rows interleaved in blocks of 32 (x32 | gate32 | x32 | ...)
                                                    so x_j and gate_j land in adjacent MFMA tiles (bias likewise)
   * self-attention to_q/to_k/to_v                -> one [3C, C] matrix (single QKV GEMM)
@@ -60,6 +62,44 @@ def pack_conv3x3(w: torch.Tensor, cin_pad: int | None = None) -> torch.Tensor:
     return _h(wp.reshape(cout, -1))
 
 
+# taps of the 3x3 kernel that window position a (or b) of output parity py (or px) collects: S[parity][position]
+UPFOLD_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+# Narrowest upsample conv (channels) of a UNet config whose up convs are folded under the default of option key 55 (2): the full model's 640- and
+# 1280-channel layers run in 0.42-0.54 of the 9-tap time at 2B = 8 (-0.31 ms per forward).  Narrower configs exist only at test size: there the
+# folded launch is faster too, but by 3-7 us of a latency-bound launch (profiles/upfold_shapes.txt), and their compact pack stays what it was --
+# bit-identical to the Whi half of the split_weights pack of the same checkpoint, which never folds.  fold_up=True or key 55 = 1 folds any config.
+# Static per config: never a function of batch or map size.
+UPFOLD_MIN_CHANNELS = 512
+
+
+def fold_up_rule(cfg: UNetConfig) -> bool:
+    ups = [l.cin for l in build_plan(cfg).all_layers() if l.kind == "up"]
+    return bool(ups) and min(ups) >= UPFOLD_MIN_CHANNELS and not getattr(cfg, "split_weights", False)
+
+
+def pack_conv_upfold(w32: torch.Tensor) -> torch.Tensor:
+    """Upsample conv [Cout, Cin, 3, 3] fp32 -> fp16 [4*Cout, 4*Cin].  After nearest-2x upsampling the nine taps of output pixel
+    (2y + py, 2x + px) touch only the source pixels (y + py - 1 + a, x + px - 1 + b), a, b in {0, 1}: per parity the layer is a 2x2 conv on the
+    source grid with Wf[py,px][:, :, a, b] = sum of W[:, :, ky, kx] over ky in S(py, a), kx in S(px, b).  The sums are taken in fp32 from the
+    unrounded weights and rounded ONCE.  Rows (parity py * 2 + px, Cout); K ordered (64-channel block, tap a * 2 + b, channel in block)."""
+    w32 = w32.float()
+    cout, cin = w32.shape[0], w32.shape[1]
+    assert tuple(w32.shape[2:]) == (3, 3) and cin % 64 == 0, "upsample conv: 3x3 kernel, input channels a multiple of 64"
+    out = []
+    for py in range(2):
+        for px in range(2):
+            f = torch.zeros(cout, cin, 2, 2, dtype=torch.float32, device=w32.device)
+            for a in range(2):
+                for b in range(2):
+                    for ky in UPFOLD_TAPS[py][a]:
+                        for kx in UPFOLD_TAPS[px][b]:
+                            f[:, :, a, b] += w32[:, :, ky, kx]
+            out.append(f.reshape(cout, cin // 64, 64, 2, 2).permute(0, 1, 3, 4, 2).reshape(cout, -1))
+    return _h(torch.cat(out, 0))
+
+
 def pack_first_conv(w: torch.Tensor, cin_pad: int) -> torch.Tensor:
     """first conv [Cout, C, 3, 3] fp32 (C = 4 latent channels of 64 padded ones; C = 9 on an inpaint_mode model: 27 of 64): input channels
     [Whi | Whi | Wlo | 0] for the latent packed as [hi | lo | hi] (gl_pack_latent / gl_pack_latent_extra split): x.W = xhi.Whi + xlo.Whi + xhi.Wlo at no cost.  The first conv alone carries 7 % of the error of storing
@@ -94,6 +134,7 @@ class PackedWeights:
         self.emb_total = 0
         self.flat: torch.Tensor | None = None
         self.has_sd_conv = False
+        self.fold_up: bool | None = None         # upsample convs packed as folded 2x2 kernels (None: the handle default, 9-tap rows unless key 55 = 1)
 
     def nbytes(self) -> int:
         return int(self.flat.numel()) if self.flat is not None else sum(t.numel() * t.element_size() for t in self.w.values())
@@ -101,7 +142,7 @@ class PackedWeights:
     def to_flat(self) -> "PackedWeights":
         """Moves every packed tensor into the flat buffer at the offsets the C engine dictates and rebinds ``w`` to views."""
         from . import _lib
-        handle = _lib.create_engine(self.cfg)
+        handle = _lib.create_engine(self.cfg, self.fold_up)
         try:
             table, total = _lib.weight_table(handle)
         finally:
@@ -132,11 +173,13 @@ class PackedWeights:
         return self
 
     @staticmethod
-    def from_flat(flat: torch.Tensor, cfg: UNetConfig, device, has_sd_conv: bool) -> "PackedWeights":
-        """Rebuilds the views (and the scalar gates) from a flat buffer, e.g. on the receiving ranks of the broadcast."""
+    def from_flat(flat: torch.Tensor, cfg: UNetConfig, device, has_sd_conv: bool, fold_up: bool | None = None) -> "PackedWeights":
+        """Rebuilds the views (and the scalar gates) from a flat buffer, e.g. on the receiving ranks of the broadcast.
+        ``fold_up``: whether the buffer was packed with folded upsample convs (None: what pack_state_dict would do now)."""
         from . import _lib
         P = PackedWeights(cfg, build_plan(cfg), device)
-        handle = _lib.create_engine(cfg)
+        P.fold_up = fold_up = _lib.resolve_fold_up(fold_up, fold_up_rule(cfg))
+        handle = _lib.create_engine(cfg, fold_up)
         try:
             table, total = _lib.weight_table(handle)
         finally:
@@ -159,8 +202,10 @@ class PackedWeights:
         return P
 
 
-def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_conv: Mapping[str, object] | None = None
-                    ) -> PackedWeights:
+def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_conv: Mapping[str, object] | None = None,
+                    fold_up: bool | None = None) -> PackedWeights:
+    """``fold_up``: upsample convs as folded 2x2 kernels (pack_conv_upfold); None = the current value of option key 55, whose default
+    folds the configs of ``fold_up_rule``.  A split_weights pack never folds."""
     plan = build_plan(cfg)
     need = param_shapes(cfg)
     missing = [k for k in need if k not in sd]
@@ -176,6 +221,9 @@ def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_
     W, S = P.w, P.s
     g = lambda k: _t(sd[k], device)
     split_all = bool(getattr(cfg, "split_weights", False))
+    from . import _lib
+    P.fold_up = _lib.resolve_fold_up(fold_up, fold_up_rule(cfg))
+    fold = P.fold_up and not split_all
 
     def mat(w32: torch.Tensor) -> torch.Tensor:
         """fp32 [N, K] -> the stored matrix: fp16 [N, K], or rows [Whi | Wlo] (fp16 [N, 2K]) in a split_weights table
@@ -240,7 +288,10 @@ def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_
     emb_w, emb_b, off = [], [], 0
     for l in plan.all_layers():
         p = l.prefix
-        if l.kind in ("down", "up"):
+        if l.kind == "up" and fold:
+            W[p + ".w"] = pack_conv_upfold(g(p + ".weight"))
+            W[p + ".b"] = g(p + ".bias").contiguous()
+        elif l.kind in ("down", "up"):
             conv3(p)
         elif l.kind == "res":
             norm(p + ".in_layers.0")

@@ -2,6 +2,7 @@
 model under different gl_set_option settings, interleaved rounds; optionally also the Python launch sequence of
 tests/engine_pyref.py (torch-captured graph) as a cross-check of the orchestration cost.
     python tools/engine_ab_probe.py [B] [variant ...]      variant = name:key=value[,key=value...]   e.g.  nofusedgn:17=0
+A variant that sets key 55 (folded upsample convs: read when a handle is created) gets an engine of its own, packed and created under that value.
 """
 import os
 import sys
@@ -35,12 +36,15 @@ P = pack_state_dict(_sd, cfg, dev, recipe.sd_first_conv(cfg, 0))
 # AB_PARITY=1: every variant's output (sample 0, cond, fuser on) against the fp32 oracle on the same UNROUNDED weights / latent / context
 PARITY = bool(int(os.environ.get("AB_PARITY", "0")))
 sd_cpu = {k: v.detach().float().cpu() for k, v in _sd.items()} if PARITY else None
-del _sd
 inp = {k: torch.from_numpy(v) for k, v in recipe.synth_inputs(cfg, B, 64, n_boxes=8, n_rel=3, seed=1).items()}
 z = torch.zeros_like
 cat = lambda a, b: torch.cat([a, b], 0)
 eng = UNetEngine(P)
 engines = {"cpp": eng}
+for _name, _opts in variants:
+    _fold = [v for k, v in (_opts or []) if k == 55]
+    if _fold:
+        engines[_name] = UNetEngine(pack_state_dict(_sd, cfg, dev, recipe.sd_first_conv(cfg, 0), fold_up=bool(_fold[-1])))
 if any(o is None for _, o in variants):
     from engine_pyref import PyRefEngine
     engines["pyref"] = PyRefEngine(P)
@@ -67,9 +71,10 @@ res = {n: {1.0: [], 0.0: []} for n, _ in variants}
 launches = {}
 for rnd in range(5):
     for name, opts in variants:
-        e = engines["pyref"] if opts is None else eng
+        e = engines["pyref"] if opts is None else engines.get(name, eng)
         for k, v in (opts or []):
-            ops.set_option(k, v)
+            if k != 55:
+                ops.set_option(k, v)
         if opts is not None:
             condition(e)                 # some options act when the conditioning is set (key 43: rows of the relation chain)
         for fs in (1.0, 0.0):
@@ -83,13 +88,14 @@ for rnd in range(5):
             torch.cuda.synchronize()
             res[name][fs].append(e0.elapsed_time(e1) / 10)
         if opts is not None:
-            launches[name] = eng.num_launches()
+            launches[name] = e.num_launches()
         if ref is not None and name not in parity:
             o = e.forward(x, 481.0, 1.0, False, 2)[0:1].float().cpu()
             d = (o - ref).abs()
             parity[name] = (float((o - ref).norm() / ref.norm()), float((d > 1e-4 + 1e-3 * ref.abs()).float().mean()))
         for k, _ in (opts or []):
-            ops.set_option(k, DEFAULTS[k])
+            if k != 55:
+                ops.set_option(k, DEFAULTS[k])
 for name, _ in variants:
     for fs in (1.0, 0.0):
         v = sorted(res[name][fs])

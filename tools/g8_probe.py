@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B probe of the 8-wave deep-pipelined GEMM / conv kernel (csrc/gemm8.hip) against the 4-wave kernels (GPU box).
 
-    python tools/g8_probe.py [check] [time] [race] [stamps] [kxr]
+    python tools/g8_probe.py [check] [time] [race] [stamps] [kxr] [upfold]
 
 check : every epilogue / operand form through gl_gemm / gl_conv3x3 with option 30 = 2 (8-wave kernel wherever it applies)
         against option 30 = 0 (the parity-tested 4-wave kernels) on the same inputs; the two differ only in fp32 summation
@@ -13,6 +13,9 @@ kxr   : the stride-1 conv shapes of a config-2 forward (2B = 8) and of the VAE d
         loop off and on (option 54 = 0 / 1), interleaved in one process: median and spread of G8_ROUNDS (5) rounds of G8_ITERS (20) launches,
         whether the launch was eligible (served by the kx-reuse loop) and whether both give the same bits.  G8_KXR=0/1 pins option 54 for
         the other modes (stamps, spin, race).
+upfold: the six upsample convs (UNet at 2B = 8, VAE decode at B = 4) as the 9-tap launch (upsample2x = 1, [Cout, 9 Cin] weights) and as the
+        folded launch (upsample2x = 2, [4 Cout, 4 Cin] weights from weights.pack_conv_upfold), interleaved in one process under the default
+        dispatch: median and spread of G8_ROUNDS (5) rounds of G8_ITERS (20) launches, and the rel-L2 of the two fp16 outputs to each other.
 """
 import math
 import os
@@ -102,6 +105,50 @@ def conv_case(B, side, cin, cout, stride=1, up=False, epi="bias", f32=False):
         ops.conv3x3(x, w, o[0], B, side, side, bias, stride=stride, upsample2x=up, epi=e, res=res, rowbias=rb,
                     rows_per_sample=ho * ho, out16=o[1])
     return alloc, launch, 2.0 * M * cout * 9 * cin
+
+
+UPFOLD_SHAPES = [("unet", 8, 8, 1280), ("unet", 8, 16, 1280), ("unet", 8, 32, 640), ("vae", 4, 64, 512), ("vae", 4, 128, 512), ("vae", 4, 256, 256)]
+
+
+# G8_UPFOLD_SMALL=1: the up convs of the small test configs (TINY UNet at 2B = 4 on a 16x16 latent, tiny VAE decoder at B = 2)
+UPFOLD_SMALL_SHAPES = [("tiny unet", 4, 2, 256), ("tiny unet", 4, 4, 256), ("tiny unet", 4, 8, 128), ("tiny vae", 2, 8, 128)]
+
+
+def upfold_probe():
+    from layoutllm_t2i_amd.weights import pack_conv3x3, pack_conv_upfold
+    iters, rounds = int(os.environ.get("G8_ITERS", "20")), int(os.environ.get("G8_ROUNDS", "5"))
+    print(f"== upsample convs, 9-tap | folded (default dispatch): us median [min..max] of {rounds} rounds x {iters} launches; algorithmic TF/s")
+    ok = True
+    for who, B, side, ch in (UPFOLD_SMALL_SHAPES if os.environ.get("G8_UPFOLD_SMALL") else UPFOLD_SHAPES):
+        name = f"up {who} {B}x{side}^2->{2 * side}^2 {ch}ch"
+        x = h(B * side * side, ch)
+        w32 = torch.randn(ch, ch, 3, 3, generator=G) * (9 * ch) ** -0.5
+        ws = [pack_conv3x3(w32).to(DEV), pack_conv_upfold(w32).to(DEV)]
+        bias = f(ch, scale=0.1)
+        M = 4 * B * side * side
+        outs = [torch.full((M, ch), 7.0, dtype=F16, device=DEV) for _ in ws]
+        launch = lambda k: ops.conv3x3(x, ws[k], outs[k], B, side, side, bias, upsample2x=True)
+        n = ops.upfold_launch_count()
+        launch(0)
+        launch(1)
+        torch.cuda.synchronize()
+        served = ops.upfold_launch_count() - n
+        rel = float((outs[1].float() - outs[0].float()).norm() / outs[0].float().norm())
+        ts = [[], []]
+        for _ in range(rounds):
+            for k in (0, 1):
+                ts[k].append(timeit(lambda: launch(k), iters) * 1e6)
+        med = [sorted(v)[len(v) // 2] for v in ts]
+        spread = max(max(v) - min(v) for v in ts)
+        d = med[0] - med[1]
+        verdict = "win" if d > spread else ("loss" if -d > spread else "tie")
+        fl = 2.0 * M * ch * 9 * ch
+        good = served == 1 and rel < 2e-3
+        ok &= good
+        print(f"  {name:34s} {med[0]:8.1f} [{min(ts[0]):.1f}..{max(ts[0]):.1f}] {fl / med[0] / 1e6:6.0f} | {med[1]:8.1f} [{min(ts[1]):.1f}..{max(ts[1]):.1f}] "
+              f"{fl / med[1] / 1e6:6.0f}  {100 * d / med[0]:+5.1f} %  spread {spread:.1f}  {verdict}  rel_l2 {rel:.2e}{'' if good else '  FAIL'}")
+        del x, ws, outs
+    return ok
 
 
 def cases():
@@ -207,6 +254,8 @@ def main():
     allok = True
     if os.environ.get("G8_KXR"):
         ops.set_option(54, int(os.environ["G8_KXR"]))
+    if "upfold" in which:
+        allok &= upfold_probe()
     if "kxr" in which:
         iters, rounds = int(os.environ.get("G8_ITERS", "20")), int(os.environ.get("G8_ROUNDS", "5"))
         print(f"== kx-reuse loop, option 54 = 0 | 1 (default dispatch otherwise): us median [min..max] of {rounds} rounds x {iters} launches")

@@ -113,6 +113,8 @@ def class_summary(iters=8, peak_tflops=2500.0, strict=False):
     fl_c = t_c = 0.0
     for (side, cin, cout, stride, up), n in convs.items():
         x, w = h(B2 * side * side, cin), h(cout, 9 * cin) * ((9 * cin) ** -0.5)
+        if up and not strict:           # the default mode's upsample convs run folded: [4 Cout, 4 Cin] weights (option key 55)
+            w = h(4 * cout, 4 * cin) * ((9 * cin) ** -0.5)
         ho = side * 2 if up else side // stride
         o = torch.empty(B2 * ho * ho, cout, dtype=torch.float16, device=DEV)
         bias = torch.zeros(cout, device=DEV)
@@ -227,6 +229,8 @@ def main():
         for (side, cin, cout, stride, up), n in convs.items():
             x = h(B2 * side * side, cin)
             w = h(cout, 9 * cin) * ((9 * cin) ** -0.5)
+            if up and not STRICT:       # folded upsample conv (option key 55): [4 Cout, 4 Cin] weights; TF/s stays algorithmic (9 taps)
+                w = h(4 * cout, 4 * cin) * ((9 * cin) ** -0.5)
             ho = side * 2 if up else side // stride
             out = torch.empty(B2 * ho * ho, cout, dtype=torch.float16, device=DEV)
             bias = torch.zeros(cout, device=DEV)

@@ -9,16 +9,18 @@ nf = float(sys.argv[2]) if len(sys.argv) > 2 else 104.0
 import re
 
 
-def g8(n, conv, s3, kxr=False):
-    """gemm8_kernel<BM, BN, CONV, DBG[, S3[, KXR]]>: the conv flag is the THIRD template argument, the three-pass loop the fifth (round 6),
-    the kx-reuse conv loop the sixth"""
-    m = re.search(r"gemm8_kernel<(\d+), (\d+), (true|false), (\d+)(?:, (true|false))?(?:, (true|false))?>", n)
-    return bool(m) and (m.group(3) == "true") == conv and ((m.group(5) or "false") == "true") == s3 and ((m.group(6) or "false") == "true") == kxr
+def g8(n, conv, s3, kxr=False, upf=False):
+    """gemm8_kernel<BM, BN, CONV, DBG[, S3[, KXR[, UPF]]]>: the conv flag is the THIRD template argument, the three-pass loop the fifth (round 6),
+    the kx-reuse conv loop the sixth, the folded upsample conv the seventh"""
+    m = re.search(r"gemm8_kernel<(\d+), (\d+), (true|false), (\d+)(?:, (true|false))?(?:, (true|false))?(?:, (true|false))?>", n)
+    t = lambda i: (m.group(i) or "false") == "true"
+    return bool(m) and t(3) == conv and t(5) == s3 and t(6) == kxr and t(7) == upf
 
 
 classes = [("8-wave conv, three-pass loop", lambda n: g8(n, True, True)),
            ("8-wave GEMM, three-pass loop", lambda n: g8(n, False, True)),
            ("8-wave conv, kx-reuse loop", lambda n: g8(n, True, False, True)),
+           ("8-wave conv, folded upsample", lambda n: g8(n, True, False, False, True)),
            ("8-wave conv (gemm8<.,true>)", lambda n: g8(n, True, False)),
            ("8-wave GEMM (gemm8<.,false>)", lambda n: "gemm8_kernel" in n),
            ("4-wave conv", lambda n: "gemm_kernel<" in n and ", true," in n),
