@@ -315,6 +315,23 @@ int gl_posnet_input_ti_f32(const float* boxes, const float* masks, const float* 
                            int32_t in_dim, int32_t num_freqs, float* out_text, float* out_image, void* stream);
 int gl_image_ground_feature(const float* feat, const float* proj, int32_t n, int32_t dim, float norm, float* out, void* stream);
 
+/*
+ * keypoint grounding (checkpoint_generation_keypoint.pth; keypoint_grounding_net.py:34-58), additive to ABI 15.
+ *   gl_posnet_input_kp(_f32) : the MLP input of the keypoint PositionNet, one block per (b, t) token row, t in [0, tokens), tokens = 17 P:
+ *                              out[b * tokens + t, :] = [ (person_emb[t / 17] + keypoint_emb[t % 17]) * m + (1 - m) * null_person   (D)
+ *                                                       | fourier(points[b, t]) * m + (1 - m) * null_xy                           (4 F)
+ *                                                       | 0                                                                      (pad) ]
+ *                              with row stride ld = D + 4 F rounded up to a multiple of 64 (the padded K of linears.0; the kernel writes the
+ *                              pad columns).  fp32 arithmetic, table sum before the blend; m = masks[b, t] is a blend factor.  Fourier order
+ *                              per frequency 100^(j / F): sin(f x), sin(f y), cos(f x), cos(f y).  points [B, tokens, 2], masks [B, tokens],
+ *                              person_emb [P, D], keypoint_emb [17, D], null_person [D], null_xy [4 F], fp32; tokens % 17 == 0.
+ *                              fp16 output, or fp32 with _f32 (strict mode, then gl_split_f32 over ld columns).
+ */
+int gl_posnet_input_kp(const float* points, const float* masks, const float* person_emb, const float* keypoint_emb, const float* null_person,
+                       const float* null_xy, int32_t B, int32_t tokens, int32_t D, int32_t num_freqs, void* out, void* stream);
+int gl_posnet_input_kp_f32(const float* points, const float* masks, const float* person_emb, const float* keypoint_emb, const float* null_person,
+                           const float* null_xy, int32_t B, int32_t tokens, int32_t D, int32_t num_freqs, float* out, void* stream);
+
 /* gl_silu_f16: y = silu(x) elementwise fp16 (emb_layers SiLU, openaimodel.py:173). n % 8 == 0. */
 int gl_silu_f16(const void* x, void* y, int64_t n, void* stream);
 
@@ -392,7 +409,14 @@ typedef struct gl_unet_config {          /* UNetModel.__init__ arguments (openai
                                     linears_image.* / null_text / null_image / null_xyxy, every box yields TWO grounding tokens (text, image), and the
                                     handle is conditioned through gl_set_conditioning_ti.  n_ground = max_objs (0) or 2 * max_objs (1) is the token count
                                     of the gated self-attention (keys N + n_ground); gl_create rejects n_ground > 64.  The relation chain keeps
-                                    max_objs boxes. */
+                                    max_objs boxes.
+                                    2 = the keypoint PositionNet (keypoint_grounding_net.py): max_objs counts grounding TOKENS, 17 per person, and must be
+                                    a multiple of 17, at most 136 (8 persons); pos_in_dim is the person-feature width (= pos_out_dim).  The table holds
+                                    position_net.person_emb [max_objs / 17, D], keypoint_emb [17, D], null_person [D], null_xy [4 F] (fp32) and
+                                    linears.{0,2,4}, linears.0 with K = pos_in_dim + 4 F zero-padded to the next multiple of 64 (800 -> 832; each of
+                                    the [Whi | Wlo] halves of a split_weights table on its own).  The handle is conditioned through
+                                    gl_set_conditioning_kp.  Requires no_relation = 1 (the relation chain pools over boxes) and inpaint_mode = 0, else
+                                    GL_ERR_UNSUPPORTED. */
     int32_t inpaint_mode;        /* additive to ABI 15.  0 = the first conv reads the latent alone (a zeroed field keeps the earlier behaviour).  1 = GLIGEN's
                                     inpainting checkpoints (openaimodel.py:293-299, :436-439): input_blocks.0.0 is [mc, 2 * in_channels + 1, 3, 3] and reads
                                     cat([x, z0 * mask, mask]); in_channels stays the latent's channel count.  The packed weight keeps its [mc, 9 * 64] slot
@@ -456,6 +480,13 @@ int gl_set_conditioning_hw(gl_engine* e, const float* context, const float* rela
 int gl_set_conditioning_ti(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
                            const float* text_masks, const float* image_masks, const float* text_emb, const float* image_emb, int32_t Bn,
                            int32_t Lc, int32_t R, int32_t h, int32_t w, void* stream);
+/* gl_set_conditioning_kp: the conditioning of a keypoint handle (gl_unet_config.grounding = 2; additive to ABI 15).  points [Bn, max_objs, 2]
+ * (x, y in [0, 1]; token t of a sample is keypoint t % 17 of person t / 17) and masks [Bn, max_objs], fp32 on the device; null grounding = both
+ * zero.  One MLP chain over Bn * max_objs rows; no relations, no rectangles.  (h, w): the shape rule of gl_set_conditioning_hw.  The text and
+ * text_image entries on a keypoint handle, and this entry on a handle of another family, return GL_ERR_BAD_ARG with a gl_last_error message
+ * that names the right entry, before any pointer is read. */
+int gl_set_conditioning_kp(gl_engine* e, const float* context, const float* points, const float* masks, int32_t Bn, int32_t Lc, int32_t h,
+                           int32_t w, void* stream);
 /* gl_set_inpaint_extra: the inpainting_extra_input of an inpaint_mode handle (gligen_inference.py:406-407: cat([z0 * mask, mask], dim=1)),
  * extra fp32 [Bs, in_channels + 1, h, w] on the device, Bs = 1 (one extra for every sample) or the number of samples Bn / reps.  It is copied
  * (stream-ordered) into a buffer of the handle's pool whose address the captured graphs read at replay time, so a new extra needs no new

@@ -20,7 +20,7 @@ EPI_BIAS, EPI_SILU, EPI_GEGLU, EPI_RES, EPI_GATE_RES, EPI_ROWBIAS = range(6)
 OUT_F16_ROWMAJOR, OUT_F32_NCHW, OUT_F32_ROWMAJOR, OUT_F16_HILO = 0, 1, 2, 3
 
 # gl_unet_config.grounding
-GROUNDING_IDS = {"text": 0, "text_image": 1}
+GROUNDING_IDS = {"text": 0, "text_image": 1, "keypoint": 2}
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -189,6 +189,9 @@ PROTOTYPES = {
     "gl_set_conditioning": (i32, [vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, vp]),
     "gl_set_conditioning_hw": (i32, [vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]),
     "gl_set_conditioning_ti": (i32, [vp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]),
+    "gl_set_conditioning_kp": (i32, [vp, fp, fp, fp, i32, i32, i32, i32, vp]),
+    "gl_posnet_input_kp": (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, vp, vp]),
+    "gl_posnet_input_kp_f32": (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, fp, vp]),
     "gl_posnet_input_ti": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp, vp, vp]),
     "gl_posnet_input_ti_f32": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, fp, fp, vp]),
     "gl_image_ground_feature": (i32, [fp, fp, i32, i32, f32, fp, vp]),

@@ -10,8 +10,12 @@ Nothing here touches a device.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, Tuple
+
+
+KEYPOINTS = 17           # COCO keypoints per person (keypoint_grounding_net.py:16)
+MAX_PERSONS = 8          # the shipped checkpoint's max_persons_per_image: 136 grounding tokens (gl_create's limit for the family)
 
 
 @dataclass(frozen=True)
@@ -36,7 +40,9 @@ class UNetConfig:
     split_weights: bool = False
     # the grounding tokenizer (config['model']['params']['grounding_tokenizer']['target']): "text" = text_grounding_net.PositionNet (one token
     # per box), "text_image" = text_image_grounding_net.PositionNet (GLIGEN's *_box_text_image checkpoints: a text token and an image token
-    # per box, gl_unet_config.grounding = 1)
+    # per box, gl_unet_config.grounding = 1), "keypoint" = keypoint_grounding_net.PositionNet (checkpoint_generation_keypoint.pth: one token
+    # per keypoint of up to max_persons people, 17 each, from 2-D points and two learned tables; gl_unet_config.grounding = 2; there max_objs
+    # counts TOKENS, 17 * max_persons, and pos_in_dim is the person-feature width = pos_out_dim)
     grounding: str = "text"
     # GLIGEN's inpainting checkpoints (checkpoint_inpainting_text*.pth; openaimodel.py:293-299, :436-439): the first conv also reads the masked
     # image latent and the mask, cat([x, z0 * mask, mask]) -- in_channels stays the LATENT's channel count (gl_unet_config.inpaint_mode)
@@ -53,8 +59,15 @@ class UNetConfig:
 
     @property
     def n_ground(self) -> int:
-        """grounding tokens per sample, the extra keys of the gated self-attention: max_objs (text) or 2 * max_objs (text_image)"""
+        """grounding tokens per sample, the extra keys of the gated self-attention: max_objs (text, keypoint) or 2 * max_objs (text_image)"""
         return self.max_objs * (2 if self.grounding == "text_image" else 1)
+
+    @property
+    def max_persons(self) -> int:
+        """people per image of a keypoint model (keypoint_grounding_net.py:10): max_objs = 17 * max_persons tokens"""
+        if self.grounding != "keypoint":
+            raise AttributeError(f"max_persons: grounding = {self.grounding!r} has boxes, not persons")
+        return self.max_objs // KEYPOINTS
 
     @property
     def time_embed_dim(self) -> int:
@@ -62,23 +75,30 @@ class UNetConfig:
 
     @property
     def position_dim(self) -> int:
-        return self.fourier_freqs * 2 * 4
+        """Fourier features of one location: sin & cos per frequency of the 4 box coordinates, or of the 2 of a keypoint"""
+        return self.fourier_freqs * 2 * (2 if self.grounding == "keypoint" else 4)
 
     @staticmethod
-    def from_dict(params: dict, allow_inpaint: bool = False) -> "UNetConfig":
+    def from_dict(params: dict, allow_inpaint: bool = False, allow_keypoint: bool = False) -> "UNetConfig":
         """Accepts the ``config['model']['params']`` dict of a GLIGEN checkpoint.
 
         ``allow_inpaint``: an ``inpaint_mode`` checkpoint (9-channel first conv) shares every parameter name with the layout-to-image UNet but
         needs ``inpainting_extra_input`` on every forward, so a caller has to say that it supplies one (``interface.load_ckpt`` does); without
-        the flag such a config keeps raising, like the other look-alike variants below."""
+        the flag such a config keeps raising, like the other look-alike variants below.
+
+        ``allow_keypoint``: the same for a keypoint checkpoint (``keypoint_grounding_net.PositionNet``): it is fed ``points`` and ``masks``
+        where the box families take boxes and embeddings, so a caller has to say that it supplies them (``interface.load_ckpt`` does)."""
         gt = (params.get("grounding_tokenizer") or {}).get("params", {})
         target = (params.get("grounding_tokenizer") or {}).get("target")
         if target is None or target.endswith(".text_grounding_net.PositionNet") or target == "text_grounding_net.PositionNet":
             grounding = "text"
         elif target.endswith("text_image_grounding_net.PositionNet"):
             grounding = "text_image"
+        elif target.endswith("keypoint_grounding_net.PositionNet") and allow_keypoint:
+            grounding = "keypoint"
         else:
-            raise NotImplementedError(f"grounding_tokenizer target {target!r}: only the text and text_image PositionNets are supported")
+            raise NotImplementedError(f"grounding_tokenizer target {target!r}: only the text and text_image PositionNets are supported (and the "
+                                      "keypoint one with allow_keypoint=True, fed points and masks: interface.load_ckpt / run_one_image do)")
         # variants that share parameter names / shapes with this UNet but compute something else must not load silently
         # (load_state_dict(strict=False), interface.py:91, would accept them): openaimodel.py:246-262, attention.py:362-384
         if params.get("fuser_type", "gatedSA") != "gatedSA":
@@ -93,7 +113,19 @@ class UNetConfig:
             raise NotImplementedError("grounding_downsampler is not on the text_layout path")
         if not params.get("use_spatial_transformer", True):
             raise NotImplementedError("use_spatial_transformer=False is not supported")
-        return UNetConfig(
+        kp = {}
+        if grounding == "keypoint":
+            if params.get("inpaint_mode", False):
+                raise NotImplementedError("a keypoint grounding tokenizer with inpaint_mode: no such checkpoint exists, and the inpainting mask is "
+                                          "drawn from boxes")
+            if "max_persons_per_image" not in gt:
+                raise ValueError("keypoint grounding_tokenizer params need max_persons_per_image")
+            P = int(gt["max_persons_per_image"])
+            if not 1 <= P <= MAX_PERSONS:
+                raise ValueError(f"max_persons_per_image = {P}: 1 .. {MAX_PERSONS} are supported ({KEYPOINTS} grounding tokens per person)")
+            # keypoint_grounding_net.py:10-31: one width, out_dim, for the person features and the tokens; 17 P tokens
+            kp = dict(max_objs=KEYPOINTS * P, pos_in_dim=int(gt.get("out_dim", 768)), relation=False)
+        cfg = UNetConfig(
             image_size=int(params.get("image_size", 64)),
             in_channels=int(params.get("in_channels", 4)),
             model_channels=int(params.get("model_channels", 320)),
@@ -109,6 +141,7 @@ class UNetConfig:
             grounding=grounding,
             inpaint_mode=bool(params.get("inpaint_mode", False)),
         )
+        return replace(cfg, **kp) if kp else cfg
 
 
 # A small config used by tests (CPU goldens and the GPU whole-model parity test).
@@ -319,6 +352,20 @@ def param_shapes(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
         out["position_net.null_text_feature"] = (cfg.pos_in_dim,)
         out["position_net.null_image_feature"] = (cfg.pos_in_dim,)
         out["position_net.null_position_feature"] = (cfg.position_dim,)
+        return out
+    if cfg.grounding == "keypoint":
+        # keypoint_grounding_net.py:15-31, in the order of the module's state dict (its own parameters, then the linears)
+        D = cfg.pos_out_dim
+        out["position_net.person_embeddings"] = (cfg.max_persons, D)
+        out["position_net.keypoint_embeddings"] = (KEYPOINTS, D)
+        out["position_net.null_person_feature"] = (D,)
+        out["position_net.null_xy_feature"] = (cfg.position_dim,)
+        out["position_net.linears.0.weight"] = (512, D + cfg.position_dim)
+        out["position_net.linears.0.bias"] = (512,)
+        out["position_net.linears.2.weight"] = (512, 512)
+        out["position_net.linears.2.bias"] = (512,)
+        out["position_net.linears.4.weight"] = (D, 512)
+        out["position_net.linears.4.bias"] = (D,)
         return out
     if cfg.grounding != "text":
         raise ValueError(f"grounding = {cfg.grounding!r}")

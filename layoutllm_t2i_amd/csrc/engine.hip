@@ -319,6 +319,12 @@ void for_all_layers(gl_engine* e, F f) {
     for (auto& b : e->output_blocks) for (auto& l : b.layers) f(l);
 }
 
+// row width of the PositionNet's MLP input = K of its first layer: in_dim + 8 F Fourier features of a box (a multiple of 64, gl_create), or on a
+// keypoint handle D + 4 F of an xy pair rounded UP to a multiple of 64 (the input kernel writes the pad columns, the table pads the weight)
+inline int pin_width(const gl_unet_config& c) {
+    return c.grounding == 2 ? (c.pos_in_dim + 4 * c.fourier_freqs + 63) / 64 * 64 : c.pos_in_dim + 8 * c.fourier_freqs;
+}
+
 // the packed-weight table, in the order weights.pack_state_dict produces its tensors
 void build_table(gl_engine* e) {
     const gl_unet_config& c = e->cfg;
@@ -395,6 +401,18 @@ void build_table(gl_engine* e) {
         }
         return;
     }
+    if (c.grounding == 2) {
+        // keypoint PositionNet (keypoint_grounding_net.py:15-31): two learned tables and two null features (fp32: the input kernel sums and
+        // blends them), one MLP whose first layer's K = D + 4 F is zero-padded to the GEMMs' multiple of 64 (800 -> 832)
+        add_w(e, "position_net.person_emb", 1, {c.max_objs / 17, c.pos_in_dim});
+        add_w(e, "position_net.keypoint_emb", 1, {17, c.pos_in_dim});
+        add_w(e, "position_net.null_person", 1, {c.pos_in_dim});
+        add_w(e, "position_net.null_xy", 1, {4 * c.fourier_freqs});
+        add_lin(e, "position_net.linears.0", 512, pin_width(c));
+        add_lin(e, "position_net.linears.2", 512, 512);
+        add_lin(e, "position_net.linears.4", c.pos_out_dim, 512);
+        return;
+    }
     add_w(e, "position_net.null_pos", 1, {c.pos_in_dim});
     add_w(e, "position_net.null_xyxy", 1, {8 * c.fourier_freqs});
     add_lin(e, "position_net.linears.0", 512, c.pos_in_dim + 8 * c.fourier_freqs);
@@ -404,7 +422,8 @@ void build_table(gl_engine* e) {
 
 // input channels of input_blocks.0.0: the latent, + the masked latent and the mask of an inpaint_mode handle (openaimodel.py:293-299)
 inline int first_conv_in(const gl_unet_config& c) { return c.in_channels + (c.inpaint_mode ? c.in_channels + 1 : 0); }
-// grounding tokens per sample (the fuser's extra keys): max_objs for the text PositionNet, 2 * max_objs for text_image
+// grounding tokens per sample (the fuser's extra keys): max_objs for the text PositionNet, 2 * max_objs for text_image; a keypoint handle's
+// max_objs already counts tokens (17 per person)
 inline int n_ground(const gl_unet_config& c) { return c.grounding == 1 ? 2 * c.max_objs : c.max_objs; }
 
 inline int vt_ld(int Nk) {
@@ -833,7 +852,8 @@ int spatial_transformer(Run& r, const LayerD& l, int li, Stream2 xin, int sh, in
         // [x ; objs] rows per sample padded to a multiple of 8 so that the QKV epilogue can store V^T in 16-byte pieces; the
         // pad rows are never normalised into (arbitrary finite-or-not contents): as keys they are masked by the attention
         // kernel (Nk = N + ng), as queries they are not used (Nq = N).  ng = the grounding-token count (n_ground): max_objs, or
-        // 2 * max_objs on a text_image handle; the relation chain below keeps mo = max_objs boxes
+        // 2 * max_objs on a text_image handle, up to 136 (17 per person) on a keypoint handle; the relation chain below keeps
+        // mo = max_objs boxes
         const int rows = N + ((ng + 7) & ~7);
         half_t* cat = e->h16("st.cat", (size_t)Bn * rows * lnw);
         CKP(cat);
@@ -1101,9 +1121,16 @@ extern "C" int gl_create(const gl_unet_config* cfg, gl_engine** out) {
     if (!cfg || !out) return GL_ERR_BAD_ARG;
     if (cfg->n_levels <= 0 || cfg->n_levels > 8 || cfg->n_attn_res < 0 || cfg->n_attn_res > 8 || cfg->num_heads <= 0) return GL_ERR_BAD_ARG;
     if (cfg->model_channels % 64 || cfg->context_dim % 64 || cfg->pos_in_dim % 8 || cfg->pos_out_dim != cfg->context_dim) return GL_ERR_UNSUPPORTED;
-    if ((cfg->pos_in_dim + 8 * cfg->fourier_freqs) % 64) return GL_ERR_UNSUPPORTED;
-    if (cfg->grounding != 0 && cfg->grounding != 1) return GL_ERR_UNSUPPORTED;
-    if (cfg->max_objs <= 0 || n_ground(*cfg) > 64) return GL_ERR_UNSUPPORTED;
+    if (cfg->grounding < 0 || cfg->grounding > 2 || cfg->max_objs <= 0) return GL_ERR_UNSUPPORTED;
+    if (cfg->grounding == 2) {
+        // keypoint: 17 tokens per person, at most 8 persons; the first MLP layer's K is padded (pin_width), so no % 64 rule on it; no relation
+        // chain (it pools over boxes) and no inpainting (its mask is drawn from boxes)
+        if (cfg->no_relation != 1 || cfg->inpaint_mode != 0 || (cfg->max_objs % 17) != 0 || cfg->max_objs > 136) return GL_ERR_UNSUPPORTED;
+        if (cfg->pos_in_dim != cfg->pos_out_dim) return GL_ERR_UNSUPPORTED;
+    } else {
+        if ((cfg->pos_in_dim + 8 * cfg->fourier_freqs) % 64) return GL_ERR_UNSUPPORTED;
+        if (n_ground(*cfg) > 64) return GL_ERR_UNSUPPORTED;
+    }
     if (cfg->no_relation != 0 && cfg->no_relation != 1) return GL_ERR_UNSUPPORTED;
     if ((cfg->inpaint_mode != 0 && cfg->inpaint_mode != 1) || first_conv_in(*cfg) > CIN_PAD) return GL_ERR_UNSUPPORTED;
     gl_engine* e = new gl_engine();
@@ -1171,6 +1198,55 @@ extern "C" int gl_load_weights(gl_engine* e, const void* packed, int64_t bytes, 
     return 0;
 }
 
+// ---- the grounding family of a handle (gl_unet_config.grounding), everything the conditioning code asks of it, in one place:
+//   GroundIn      the grounding tensors a conditioning entry takes.  loc: boxes [Bn, mo, 4], or points [Bn, mo, 2] on a keypoint handle; emb: the
+//                 phrase embeddings (positive_embeddings of the text PositionNet, text_embeddings of the text_image one); text_masks / image_masks
+//                 / image_emb: the three further inputs of a text_image handle.  What a family does not take stays NULL
+//   kept_inputs   those of them the family reads, with the pool tags a split_weights handle keeps device copies under for the lazy strict hoists
+//   posnet_input  the kernel that builds the MLP input rows of every chain ([nch, Bn * mo] chain-major rows of pin_width columns)
+//   posnet_chains / posnet_chain   the MLP chains those rows feed
+struct GroundIn { const float *loc = nullptr, *masks = nullptr, *emb = nullptr, *text_masks = nullptr, *image_masks = nullptr, *image_emb = nullptr; };
+struct KeptIn { const char* tag; const float* GroundIn::*field; size_t n; };
+
+static std::vector<KeptIn> kept_inputs(const gl_unet_config& c, int Bn) {
+    const size_t rows = (size_t)Bn * c.max_objs;
+    if (c.grounding == 2) return {{"cond.in.points", &GroundIn::loc, rows * 2}, {"cond.in.masks", &GroundIn::masks, rows}};
+    std::vector<KeptIn> k{{"cond.in.boxes", &GroundIn::loc, rows * 4}, {"cond.in.masks", &GroundIn::masks, rows}, {"cond.in.posemb", &GroundIn::emb, rows * c.pos_in_dim}};
+    if (c.grounding == 1) {
+        k.push_back({"cond.in.tmasks", &GroundIn::text_masks, rows});
+        k.push_back({"cond.in.imasks", &GroundIn::image_masks, rows});
+        k.push_back({"cond.in.imgemb", &GroundIn::image_emb, rows * c.pos_in_dim});
+    }
+    return k;
+}
+static int posnet_chains(const gl_unet_config& c) { return c.grounding == 1 ? 2 : 1; }      // text (+ image); one for text and for keypoint
+static const char* posnet_chain(const gl_unet_config& c, int chain) {
+    return c.grounding != 1 ? "position_net.linears" : (chain == 0 ? "position_net.linears_text" : "position_net.linears_image");
+}
+// out: fp16 rows, or fp32 rows with f32 (the strict chain, split into [hi | lo] afterwards)
+static int posnet_input(gl_engine* e, const GroundIn& in, int Bn, bool f32, void* out, hipStream_t st) {
+    const gl_unet_config& c = e->cfg;
+    const int rows = Bn * c.max_objs, F = c.fourier_freqs;
+    float* o32 = reinterpret_cast<float*>(out);
+    if (c.grounding == 2) {
+        const float *pe = e->Wf("position_net.person_emb"), *ke = e->Wf("position_net.keypoint_emb"), *np = e->Wf("position_net.null_person"),
+                    *nx = e->Wf("position_net.null_xy");
+        return f32 ? gl_posnet_input_kp_f32(in.loc, in.masks, pe, ke, np, nx, Bn, c.max_objs, c.pos_in_dim, F, o32, st)
+                   : gl_posnet_input_kp(in.loc, in.masks, pe, ke, np, nx, Bn, c.max_objs, c.pos_in_dim, F, out, st);
+    }
+    if (c.grounding == 1) {
+        const float *nt = e->Wf("position_net.null_text"), *ni = e->Wf("position_net.null_image"), *nx = e->Wf("position_net.null_xyxy");
+        const size_t o = (size_t)rows * pin_width(c);            // the image chain's rows follow the text chain's
+        return f32 ? gl_posnet_input_ti_f32(in.loc, in.masks, in.text_masks, in.image_masks, in.emb, in.image_emb, nt, ni, nx, rows, c.pos_in_dim, F, o32,
+                                            o32 + o, st)
+                   : gl_posnet_input_ti(in.loc, in.masks, in.text_masks, in.image_masks, in.emb, in.image_emb, nt, ni, nx, rows, c.pos_in_dim, F, out,
+                                        reinterpret_cast<half_t*>(out) + o, st);
+    }
+    const float *np = e->Wf("position_net.null_pos"), *nx = e->Wf("position_net.null_xyxy");
+    return f32 ? gl_posnet_input_f32(in.loc, in.masks, in.emb, np, nx, rows, c.pos_in_dim, F, o32, st)
+               : gl_posnet_input(in.loc, in.masks, in.emb, np, nx, rows, c.pos_in_dim, F, out, st);
+}
+
 // Strict mode's hoists (handles created with split_weights): the conditioning tensors from split-fp16 operands all the way -- PositionNet on fp32
 // inputs split into [hi | lo], every Linear with [hi | lo] activations (+ the third pass x.Wlo, key 51), K / V of the text context as
 // [k v | k_lo v_lo] rows with V^T hi / lo, fuser.linear(objs) in fp32.  Computed LAZILY: gl_set_conditioning keeps device copies of
@@ -1180,19 +1256,14 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
     const gl_unet_config& cfg = e->cfg;
     const int Bn = e->Bn, Lc = e->Lc, mo = cfg.max_objs, ng = n_ground(cfg), ctx = cfg.context_dim, H = cfg.num_heads;
     const bool ti = cfg.grounding == 1;
-    const int nch = ti ? 2 : 1;                      // MLP chains of the PositionNet: text (+ image)
-    const int pin_dim = cfg.pos_in_dim + 8 * cfg.fourier_freqs;
+    const int nch = posnet_chains(cfg);
+    const int pin_dim = pin_width(cfg);
     const float* context = e->f32("cond.in.context", (size_t)Bn * Lc * ctx);
-    const float* boxes = e->f32("cond.in.boxes", (size_t)Bn * mo * 4);
-    const float* masks = e->f32("cond.in.masks", (size_t)Bn * mo);
-    const float* pos_emb = e->f32("cond.in.posemb", (size_t)Bn * mo * cfg.pos_in_dim);
-    CKP(context); CKP(boxes); CKP(masks); CKP(pos_emb);
-    const float *text_masks = nullptr, *image_masks = nullptr, *image_emb = nullptr;
-    if (ti) {
-        text_masks = e->f32("cond.in.tmasks", (size_t)Bn * mo);
-        image_masks = e->f32("cond.in.imasks", (size_t)Bn * mo);
-        image_emb = e->f32("cond.in.imgemb", (size_t)Bn * mo * cfg.pos_in_dim);
-        CKP(text_masks); CKP(image_masks); CKP(image_emb);
+    CKP(context);
+    GroundIn in;                                     // the device copies set_conditioning kept
+    for (const KeptIn& k : kept_inputs(cfg, Bn)) {
+        in.*(k.field) = e->f32(k.tag, k.n);
+        CKP(in.*(k.field));
     }
     Run r{e, st, e->buf("splitk.ws", GL_WS_BYTES)};
     CKP(r.ws);
@@ -1210,20 +1281,13 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
     half_t* objss = e->h16("pn.objss", nch * rows * 2 * D);
     half_t* ctxs = e->h16("cond.ctxs", (size_t)Bn * Lc * 2 * ctx);
     CKP(pin32); CKP(pins); CKP(h1s); CKP(h2s); CKP(objss); CKP(ctxs);
-    if (ti) {
-        CK(gl_posnet_input_ti_f32(boxes, masks, text_masks, image_masks, pos_emb, image_emb, e->Wf("position_net.null_text"),
-                                  e->Wf("position_net.null_image"), e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim, cfg.fourier_freqs, pin32,
-                                  pin32 + rows * pin_dim, st));
-    } else {
-        CK(gl_posnet_input_f32(boxes, masks, pos_emb, e->Wf("position_net.null_pos"), e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim,
-                               cfg.fourier_freqs, pin32, st));
-    }
+    CK(posnet_input(e, in, Bn, true, pin32, st));
     CK(r.split(pin32, (int64_t)(nch * rows), pin_dim, pins));
     auto lin = [&](const half_t* a, int k, const std::string& w, void* out, int ldc, int out_mode, int epi, size_t m) {
         return r.gemm({a, 2 * k, true}, w, (int)m, out, ldc, {.out_mode = out_mode, .epi = epi});
     };
     for (int c = 0; c < nch; ++c) {                  // chain c on rows [c * rows, (c + 1) * rows) of every buffer
-        const std::string pw = !ti ? "position_net.linears" : (c == 0 ? "position_net.linears_text" : "position_net.linears_image");
+        const std::string pw = posnet_chain(cfg, c);
         const size_t o = c * rows;
         CK(lin(pins + o * 2 * pin_dim, pin_dim, pw + ".0", h1s + o * 2 * 512, 2 * 512, GL_OUT_F16_HILO, GL_EPI_SILU, rows));
         CK(lin(h1s + o * 2 * 512, 512, pw + ".2", h2s + o * 2 * 512, 2 * 512, GL_OUT_F16_HILO, GL_EPI_SILU, rows));
@@ -1260,12 +1324,10 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
 }
 
 namespace {
-// pos_emb: the phrase embeddings (positive_embeddings of the text PositionNet, text_embeddings of the text_image one); text_masks /
-// image_masks / image_emb: the three further inputs of a text_image handle (text_image_grounding_net.py:41), NULL on a text handle
-int set_conditioning(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks, const float* pos_emb,
-                     const float* text_masks, const float* image_masks, const float* image_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t h,
+int set_conditioning(gl_engine* e, const float* context, const float* relations, const GroundIn& in, int32_t Bn, int32_t Lc, int32_t R, int32_t h,
                      int32_t w, void* stream) {
-    if (!e || !e->wbase || !context || !boxes || !masks || !pos_emb || Bn <= 0 || Lc <= 0 || h <= 0 || w <= 0) return GL_ERR_BAD_ARG;
+    if (!e || !e->wbase || !context || Bn <= 0 || Lc <= 0 || h <= 0 || w <= 0) return GL_ERR_BAD_ARG;
+    for (const KeptIn& k : kept_inputs(e->cfg, Bn)) if (in.*(k.field) == nullptr) return GL_ERR_BAD_ARG;      // every tensor the family reads
     const bool rel = e->cfg.no_relation == 0;
     if (rel && (!relations || R <= 0)) return GL_ERR_BAD_ARG;
     if (!rel) { relations = nullptr; R = 0; }       // a no_relation handle ignores both (R = 0 in its graph keys)
@@ -1274,16 +1336,15 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     hipStream_t st = (hipStream_t)stream;
     const int mo = cfg.max_objs, ng = n_ground(cfg), ctx = cfg.context_dim, H = cfg.num_heads;
     const bool ti = cfg.grounding == 1;
-    const int nch = ti ? 2 : 1;
-    if (ti && (!text_masks || !image_masks || !image_emb)) return GL_ERR_BAD_ARG;
+    const int nch = posnet_chains(cfg);
     if (Bn != e->Bn || Lc != e->Lc || R != e->R || h != e->lat_h || w != e->lat_w) e->drop_graphs();     // shapes are part of the graph keys anyway
     if (h != e->lat_h || w != e->lat_w) e->extra_set = false;       // the inpainting extra was sized for the previous latent shape
     e->pool_changed = false;
     e->Bn = Bn; e->Lc = Lc; e->R = R; e->lat_h = h; e->lat_w = w;
     Run r{e, st, e->buf("splitk.ws", GL_WS_BYTES)};
     CKP(r.ws);
-    // --- grounding tokens: PositionNet (text_grounding_net.py:26-43)
-    const int pin_dim = cfg.pos_in_dim + 8 * cfg.fourier_freqs;
+    // --- grounding tokens: PositionNet (text_grounding_net.py:26-43; keypoint_grounding_net.py:34-58: one chain over Bn * 17 P rows)
+    const int pin_dim = pin_width(cfg);
     // (text_image_grounding_net.py:41-62: two chains, text then image, chain-major [nch, Bn * mo] rows until the final concatenation)
     const size_t crow = (size_t)Bn * mo;
     const int D = cfg.pos_out_dim;
@@ -1295,15 +1356,9 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     half_t* rel16 = rel ? e->h16("cond.rel", (size_t)Bn * R * ctx) : nullptr;
     CKP(pin); CKP(h1); CKP(h2); CKP(objs); CKP(ctx16);
     if (rel) CKP(rel16);
-    if (ti) {
-        CK(gl_posnet_input_ti(boxes, masks, text_masks, image_masks, pos_emb, image_emb, e->Wf("position_net.null_text"), e->Wf("position_net.null_image"),
-                              e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim, cfg.fourier_freqs, pin, pin + crow * pin_dim, st));
-    } else {
-        CK(gl_posnet_input(boxes, masks, pos_emb, e->Wf("position_net.null_pos"), e->Wf("position_net.null_xyxy"), Bn * mo, cfg.pos_in_dim,
-                           cfg.fourier_freqs, pin, st));
-    }
+    CK(posnet_input(e, in, Bn, false, pin, st));
     for (int c = 0; c < nch; ++c) {
-        const std::string pw = !ti ? "position_net.linears" : (c == 0 ? "position_net.linears_text" : "position_net.linears_image");
+        const std::string pw = posnet_chain(cfg, c);
         const size_t o = c * crow;
         CK(r.gemm({pin + o * pin_dim, pin_dim}, pw + ".0", Bn * mo, h1 + o * 512, 512, {.epi = GL_EPI_SILU}));
         CK(r.gemm({h1 + o * 512, 512}, pw + ".2", Bn * mo, h2 + o * 512, 512, {.epi = GL_EPI_SILU}));
@@ -1351,19 +1406,13 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     //     when the handle is in strict mode at this point, else with the first strict forward
     e->strict_hoists_ok = false;
     if (cfg.split_weights) {
-        // (the last three: a text_image handle's further inputs; src == NULL on a text handle)
-        struct { const char* tag; const float* src; size_t n; } keep[] = {{"cond.in.context", context, (size_t)Bn * Lc * ctx},
-                                                                          {"cond.in.boxes", boxes, (size_t)Bn * mo * 4},
-                                                                          {"cond.in.masks", masks, (size_t)Bn * mo},
-                                                                          {"cond.in.posemb", pos_emb, (size_t)Bn * mo * cfg.pos_in_dim},
-                                                                          {"cond.in.tmasks", text_masks, (size_t)Bn * mo},
-                                                                          {"cond.in.imasks", image_masks, (size_t)Bn * mo},
-                                                                          {"cond.in.imgemb", image_emb, (size_t)Bn * mo * cfg.pos_in_dim}};
-        for (auto& k : keep) {
-            if (k.src == nullptr) continue;
+        float* cdst = e->f32("cond.in.context", (size_t)Bn * Lc * ctx);
+        CKP(cdst);
+        if (hipMemcpyAsync(cdst, context, (size_t)Bn * Lc * ctx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
+        for (const KeptIn& k : kept_inputs(cfg, Bn)) {
             float* dst = e->f32(k.tag, k.n);
             CKP(dst);
-            if (hipMemcpyAsync(dst, k.src, k.n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
+            if (hipMemcpyAsync(dst, in.*(k.field), k.n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
         }
         if (g_strict != 0) CK(strict_hoists(e, st));
     }
@@ -1385,7 +1434,7 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
             int* nvalid = reinterpret_cast<int*>(e->buf("cond.nvalid." + ss, (size_t)Bn * 4));
             int* poison = reinterpret_cast<int*>(e->buf("cond.poison." + ss, (size_t)Bn * 4));
             CKP(rects); CKP(nvalid); CKP(poison);
-            rela_rects_kernel<<<dim3((Bn + 63) / 64), dim3(64), 0, st>>>(boxes, masks, Bn, mo, s.first, s.second, rects, nvalid, poison);
+            rela_rects_kernel<<<dim3((Bn + 63) / 64), dim3(64), 0, st>>>(in.loc, in.masks, Bn, mo, s.first, s.second, rects, nvalid, poison);
             GL_CHECK_LAUNCH();
         }
         // Rows of the relation chain (attention.py:348-351 runs LN / cross-attention / FeedForward over all 30 rows of every sample; only
@@ -1418,8 +1467,9 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
 // the grounding family is a property of the handle: each family has its own conditioning entries
 static int wrong_family(gl_engine* e, const char* entry, int want) {
     if (e->cfg.grounding == want) return 0;
-    e->err = std::string(entry) + (want == 1 ? ": the handle was created with grounding = 0 (text); use gl_set_conditioning / gl_set_conditioning_hw"
-                                             : ": the handle was created with grounding = 1 (text_image); use gl_set_conditioning_ti");
+    static const char* const made[3] = {"0 (text)", "1 (text_image)", "2 (keypoint)"};
+    static const char* const use[3] = {"gl_set_conditioning / gl_set_conditioning_hw", "gl_set_conditioning_ti", "gl_set_conditioning_kp"};
+    e->err = std::string(entry) + ": the handle was created with grounding = " + made[e->cfg.grounding] + "; use " + use[e->cfg.grounding];
     return GL_ERR_BAD_ARG;
 }
 // an axis that is not a multiple of 2^(number of downsamples) comes back shorter than the skip tensor it is concatenated with
@@ -1437,7 +1487,7 @@ extern "C" int gl_set_conditioning(gl_engine* e, const float* context, const flo
                                    const float* pos_emb, int32_t Bn, int32_t Lc, int32_t R, int32_t hw, void* stream) {
     if (!e) return GL_ERR_BAD_ARG;
     CK(wrong_family(e, "gl_set_conditioning", 0));
-    return set_conditioning(e, context, relations, boxes, masks, pos_emb, nullptr, nullptr, nullptr, Bn, Lc, R, hw, hw, stream);
+    return set_conditioning(e, context, relations, GroundIn{boxes, masks, pos_emb}, Bn, Lc, R, hw, hw, stream);
 }
 
 extern "C" int gl_set_conditioning_ti(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
@@ -1446,7 +1496,7 @@ extern "C" int gl_set_conditioning_ti(gl_engine* e, const float* context, const 
     if (!e) return GL_ERR_BAD_ARG;
     CK(wrong_family(e, "gl_set_conditioning_ti", 1));
     CK(check_hw(e, "gl_set_conditioning_ti", h, w));
-    return set_conditioning(e, context, relations, boxes, masks, text_emb, text_masks, image_masks, image_emb, Bn, Lc, R, h, w, stream);
+    return set_conditioning(e, context, relations, GroundIn{boxes, masks, text_emb, text_masks, image_masks, image_emb}, Bn, Lc, R, h, w, stream);
 }
 
 extern "C" int gl_set_conditioning_hw(gl_engine* e, const float* context, const float* relations, const float* boxes, const float* masks,
@@ -1456,7 +1506,15 @@ extern "C" int gl_set_conditioning_hw(gl_engine* e, const float* context, const 
     // every DOWN halves both axes and every UP doubles them back: an axis that is not a multiple of 2^(number of downsamples) comes back
     // shorter than the skip tensor it is concatenated with (the reference fails there too) -- rejected here, before anything is launched
     CK(check_hw(e, "gl_set_conditioning_hw", h, w));
-    return set_conditioning(e, context, relations, boxes, masks, pos_emb, nullptr, nullptr, nullptr, Bn, Lc, R, h, w, stream);
+    return set_conditioning(e, context, relations, GroundIn{boxes, masks, pos_emb}, Bn, Lc, R, h, w, stream);
+}
+
+extern "C" int gl_set_conditioning_kp(gl_engine* e, const float* context, const float* points, const float* masks, int32_t Bn, int32_t Lc, int32_t h,
+                                      int32_t w, void* stream) {
+    if (!e) return GL_ERR_BAD_ARG;
+    CK(wrong_family(e, "gl_set_conditioning_kp", 2));
+    CK(check_hw(e, "gl_set_conditioning_kp", h, w));
+    return set_conditioning(e, context, nullptr, GroundIn{points, masks}, Bn, Lc, 0, h, w, stream);
 }
 
 extern "C" int gl_set_inpaint_extra(gl_engine* e, const float* extra, int32_t Bs, void* stream) {

@@ -65,6 +65,39 @@ __global__ __launch_bounds__(256) void posnet_input_ti_kernel(const float* __res
     }
 }
 
+// keypoint_grounding_net.py:39-56 + util.py:12-26.  One block per (b, t) token row, t in [0, tokens = 17 P): person t / 17, keypoint t % 17.
+// out row (ld columns, ld = D + 4 F rounded up to 64) = [ (person_emb[t / 17] + keypoint_emb[t % 17]) * m + (1 - m) * null_person  (D)
+//                                                        | fourier(point) * m + (1 - m) * null_xy                                (4 F)
+//                                                        | 0 (the pad columns of the padded-K linears.0, written here)          ]
+// in fp32, the table sum first and then the blend, as the reference orders them; m is a blend factor (any value), not a select.
+// Fourier order: for each frequency f_j = 100^(j/num_freqs): sin(f_j x), sin(f_j y), cos(f_j x), cos(f_j y).
+template <typename OT>
+__global__ __launch_bounds__(256) void posnet_input_kp_kernel(const float* __restrict__ points, const float* __restrict__ masks,
+                                                              const float* __restrict__ person_emb, const float* __restrict__ keypoint_emb,
+                                                              const float* __restrict__ null_person, const float* __restrict__ null_xy, int tokens,
+                                                              int D, int num_freqs, int ld, OT* __restrict__ out) {
+    const int row = blockIdx.x;
+    const int t = row % tokens;
+    const float m = masks[row];
+    const int pos_dim = num_freqs * 4;
+    const float* pe = person_emb + (size_t)(t / 17) * D;
+    const float* ke = keypoint_emb + (size_t)(t % 17) * D;
+    OT* o = out + (size_t)row * ld;
+    for (int c = threadIdx.x; c < D; c += 256) {
+        const float s = pe[c] + ke[c];
+        o[c] = (OT)(s * m + (1.0f - m) * null_person[c]);
+    }
+    for (int c = threadIdx.x; c < pos_dim; c += 256) {
+        const int j = c / 4;
+        const int r = c - j * 4;
+        const float freq = powf(100.0f, (float)j / (float)num_freqs);
+        const float arg = freq * points[(size_t)row * 2 + (r & 1)];
+        const float e = (r < 2) ? sinf(arg) : cosf(arg);
+        o[D + c] = (OT)(e * m + (1.0f - m) * null_xy[c]);
+    }
+    for (int c = D + pos_dim + threadIdx.x; c < ld; c += 256) o[c] = (OT)0.0f;
+}
+
 // interface.py:126-129: out = norm * (f P) / || f P ||_2 per image, fp32.  f [n, dim], P [dim, dim] row-major (project(feature, P.T) =
 // feature @ P), one block of 256 threads per image, dim <= 1024: thread t owns output columns t, t + 256, ... (coalesced reads of P's rows).
 // Deliberately one block per image, so a single image streams all of P (2.4 MB at dim 768) through one CU: this runs once per distinct
@@ -400,6 +433,31 @@ extern "C" int gl_posnet_input_ti_f32(const float* boxes, const float* masks, co
                                                                                      null_image, null_xyxy, in_dim, num_freqs, out_text, out_image);
     GL_CHECK_LAUNCH();
     return 0;
+}
+
+template <typename OT>
+static int posnet_input_kp(const float* points, const float* masks, const float* person_emb, const float* keypoint_emb, const float* null_person,
+                           const float* null_xy, int32_t B, int32_t tokens, int32_t D, int32_t num_freqs, OT* out, void* stream) {
+    if (!points || !masks || !person_emb || !keypoint_emb || !null_person || !null_xy || !out || B <= 0 || tokens <= 0 || (tokens % 17) != 0 || D <= 0 ||
+        num_freqs <= 0)
+        return GL_ERR_BAD_ARG;
+    const int ld = (D + 4 * num_freqs + 63) / 64 * 64;
+    posnet_input_kp_kernel<OT><<<dim3(B * tokens), dim3(256), 0, (hipStream_t)stream>>>(points, masks, person_emb, keypoint_emb, null_person, null_xy,
+                                                                                       tokens, D, num_freqs, ld, out);
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_posnet_input_kp(const float* points, const float* masks, const float* person_emb, const float* keypoint_emb,
+                                  const float* null_person, const float* null_xy, int32_t B, int32_t tokens, int32_t D, int32_t num_freqs, void* out,
+                                  void* stream) {
+    return posnet_input_kp(points, masks, person_emb, keypoint_emb, null_person, null_xy, B, tokens, D, num_freqs, reinterpret_cast<half_t*>(out), stream);
+}
+
+extern "C" int gl_posnet_input_kp_f32(const float* points, const float* masks, const float* person_emb, const float* keypoint_emb,
+                                      const float* null_person, const float* null_xy, int32_t B, int32_t tokens, int32_t D, int32_t num_freqs,
+                                      float* out, void* stream) {
+    return posnet_input_kp(points, masks, person_emb, keypoint_emb, null_person, null_xy, B, tokens, D, num_freqs, out, stream);
 }
 
 extern "C" int gl_image_ground_feature(const float* feat, const float* proj, int32_t n, int32_t dim, float norm, float* out, void* stream) {

@@ -107,6 +107,8 @@ class UNetEngine:
 
         An engine without the relation chain (``cfg.relation`` False, gl_unet_config.no_relation) takes ``relations=None`` and ignores a
         given tensor; on every other engine ``None`` raises ValueError before anything is launched."""
+        if self.cfg.grounding == "keypoint":
+            raise ValueError("a keypoint model is conditioned on points and masks (set_conditioning_kp), not on boxes and embeddings")
         rel_on = getattr(self.cfg, "relation", True)
         if not rel_on:
             relations = None
@@ -162,6 +164,31 @@ class UNetEngine:
         self.cond = dict(Bn=Bn, mo=mo, R=R, Lc=Lc, hw=hw, H=h, W=w)
 
     @torch.no_grad()
+    def set_conditioning_kp(self, context, points, masks, hw) -> None:
+        """The conditioning of a keypoint engine (``cfg.grounding == "keypoint"``, gl_set_conditioning_kp): context [Bn,77,ctx], points
+        [Bn,17P,2] (token t = keypoint t % 17 of person t // 17), masks [Bn,17P], fp32 tensors (any device); null grounding = zeros.
+        ``hw``: the latent side or ``(h, w)``, under the shape rule of the rectangular entry.  On an engine of another family: ValueError."""
+        if self.cfg.grounding != "keypoint":
+            raise ValueError(f"points / masks given to a {self.cfg.grounding} model: keypoint grounding needs a keypoint checkpoint")
+        h, w = (hw, hw) if isinstance(hw, int) else (int(v) for v in hw)
+        check_latent_hw(self.cfg, h, w)
+        dev = self.dev
+        f32 = lambda t: torch.as_tensor(t, dtype=F32).to(dev).contiguous()
+        context, points, masks = f32(context), f32(points), f32(masks)
+        Bn, mo = points.shape[0], self.cfg.max_objs
+        if tuple(points.shape) != (Bn, mo, 2) or tuple(masks.shape) != (Bn, mo):
+            raise ValueError(f"points {tuple(points.shape)} / masks {tuple(masks.shape)}: the model was built for {self.cfg.max_persons} persons, "
+                             f"[Bn, {mo}, 2] and [Bn, {mo}]")
+        if context.dim() != 3 or context.shape[0] != Bn or context.shape[-1] != self.cfg.context_dim:
+            raise ValueError("context does not match the batch or the model config")
+        Lc = context.shape[1]
+        with torch.cuda.device(dev):
+            self._check(self._lib.gl_set_conditioning_kp(self.handle, context.data_ptr(), points.data_ptr(), masks.data_ptr(), Bn, Lc, h, w,
+                                                         self._stream()), "gl_set_conditioning_kp")
+        self._cond_refs = (context, points, masks)      # read asynchronously by the launched kernels
+        self.cond = dict(Bn=Bn, mo=mo, R=0, Lc=Lc, hw=hw, H=h, W=w)
+
+    @torch.no_grad()
     def set_inpaint_extra(self, extra: torch.Tensor) -> None:
         """The ``inpainting_extra_input`` of an inpaint_mode model (gligen_inference.py:406-407: cat([z0 * mask, mask], dim=1)): fp32
         [1 | samples, in_channels + 1, h, w] at the conditioning's latent shape (gl_set_inpaint_extra).  The engine copies it into a pool
@@ -181,7 +208,7 @@ class UNetEngine:
 
     def _check(self, code: int, what: str) -> None:
         """``check`` with the handle's gl_last_error message: the entries of an inpaint_mode handle leave one for every refusal"""
-        if code != 0 and self.cfg.inpaint_mode:
+        if code != 0 and (self.cfg.inpaint_mode or self.cfg.grounding == "keypoint"):
             msg = _lib.last_error(self.handle)
             if msg:
                 raise _lib.HipLibraryError(f"{what} failed with code {code}: {msg}")

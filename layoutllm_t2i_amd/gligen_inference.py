@@ -25,6 +25,10 @@ here and additionally feeds ``cat([z0 * mask, mask])`` to the first conv on ever
 ``meta["input_image"]`` (ValueError otherwise).  A 4-channel text_layout / text_image checkpoint with ``input_image`` keeps running the
 latent-blend inpainting alone, which the reference refuses.
 
+A keypoint checkpoint (``checkpoint_generation_keypoint.pth``, ``keypoint_grounding_net.PositionNet``) takes ``meta["locations"]`` as a
+list of persons, each a list of 17 ``[x, y]`` in [0, 1] with ``[0, 0]`` for a missing keypoint (gligen_inference.py:199-218, :585-633); it
+needs neither ``phrases`` nor a CLIP model, and ``images`` / ``input_image`` raise ValueError.
+
 A checkpoint without ``rela_fuse`` tensors (every public GLIGEN checkpoint) runs on the upstream transformer block it was trained with
 (attention_original.py:312-316): no relation phrases are parsed or encoded for it.
 """
@@ -68,7 +72,10 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     if starting_noise is None:
         h, w = interface.latent_hw(_get(config, "height"), _get(config, "width"), all_models[1])
         starting_noise = torch.randn(bs, 4, h, w).to(device)
-    if clip_model is None or clip_processor is None:
+    # a keypoint checkpoint (the reference routes on "keypoint" in meta["ckpt"], gligen_inference.py:363; here the loaded model decides) is
+    # grounded on meta["locations"] = persons of 17 [x, y] alone: no phrases, and no CLIP model to create
+    keypoint = getattr(getattr(all_models[0], "cfg", None), "grounding", "text") == "keypoint"
+    if not keypoint and (clip_model is None or clip_processor is None):
         from transformers import CLIPModel, CLIPProcessor
         version = "openai/clip-vit-large-patch14"
         clip_model = CLIPModel.from_pretrained(version).to(device)

@@ -148,8 +148,12 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
     keeps the GLIGEN conv.  ``GLIGEN_ALLOW_NO_SD_CONV=1`` opts out explicitly (first_conv_restorable = False)."""
     saved_ckpt = torch.load(ckpt_path, map_location="cpu")
     config = saved_ckpt["config_dict"]["_content"]
-    cfg = UNetConfig.from_dict(config["model"]["params"], allow_inpaint=True)      # _run builds the inpainting extra such a model needs
+    # (_run builds the inpainting extra an inpaint_mode model needs, and the points / masks batch of a keypoint model)
+    cfg = UNetConfig.from_dict(config["model"]["params"], allow_inpaint=True, allow_keypoint=True)
     import dataclasses
+    if cfg.grounding == "keypoint" and any(".rela_fuse." in k for k in saved_ckpt["model"]):
+        raise NotImplementedError("a keypoint checkpoint with *.rela_fuse.* tensors: the relation chain pools image features over grounding "
+                                  "boxes, and a keypoint model has none (keypoint grounding runs on the upstream block only)")
     # a checkpoint without rela_fuse tensors (GLIGEN's own) runs on the upstream block, not on a default-initialised relation chain
     cfg = dataclasses.replace(cfg, relation=checkpoint_has_relation(saved_ckpt["model"], cfg))
     if strict is None:
@@ -194,7 +198,7 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
 def load_all_models(ckpt, device, strict=None):
     """interface.py:366-373 (``strict``: see load_ckpt)."""
     model, autoencoder, text_encoder, diffusion, config = load_ckpt(ckpt, device, strict=strict)
-    model.grounding_tokenizer_input = grounding_input_for(model.cfg)      # text, or text_image for a *_box_text_image checkpoint
+    model.grounding_tokenizer_input = grounding_input_for(model.cfg)      # text, text_image (*_box_text_image) or keypoint
     return model, autoencoder, text_encoder, diffusion, config
 
 
@@ -370,6 +374,39 @@ def prepare_batch(meta, model, processor, batch=1, max_objs=MAX_OBJS, device=Non
 
 
 @torch.no_grad()
+def prepare_batch_kp(meta, batch=1, max_persons=8, device=None):
+    """gligen_inference.py:199-218: ``meta["locations"]`` is a list of persons, each a list of 17 ``[x, y]`` in [0, 1] (a missing keypoint is
+    ``[0, 0]``); one pose layout repeated ``batch`` times.  Returns ``points`` [batch, 17 * max_persons, 2] and ``masks`` [batch, 17 * max_persons]
+    = ``points.mean(dim=1) != 0``, as the reference derives them.  More than ``max_persons`` persons (the reference runs off the end of its
+    tensor) and a person without exactly 17 points (the reference would misalign every later person) raise ValueError."""
+    points, masks = _one_sample_pose(meta["locations"], max_persons)
+    out = {"points": points.unsqueeze(0).repeat(batch, 1, 1), "masks": masks.unsqueeze(0).repeat(batch, 1)}
+    return {k: v.to(device) for k, v in out.items()} if device is not None else out
+
+
+def _one_sample_pose(persons, max_persons):
+    if len(persons) > max_persons:
+        raise ValueError(f"{len(persons)} persons, the checkpoint was built for at most {max_persons} (max_persons_per_image)")
+    points = torch.zeros(max_persons * 17, 2)
+    for p, kps in enumerate(persons):
+        if len(kps) != 17 or any(len(kp) != 2 for kp in kps):
+            raise ValueError(f"person {p} has {len(kps)} keypoints: each person is a list of 17 [x, y] pairs ([0, 0] = missing)")
+        points[17 * p:17 * (p + 1)] = torch.tensor(kps, dtype=torch.float32)
+    masks = ((points.mean(dim=1) != 0) * 1).float()
+    return points, masks
+
+
+@torch.no_grad()
+def prepare_batch_kp_multiple(meta, batch, max_persons=8, device=None):
+    """``prepare_batch_kp`` with one pose layout per prompt: ``meta["locations"][i]`` is prompt i's list of persons."""
+    if len(meta["locations"]) != batch:
+        raise ValueError(f"locations: {len(meta['locations'])} pose layouts for a batch of {batch}")
+    parts = [_one_sample_pose(persons, max_persons) for persons in meta["locations"]]
+    out = {"points": torch.stack([p for p, _ in parts], 0), "masks": torch.stack([m for _, m in parts], 0)}
+    return {k: v.to(device) for k, v in out.items()} if device is not None else out
+
+
+@torch.no_grad()
 def prepare_batch_multiple(meta, model, processor, batch=1, max_objs=MAX_OBJS, device=None):
     """interface.py:424-475: one layout per prompt."""
     phrases_batch = meta.get("phrases")
@@ -514,6 +551,11 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
         # (the reference would prepare image tokens and drop them silently: text_layout_tokinzer_input.py reads three keys)
         raise ValueError("meta['images'] given to a text-only checkpoint: image grounding needs a *_box_text_image checkpoint "
                          "(grounding_tokenizer target text_image_grounding_net.PositionNet)")
+    keypoint = getattr(model.cfg, "grounding", "text") == "keypoint"       # the batch builder follows the model, not the checkpoint's file name
+    if keypoint and meta.get("images") is not None:
+        raise ValueError("meta['images'] given to a keypoint checkpoint: it is grounded on poses (meta['locations'] = persons of 17 [x, y])")
+    if keypoint and meta.get("input_image") is not None:
+        raise ValueError("meta['input_image'] given to a keypoint checkpoint: the inpainting mask is drawn from boxes, and poses have none")
     inpaint_model = bool(getattr(model.cfg, "inpaint_mode", False))
     if inpaint_model and meta.get("input_image") is None:
         # (the reference would fail inside the first forward, on th.cat([h, None]), openaimodel.py:439)
@@ -528,12 +570,15 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     with_rel = bool(getattr(model.cfg, "relation", True))       # a checkpoint without rela_fuse: no scene-graph parse, no relation phrases
     relations = None
     if multiple:
-        batch = prepare_batch_multiple(meta, clip_model, clip_processor, bs, device=device)
+        # (a keypoint model: no phrases, no CLIP model, and -- always on the upstream block -- no relation phrases)
+        batch = prepare_batch_kp_multiple(meta, bs, model.cfg.max_persons, device) if keypoint else \
+            prepare_batch_multiple(meta, clip_model, clip_processor, bs, device=device)
         context = text_encoder.encode(meta["prompts"])
         if with_rel:
             relations = prepare_relation_phrases_batch(meta["prompts"], max_rel, text_encoder, device=device)
     else:
-        batch = prepare_batch(meta, clip_model, clip_processor, bs, device=device)
+        batch = prepare_batch_kp(meta, bs, model.cfg.max_persons, device) if keypoint else \
+            prepare_batch(meta, clip_model, clip_processor, bs, device=device)
         context = text_encoder.encode([meta["prompt"]] * bs)
         if with_rel:
             relations = prepare_relation_phrases(meta["prompt"], bs, max_rel, text_encoder, device=device)
@@ -569,13 +614,15 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
 
 @torch.no_grad()
 def run_one_image(all_models, args, meta, starting_noise=None, clip_model=None, clip_processor=None, device=None):
-    """interface.py:292-357.  ``meta["input_image"]`` (a path or a PIL.Image): inpaint that image inside the boxes."""
+    """interface.py:292-357.  ``meta["input_image"]`` (a path or a PIL.Image): inpaint that image inside the boxes.  On a keypoint checkpoint
+    ``meta["locations"]`` is a list of persons, each 17 ``[x, y]`` (prepare_batch_kp); no phrases, no CLIP model, no input image."""
     return _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple=False)
 
 
 @torch.no_grad()
 def run_batch_images(all_models, args, meta, starting_noise=None, clip_model=None, clip_processor=None, device=None):
-    """interface.py:478-549.  ``meta["input_image"]``: a list with one image (path or PIL.Image) per sample, or one for all."""
+    """interface.py:478-549.  ``meta["input_image"]``: a list with one image (path or PIL.Image) per sample, or one for all.  On a keypoint
+    checkpoint ``meta["locations"]`` holds one pose layout (a list of persons of 17 ``[x, y]``) per prompt; no phrases, no CLIP model."""
     return _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple=True)
 
 
@@ -662,7 +709,8 @@ def load_all_models_sharded(ckpt, device, src=0, strict=None):
         am = load_all_models(ckpt, device, strict=strict)
         model, autoencoder, text_encoder, diffusion, config = am
         if model.cfg.grounding != "text":
-            raise NotImplementedError("the sharded entry is text-only: a text_image checkpoint runs through load_all_models / run_batch_images")
+            raise NotImplementedError(f"the sharded entry is text-only: a {model.cfg.grounding} checkpoint runs through load_all_models / "
+                                      "run_batch_images")
         if model.cfg.inpaint_mode:
             raise NotImplementedError("the sharded entry has no input image: an inpaint_mode checkpoint runs through load_all_models / "
                                       "run_one_image / run_batch_images with meta['input_image']")

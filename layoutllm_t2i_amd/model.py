@@ -117,9 +117,38 @@ class TextImageGroundingNetInput:
                 "image_embeddings": z(batch, self.max_box, self.in_dim)}
 
 
+class KeypointGroundingNetInput:
+    """keypoint_grounding_tokinzer_input.py:6-44: pass-through of ``points`` [B, 17 P, 2] and ``masks`` [B, 17 P] of a keypoint checkpoint,
+    zeros as null.  ``prepare`` also accepts the two-argument call of interface.py:516."""
+    KEYS = ("points", "masks")
+
+    def __init__(self):
+        self.set = False
+
+    def prepare(self, batch, text_encoder=None):
+        self.set = True
+        points, masks = batch["points"], batch["masks"]
+        self.batch, tokens, _ = points.shape
+        self.max_persons_per_image = int(tokens / 17)
+        self.device = points.device
+        self.dtype = points.dtype
+        return {"points": points, "masks": masks}
+
+    def get_null_input(self, batch=None, device=None, dtype=None):
+        assert self.set, "not set yet, cannot call this funcion"
+        batch = self.batch if batch is None else batch
+        device = self.device if device is None else device
+        dtype = self.dtype if dtype is None else dtype
+        return {"points": torch.zeros(batch, self.max_persons_per_image * 17, 2).type(dtype).to(device),
+                "masks": torch.zeros(batch, self.max_persons_per_image * 17).type(dtype).to(device)}
+
+
+_GROUNDING_INPUTS = {"text": GroundingNetInput, "text_image": TextImageGroundingNetInput, "keypoint": KeypointGroundingNetInput}
+
+
 def grounding_input_for(cfg: UNetConfig):
     """the grounding-tokenizer input class that goes with the config's PositionNet"""
-    return TextImageGroundingNetInput() if cfg.grounding == "text_image" else GroundingNetInput()
+    return _GROUNDING_INPUTS[cfg.grounding]()
 
 
 class UNetModel:
@@ -201,7 +230,7 @@ class UNetModel:
             return input["grounding_input"]
         if self.grounding_tokenizer_input is None:
             raise RuntimeError("model.grounding_tokenizer_input is not set (interface.py:370)")
-        return self.grounding_tokenizer_input.get_null_input()
+        return self.grounding_tokenizer_input.get_null_input()      # (the family's own keys: grounding_input_for)
 
     def set_conditioning(self, context, relations, grounding: dict, hw, key=None) -> None:
         """``hw``: the latent side, or (h, w) for a rectangular latent (UNetEngine.set_conditioning).  ``relations``: None on a model without
@@ -210,10 +239,14 @@ class UNetModel:
             self.relations_of({})
         if key is not None and key == self._cond_key:
             return
-        if self.cfg.grounding == "text_image":
-            missing = [k for k in TextImageGroundingNetInput.KEYS if k not in grounding]
+        if self.cfg.grounding != "text":
+            keys = _GROUNDING_INPUTS[self.cfg.grounding].KEYS
+            missing = [k for k in keys if k not in grounding]
             if missing:
-                raise ValueError(f"a text_image model needs the grounding keys {TextImageGroundingNetInput.KEYS}; missing {missing}")
+                raise ValueError(f"a {self.cfg.grounding} model needs the grounding keys {keys}; missing {missing}")
+        if self.cfg.grounding == "keypoint":
+            self.engine.set_conditioning_kp(context, grounding["points"], grounding["masks"], hw)
+        elif self.cfg.grounding == "text_image":
             self.engine.set_conditioning(context, relations, grounding["boxes"], grounding["masks"], grounding["text_embeddings"], hw,
                                          text_masks=grounding["text_masks"], image_masks=grounding["image_masks"],
                                          image_embeddings=grounding["image_embeddings"])

@@ -478,6 +478,32 @@ def posnet_input(boxes, masks, emb, null_pos, null_xyxy, num_freqs, out):
     return out
 
 
+def posnet_input_kp(points, masks, person_emb, keypoint_emb, null_person, null_xy, num_freqs, out):
+    """The MLP input of the keypoint PositionNet (gl_posnet_input_kp / _f32 by ``out``'s dtype): points [B, 17 P, 2], masks [B, 17 P],
+    person_emb [P, D], keypoint_emb [17, D], null_person [D], null_xy [4 * num_freqs], fp32; out [B, 17 P, ld] fp16 or fp32 with
+    ld = D + 4 * num_freqs rounded up to a multiple of 64 (the kernel writes the pad columns as zeros)."""
+    for t, n in ((points, "points"), (masks, "masks"), (person_emb, "person_emb"), (keypoint_emb, "keypoint_emb"), (null_person, "null_person"),
+                 (null_xy, "null_xy")):
+        _req(t, F32, n, 4)
+        if not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous")
+    if points.dim() != 3 or points.shape[2] != 2 or person_emb.dim() != 2 or keypoint_emb.dim() != 2:
+        raise ValueError("posnet_input_kp: points [B, 17 P, 2], person_emb [P, D], keypoint_emb [17, D]")
+    B, tokens = points.shape[0], points.shape[1]
+    P, D = person_emb.shape
+    if tokens != 17 * P or tuple(masks.shape) != (B, tokens) or tuple(keypoint_emb.shape) != (17, D) or null_person.numel() != D or \
+            null_xy.numel() != 4 * num_freqs:
+        raise ValueError("posnet_input_kp: inconsistent shapes")
+    ld = (D + 4 * num_freqs + 63) // 64 * 64
+    _req(out, F32 if out.dtype == F32 else F16, "out", 4)
+    if not out.is_contiguous() or out.numel() != B * tokens * ld:
+        raise ValueError(f"out: need a contiguous [B, 17 P, {ld}] tensor")
+    fn = _lib.lib().gl_posnet_input_kp_f32 if out.dtype == F32 else _lib.lib().gl_posnet_input_kp
+    check(fn(points.data_ptr(), masks.data_ptr(), person_emb.data_ptr(), keypoint_emb.data_ptr(), null_person.data_ptr(), null_xy.data_ptr(),
+             B, tokens, D, num_freqs, out.data_ptr(), _stream()), "gl_posnet_input_kp")
+    return out
+
+
 def posnet_input_ti(boxes, masks, text_masks, image_masks, text_emb, image_emb, null_text, null_image, null_xyxy, num_freqs, out_text, out_image):
     """Both MLP inputs of the text_image PositionNet (gl_posnet_input_ti / _f32 by the outputs' dtype): out_text / out_image
     [B, n, in_dim + 8 * num_freqs], both fp16 or both fp32."""

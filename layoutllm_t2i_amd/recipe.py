@@ -57,7 +57,8 @@ def tensor(name: str, shape: Tuple[int, ...], seed: int = 0) -> np.ndarray:
         # non-zero gates, sign and size vary per module: tanh in roughly +-[0.3, 0.6]
         u = float(uniform(name, (1,), seed)[0])
         return np.float32(np.copysign(0.3 + 0.35 * abs(u), u if u != 0 else 1.0)).reshape(())
-    if leaf.startswith("null_"):
+    if leaf.startswith("null_") or leaf in ("person_embeddings", "keypoint_embeddings"):
+        # (the keypoint PositionNet's two learned tables: O(1) rows like the null features, none of them zero)
         return uniform(name, shape, seed) * np.float32(0.5)
     is_norm = (".norm" in name or "in_layers.0" in name or "out_layers.0" in name
                or name.startswith("out.0") or "norm_out" in name)
@@ -119,6 +120,8 @@ def synth_inputs(cfg: UNetConfig, batch: int, hw, n_boxes: int = 8, n_rel: int =
     """
     mo = cfg.max_objs
     lh, lw = (hw, hw) if isinstance(hw, int) else (int(v) for v in hw)
+    if getattr(cfg, "grounding", "text") == "keypoint":
+        return synth_inputs_kp(cfg, batch, (lh, lw), seed=seed)
     x = normal("in.x", (batch, cfg.in_channels, lh, lw), seed)
     context = normal("in.context", (batch, 77, cfg.context_dim), seed)
     uc = np.repeat(normal("in.uc", (1, 77, cfg.context_dim), seed), batch, axis=0)
@@ -156,3 +159,24 @@ def synth_inputs(cfg: UNetConfig, batch: int, hw, n_boxes: int = 8, n_rel: int =
                     text_embeddings=emb, image_embeddings=iemb)
     return dict(x=x, context=context, uc=uc, relations=relations, boxes=bx, masks=masks,
                 positive_embeddings=emb)
+
+
+def synth_inputs_kp(cfg: UNetConfig, batch: int, hw, n_persons: int | None = None, seed: int = 1234) -> Dict[str, np.ndarray]:
+    """Synthetic conditioning of a keypoint model (keypoint_grounding_net.py:34): points [B, 17 P, 2] in (0, 1), masks [B, 17 P].  The first
+    ``n_persons`` people (default: all but the last, at least one) are present; of a present person of sample b every (3 + b)-th keypoint is
+    missing (zero point, zero mask, as gligen_inference.py:199-211 derives it), and the first keypoint of sample 0 carries the fractional mask
+    0.25, so the blend against the null features is exercised as a blend."""
+    P, mo = cfg.max_persons, cfg.max_objs
+    lh, lw = (hw, hw) if isinstance(hw, int) else (int(v) for v in hw)
+    n_persons = max(1, P - 1) if n_persons is None else n_persons
+    x = normal("in.x", (batch, cfg.in_channels, lh, lw), seed)
+    context = normal("in.context", (batch, 77, cfg.context_dim), seed)
+    uc = np.repeat(normal("in.uc", (1, 77, cfg.context_dim), seed), batch, axis=0)
+    pts = (uniform("in.points", (batch, mo, 2), seed) * np.float32(0.45) + np.float32(0.5)).astype(np.float32)
+    masks = np.zeros((batch, mo), np.float32)
+    for b in range(batch):
+        for t in range(17 * n_persons):
+            masks[b, t] = 0.0 if (t % 17) % (3 + b) == 2 else 1.0
+    pts = pts * masks[..., None]
+    masks[0, 0] = 0.25
+    return dict(x=x, context=context, uc=uc, points=pts, masks=masks)

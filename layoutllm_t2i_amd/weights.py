@@ -39,6 +39,11 @@ def q_fold(d_head: int) -> float:
     return float(d_head) ** -0.5 * LOG2E
 
 
+def pad64(k: int) -> int:
+    """k rounded up to the GEMMs' K multiple (the row width of a keypoint model's position_net.linears.0 and of the rows it multiplies)"""
+    return (k + 63) // 64 * 64
+
+
 def _t(v, device) -> torch.Tensor:
     if not torch.is_tensor(v):
         v = torch.from_numpy(np.ascontiguousarray(np.asarray(v, dtype=np.float32)))
@@ -344,6 +349,19 @@ def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_
             for i in (0, 2, 4):
                 lin(f"position_net.{chain}.{i}")
         return P.to_flat()
+    if cfg.grounding == "keypoint":
+        # the two tables and the two null features stay fp32 (the input kernel sums and blends them in fp32); linears.0 with its K = D + 4 F
+        # columns zero-padded to the GEMMs' multiple of 64 (800 -> 832), each of the [Whi | Wlo] halves on its own in a split_weights table
+        W["position_net.person_emb"] = g("position_net.person_embeddings").contiguous()
+        W["position_net.keypoint_emb"] = g("position_net.keypoint_embeddings").contiguous()
+        W["position_net.null_person"] = g("position_net.null_person_feature").contiguous()
+        W["position_net.null_xy"] = g("position_net.null_xy_feature").contiguous()
+        w0 = g("position_net.linears.0.weight")
+        W["position_net.linears.0.w"] = mat(torch.nn.functional.pad(w0, (0, pad64(w0.shape[1]) - w0.shape[1])))
+        W["position_net.linears.0.b"] = g("position_net.linears.0.bias").contiguous()
+        for i in (2, 4):
+            lin(f"position_net.linears.{i}")
+        return P.to_flat()
     W["position_net.null_pos"] = g("position_net.null_positive_feature").contiguous()
     W["position_net.null_xyxy"] = g("position_net.null_position_feature").contiguous()
     for i in (0, 2, 4):
@@ -364,7 +382,7 @@ def random_state_dict(cfg: UNetConfig, device, seed: int = 0) -> Dict[str, torch
         if leaf in ("alpha_attn", "alpha_dense"):
             v = u().reshape(())
             t = torch.sign(v) * (0.3 + 0.35 * v.abs())
-        elif leaf.startswith("null_"):
+        elif leaf.startswith("null_") or leaf in ("person_embeddings", "keypoint_embeddings"):
             t = u() * 0.5
         elif (".norm" in name or "in_layers.0" in name or "out_layers.0" in name or name.startswith("out.0")) and len(shape) == 1:
             t = 1.0 + 0.1 * u() if leaf == "weight" else 0.05 * u()
