@@ -497,7 +497,8 @@ int gl_set_conditioning_kp(gl_engine* e, const float* context, const float* poin
 int gl_set_inpaint_extra(gl_engine* e, const float* extra, int32_t Bs, void* stream);
 /* gl_last_error: the message of the handle's last GL_ERR_BAD_ARG that carries one (a conditioning entry of the wrong grounding family, a
  * latent shape that breaks the shape rule, strict mode without split weights, the inpaint_mode checks of gl_set_inpaint_extra), copied NUL-terminated into dst (at most bytes - 1
- * characters).  Returns the message's full length, 0 when there is none.  Additive to ABI 15. */
+ * characters).  Returns the message's full length, 0 when there is none.  With e == NULL it returns the calling thread's last message of
+ * the entries that take no handle (gl_layout_reward).  Additive to ABI 15. */
 int gl_last_error(const gl_engine* e, char* dst, int32_t bytes);
 /* gl_unet_forward: eps[Bn, out_ch, hw, hw] fp32 = UNet(x, t | conditioning).  x fp32 NCHW [Bn / reps, in_ch, hw, hw]:
  * with reps = 2 both CFG halves of a [cond ; uncond] conditioning batch share the latent.  t_dev: fp32 [Bn] device
@@ -548,6 +549,34 @@ typedef struct gl_reward_args {
 } gl_reward_args;
 int gl_reward_score(const gl_reward_args* a, void* stream);
 int gl_sizeof_reward_args(void);
+
+/*
+ * gl_layout_reward: the layout half of Reward.forward (models/policy.py:126-135), i.e. compute_maximum_iou (tools/metrics.py:58-91, with
+ * compute_iou :29-42) and compute_docsim (tools/metrics.py:93-164) of B (ground truth, prediction) layout pairs, which the reference runs in
+ * CPU python with scipy's linear_sum_assignment.  One 64-lane wave per (sample, term), all arithmetic in double.  A layout is padded to
+ * GL_LAYOUT_MAX_BOXES rows; label ids are what Reward.label_to_id (policy.py:74-82) produces.  The reference's behaviour is kept, accidents
+ * included: the four numbers of a box are (l, t, r, b) to the IoU and (cx, cy, w, h) to DocSim, and the matrices are filled in
+ * np.meshgrid's 'xy' order (flat entry k = f(box1[k % n], box2[k / n]), reshaped to n x m).
+ *   miou[b]   = sum over the distinct ground-truth labels of the best assignment's IoU sum, / n_gt[b]
+ *   docsim[b] = mean of the best assignment's box similarities; 0 when the counts differ by 3 or more, or nothing is assigned
+ * A term whose matrix holds a NaN (the IoU of two zero-area boxes) is NaN for that sample only; the reference raises from scipy there.
+ * The counts are given twice: device arrays the kernel reads, and HOST arrays with the same values that this entry validates, so that
+ * it returns GL_ERR_BAD_ARG, before anything is launched and with a message gl_last_error(NULL, ...) returns, for a null pointer, B < 1,
+ * a count outside [0, GL_LAYOUT_MAX_BOXES] and n_gt == 0 (the reference: ZeroDivisionError).  Additive to ABI 15.
+ */
+#define GL_LAYOUT_MAX_BOXES 64
+typedef struct gl_layout_reward_args {
+    const double* boxes_gt; const double* boxes_pred;       /* device [B, 64, 4] */
+    const int32_t* labels_gt; const int32_t* labels_pred;   /* device [B, 64] */
+    const int32_t* n_gt; const int32_t* n_pred;             /* device [B]: boxes per layout */
+    const int32_t* n_gt_host; const int32_t* n_pred_host;   /* HOST [B]: the same counts, read by the entry only */
+    int32_t B;
+    double* miou; double* docsim;                           /* device [B] */
+} gl_layout_reward_args;
+int gl_layout_reward(const gl_layout_reward_args* a, void* stream);
+/* sizeof(gl_layout_reward_args), for the binding's layout check (tests/test_layout_host.py).  Replaces nothing of the reference (the
+ * arguments of metrics.py:77-82,146-151 are Python lists).  Additive to ABI 15. */
+int gl_sizeof_layout_reward_args(void);
 
 int gl_gemm(const gl_gemm_args* a, void* stream);
 int gl_conv3x3(const gl_conv_args* a, void* stream);

@@ -139,6 +139,12 @@ class RewardArgs(C.Structure):
                 ("sims_ti", vp), ("sims_ii", vp), ("aesthetic", vp), ("partial_reward", vp)]
 
 
+class LayoutRewardArgs(C.Structure):
+    """gl_layout_reward_args"""
+    _fields_ = [("boxes_gt", vp), ("boxes_pred", vp), ("labels_gt", vp), ("labels_pred", vp), ("n_gt", vp), ("n_pred", vp),
+                ("n_gt_host", vp), ("n_pred_host", vp), ("B", i32), ("miou", vp), ("docsim", vp)]
+
+
 class FFArgs(C.Structure):
     """gl_ff_args"""
     _fields_ = [("x", vp), ("ldx", i32), ("w1", vp), ("b1", vp), ("w2", vp), ("b2", vp), ("res", vp), ("ldres", i32), ("res_f32", i32),
@@ -206,6 +212,8 @@ PROTOTYPES = {
     "gl_sizeof_plms_step_args": (i32, []),
     "gl_reward_score": (i32, [C.POINTER(RewardArgs), vp]),
     "gl_sizeof_reward_args": (i32, []),
+    "gl_layout_reward": (i32, [C.POINTER(LayoutRewardArgs), vp]),
+    "gl_sizeof_layout_reward_args": (i32, []),
     "gl_ff_fused": (i32, [C.POINTER(FFArgs), vp]),
     "gl_ff_fused_supported": (i32, [i32]),
     "gl_ff_fused_applicable": (i32, [i32, i32]),
@@ -276,7 +284,8 @@ def lib() -> C.CDLL:
     for cls, fn in ((GemmArgs, l.gl_sizeof_gemm_args), (ConvArgs, l.gl_sizeof_conv_args), (AttnArgs, l.gl_sizeof_attn_args),
                     (UNetConfigC, l.gl_sizeof_unet_config), (WeightInfo, l.gl_sizeof_weight_info),
                     (PlmsStepArgs, l.gl_sizeof_plms_step_args), (RewardArgs, l.gl_sizeof_reward_args), (FFArgs, l.gl_sizeof_ff_args),
-                    (VaeConfigC, l.gl_sizeof_vae_config), (GnArgs, l.gl_sizeof_gn_args)):
+                    (VaeConfigC, l.gl_sizeof_vae_config), (GnArgs, l.gl_sizeof_gn_args),
+                    (LayoutRewardArgs, l.gl_sizeof_layout_reward_args)):
         if C.sizeof(cls) != fn():
             raise HipLibraryError(f"struct size mismatch for {cls.__name__}: host {C.sizeof(cls)} vs lib {fn()}")
     _lib = l
@@ -405,8 +414,9 @@ def weight_table(handle: int):
     return out, int(l.gl_weights_bytes(handle))
 
 
-def last_error(handle: int) -> str:
-    """gl_last_error: the message the handle's last failing entry left (empty when there is none)"""
+def last_error(handle) -> str:
+    """gl_last_error: the message the handle's last failing entry left (empty when there is none); ``None``: the calling thread's last
+    message of the entries that take no handle (gl_layout_reward)"""
     buf = C.create_string_buffer(512)
     n = lib().gl_last_error(handle, buf, len(buf))
     return buf.value.decode() if n > 0 else ""

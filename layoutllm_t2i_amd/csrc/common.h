@@ -80,6 +80,9 @@ static inline int gn_nchunk(int HW) {
     return c > 512 ? 512 : c;
 }
 
+// The calling thread's last refusal message of an entry that takes no handle (layout_reward.hip); gl_last_error(NULL, ...) reads it
+const char* gl_handleless_error();
+
 #define GL_CHECK_LAUNCH()                                   \
     do {                                                    \
         hipError_t e__ = hipGetLastError();                 \

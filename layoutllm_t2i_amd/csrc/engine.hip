@@ -1656,11 +1656,13 @@ extern "C" int gl_clear_handle_options(gl_engine* e) {
 }
 
 extern "C" int gl_last_error(const gl_engine* e, char* dst, int32_t bytes) {
-    if (!e || !dst || bytes <= 0) return GL_ERR_BAD_ARG;
-    const size_t n = e->err.size() < (size_t)bytes - 1 ? e->err.size() : (size_t)bytes - 1;
-    memcpy(dst, e->err.data(), n);
+    if (!dst || bytes <= 0) return GL_ERR_BAD_ARG;
+    const std::string hl = e ? std::string() : std::string(gl_handleless_error());   // no handle: the entries that take none
+    const std::string& err = e ? e->err : hl;
+    const size_t n = err.size() < (size_t)bytes - 1 ? err.size() : (size_t)bytes - 1;
+    memcpy(dst, err.data(), n);
     dst[n] = 0;
-    return (int)e->err.size();
+    return (int)err.size();
 }
 
 extern "C" int64_t gl_pool_bytes(const gl_engine* e) {
