@@ -416,7 +416,12 @@ typedef struct gl_unet_config {          /* UNetModel.__init__ arguments (openai
                                     linears.{0,2,4}, linears.0 with K = pos_in_dim + 4 F zero-padded to the next multiple of 64 (800 -> 832; each of
                                     the [Whi | Wlo] halves of a split_weights table on its own).  The handle is conditioned through
                                     gl_set_conditioning_kp.  Requires no_relation = 1 (the relation chain pools over boxes) and inpaint_mode = 0, else
-                                    GL_ERR_UNSUPPORTED. */
+                                    GL_ERR_UNSUPPORTED.
+                                    4 = the spatial families (canny / hed / depth / normal): the tokenizer, a ConvNeXt run by the caller once per image,
+                                    is NOT part of the handle: the table has no position_net.* entries and the handle is conditioned through
+                                    gl_set_conditioning_tokens with the finished grounding tokens; max_objs counts those tokens, <= 64.  Requires
+                                    no_relation = 1, inpaint_mode = 0 and split_weights = 0, else GL_ERR_UNSUPPORTED.  The channels of the grounding
+                                    downsampler are not in this struct: gl_set_extra_channels.  3 is not assigned (GL_ERR_UNSUPPORTED). */
     int32_t inpaint_mode;        /* additive to ABI 15.  0 = the first conv reads the latent alone (a zeroed field keeps the earlier behaviour).  1 = GLIGEN's
                                     inpainting checkpoints (openaimodel.py:293-299, :436-439): input_blocks.0.0 is [mc, 2 * in_channels + 1, 3, 3] and reads
                                     cat([x, z0 * mask, mask]); in_channels stays the latent's channel count.  The packed weight keeps its [mc, 9 * 64] slot
@@ -495,6 +500,24 @@ int gl_set_conditioning_kp(gl_engine* e, const float* context, const float* poin
  * set, when Bs is neither 1 nor Bn / reps, and for sd_conv != 0; on any other handle this entry returns GL_ERR_BAD_ARG with a message.
  * Additive to ABI 15. */
 int gl_set_inpaint_extra(gl_engine* e, const float* extra, int32_t Bs, void* stream);
+/* gl_set_conditioning_tokens: the conditioning of a spatial handle (gl_unet_config.grounding = 4; additive to ABI 15).  objs fp32
+ * [Bn, max_objs, pos_out_dim] on the device: the grounding tokens as the family's PositionNet returns them (the null tokens in the unconditional
+ * half).  Hoists fuser.linear(objs) and the context K / V exactly as the other entries do after their PositionNet.  (h, w): the shape rule of
+ * gl_set_conditioning_hw.  On a handle of another family, and the other entries on a spatial handle: GL_ERR_BAD_ARG with a gl_last_error
+ * message naming the right entry, before any pointer is read. */
+int gl_set_conditioning_tokens(gl_engine* e, const float* context, const float* objs, int32_t Bn, int32_t Lc, int32_t h, int32_t w, void* stream);
+/* gl_set_extra_channels: the output channels Ce of the grounding downsampler of a spatial handle (grounding = 4; GLIGEN's canny / depth /
+ * normal checkpoints have 8, hed has 1; openaimodel_original.py: h = cat([x, downsample_net(grounding_extra_input)], 1)), set once after
+ * gl_create.  gl_unet_config keeps its layout: the weight table does not depend on Ce (input_blocks.0.0 is [mc, in_channels + Ce, 3, 3] in
+ * the same 64-padded slot and the sd_first_conv.* entries stay -- this first conv IS restorable), only the pack launch of a GLIGEN-conv
+ * forward and the size of the extra buffer do.  0 (what a new handle has) = the first conv reads the latent alone.  On a handle of another
+ * family, channels < 0 or in_channels + channels > 64: GL_ERR_UNSUPPORTED with a gl_last_error message.  Additive to ABI 15. */
+int gl_set_extra_channels(gl_engine* e, int32_t channels);
+/* gl_set_grounding_extra: the downsampled grounding_extra_input of a spatial handle with Ce > 0 extra channels (gl_set_extra_channels), extra fp32
+ * [Bs, Ce, h, w] on the device, Bs = 1 or the number of samples Bn / reps; both CFG halves read the same extra (plms.py:118-121).  Copied
+ * (stream-ordered) into a pool buffer like gl_set_inpaint_extra's.  A forward with sd_conv = 0 packs cat([x, extra]) for the GLIGEN conv and is
+ * refused (GL_ERR_BAD_ARG, gl_last_error) while no extra is set for the current latent shape; a forward with sd_conv = 1 reads x alone. */
+int gl_set_grounding_extra(gl_engine* e, const float* extra, int32_t Bs, void* stream);
 /* gl_last_error: the message of the handle's last GL_ERR_BAD_ARG that carries one (a conditioning entry of the wrong grounding family, a
  * latent shape that breaks the shape rule, strict mode without split weights, the inpaint_mode checks of gl_set_inpaint_extra), copied NUL-terminated into dst (at most bytes - 1
  * characters).  Returns the message's full length, 0 when there is none.  With e == NULL it returns the calling thread's last message of
@@ -661,6 +684,37 @@ int gl_clip_embed_tokens(const int32_t* ids, const float* tok_emb, const float* 
 int gl_clip_gather_rows(const float* x, int32_t ldx, const int32_t* rows, int32_t B, int32_t C, float* out, void* stream);
 int gl_attention_small(const void* q, const void* k, const void* v, int32_t ld, int32_t B, int32_t T, int32_t H, int32_t d,
                        float scale, int32_t causal, void* out, int32_t ldo, void* stream);
+
+/*
+ * Spatial grounding (GLIGEN's canny / hed / depth / normal checkpoints), additive to ABI 15: the stages of the ConvNeXt tokenizer
+ * ({canny,hed,depth,normal}_grounding_net.py, convnext.py) around gl_gemm, and the grounding downsampler.  Run once per image.
+ *   gl_sp_stem_patchify : map fp32 [B, 3, S, S] -> F.interpolate(map, R) (nearest: src = min(floor(dst * (float)S / R), S - 1)) -> fp16 rows
+ *                         [B * (R/4)^2, 64] of the 4x4 stride-4 stem conv, K index (c * 4 + i) * 4 + j, columns 48..63 zero.  R % 4 == 0.
+ *   gl_sp_layernorm     : y[r, :] = LayerNorm(x[r, :]) over C, eps 1e-6, fp32 in and out (y may be x).
+ *   gl_sp_dwconv_ln     : x fp32 NHWC [B, H, W, C] -> depthwise 7x7 (pad 3, zero border; w fp32 [49, C] tap-major, bias [C]) -> LayerNorm over C
+ *                         (eps 1e-6) -> fp16 rows [B * H * W, ldo], ldo % 64 == 0, ldo >= C, columns [C, ldo) written as zeros.  C <= 768.
+ *   gl_sp_gelu          : y = 0.5 x erfc(-x / sqrt 2) (erf-GELU), fp16 in and out, fp32 arithmetic; n even.
+ *   gl_sp_down_gather   : x fp32 NHWC -> per-pixel LayerNorm (eps 1e-6) -> fp16 rows [B * H/2 * W/2, 4 C], pixel (2 oy + ky, 2 ox + kx) at columns
+ *                         [(ky * 2 + kx) * C, + C).  H, W even.
+ *   gl_sp_assemble      : out[b * T + t, :] = feat[b * T + t, :] * mask[b] + null_feature * (1 - mask[b]) + pos[t, :], fp32 in, fp16 out.
+ *   gl_sp_bicubic       : out[b, c, oy, ox] = sum_i wy[oy, i] sum_j wx[ox, j] in[b, c, iy[oy, i], ix[ox, j]] for the first C of the input's Ct
+ *                         channels; iy / ix int32 [Hout | Wout, 4] clamped source indices, wy / wx fp32 [.., 4] (torch's bicubic: align_corners
+ *                         False, A = -0.75, no antialias -- built by the host).  fp32.
+ *   gl_sp_conv4x4s2     : Conv2d(Ci, Co, 4, 2, 1) on fp32 NCHW with an optional SiLU, Ci, Co <= 8, Hin, Win even.
+ */
+int gl_sp_stem_patchify(const float* map, int32_t B, int32_t S, int32_t R, void* out, void* stream);
+int gl_sp_layernorm(const float* x, int64_t rows, int32_t C, const float* gamma, const float* beta, float* y, void* stream);
+int gl_sp_dwconv_ln(const float* x, const float* w, const float* bias, const float* ln_gamma, const float* ln_beta, int32_t B, int32_t H,
+                    int32_t W, int32_t C, int32_t ldo, void* out, void* stream);
+int gl_sp_gelu(const void* x, void* y, int64_t n, void* stream);
+int gl_sp_down_gather(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* ln_gamma, const float* ln_beta, void* out,
+                      void* stream);
+int gl_sp_assemble(const float* feat, const float* mask, const float* null_feature, const float* pos, int32_t B, int32_t T, int32_t C,
+                   void* out, void* stream);
+int gl_sp_bicubic(const float* in, int32_t B, int32_t Ct, int32_t C, int32_t Hin, int32_t Win, const int32_t* iy, const float* wy,
+                  const int32_t* ix, const float* wx, int32_t Hout, int32_t Wout, float* out, void* stream);
+int gl_sp_conv4x4s2(const float* in, const float* w, const float* bias, int32_t B, int32_t Ci, int32_t Co, int32_t Hin, int32_t Win,
+                    int32_t silu, float* out, void* stream);
 
 /* ---- image preprocessing of the reward stage (models/policy.py:108-111: self.processor(images=...), the HuggingFace CLIP
  * feature extractor on PIL images; transformers 4.19.2 image_utils + Pillow) -- on the GPU, so rollout images stay in HBM

@@ -20,7 +20,7 @@ EPI_BIAS, EPI_SILU, EPI_GEGLU, EPI_RES, EPI_GATE_RES, EPI_ROWBIAS = range(6)
 OUT_F16_ROWMAJOR, OUT_F32_NCHW, OUT_F32_ROWMAJOR, OUT_F16_HILO = 0, 1, 2, 3
 
 # gl_unet_config.grounding
-GROUNDING_IDS = {"text": 0, "text_image": 1, "keypoint": 2}
+GROUNDING_IDS = {"text": 0, "text_image": 1, "keypoint": 2, "spatial": 4}      # (3 is not assigned)
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -196,6 +196,17 @@ PROTOTYPES = {
     "gl_set_conditioning_hw": (i32, [vp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]),
     "gl_set_conditioning_ti": (i32, [vp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]),
     "gl_set_conditioning_kp": (i32, [vp, fp, fp, fp, i32, i32, i32, i32, vp]),
+    "gl_set_conditioning_tokens": (i32, [vp, fp, fp, i32, i32, i32, i32, vp]),
+    "gl_set_grounding_extra": (i32, [vp, fp, i32, vp]),
+    "gl_set_extra_channels": (i32, [vp, i32]),
+    "gl_sp_stem_patchify": (i32, [fp, i32, i32, i32, vp, vp]),
+    "gl_sp_layernorm": (i32, [fp, i64, i32, fp, fp, fp, vp]),
+    "gl_sp_dwconv_ln": (i32, [fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
+    "gl_sp_gelu": (i32, [vp, vp, i64, vp]),
+    "gl_sp_down_gather": (i32, [fp, i32, i32, i32, i32, fp, fp, vp, vp]),
+    "gl_sp_assemble": (i32, [fp, fp, fp, fp, i32, i32, i32, vp, vp]),
+    "gl_sp_bicubic": (i32, [fp, i32, i32, i32, i32, i32, vp, fp, vp, fp, i32, i32, fp, vp]),
+    "gl_sp_conv4x4s2": (i32, [fp, fp, fp, i32, i32, i32, i32, i32, i32, fp, vp]),
     "gl_posnet_input_kp": (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, vp, vp]),
     "gl_posnet_input_kp_f32": (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, fp, vp]),
     "gl_posnet_input_ti": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp, vp, vp]),
@@ -322,6 +333,9 @@ def unet_config_c(cfg) -> UNetConfigC:
     c.grounding = GROUNDING_IDS[getattr(cfg, "grounding", "text")]
     c.inpaint_mode = int(bool(getattr(cfg, "inpaint_mode", False)))
     c.no_relation = int(not getattr(cfg, "relation", True))
+    if c.grounding == GROUNDING_IDS["spatial"]:
+        # max_objs counts the tokenizer's tokens (the downsampler's channels are not in the struct: create_engine, gl_set_extra_channels)
+        c.max_objs = cfg.n_ground
     return c
 
 
@@ -373,6 +387,13 @@ def create_engine(cfg, fold_up=None) -> int:
     cc = unet_config_c(cfg)
     with _fold_up_scope(fold_up):
         check(lib().gl_create(C.byref(cc), C.byref(h)), "gl_create")
+    if getattr(cfg, "ds_out", 0):
+        # a spatial config: the channels its grounding downsampler adds in front of the first conv
+        rc = lib().gl_set_extra_channels(h, int(cfg.ds_out))
+        if rc != 0:
+            msg = last_error(h.value)
+            lib().gl_destroy(h)
+            raise HipLibraryError(f"gl_set_extra_channels failed with code {rc}: {msg}")
     return h.value
 
 

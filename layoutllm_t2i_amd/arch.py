@@ -17,6 +17,20 @@ from typing import Dict, List, Tuple
 KEYPOINTS = 17           # COCO keypoints per person (keypoint_grounding_net.py:16)
 MAX_PERSONS = 8          # the shipped checkpoint's max_persons_per_image: 136 grounding tokens (gl_create's limit for the family)
 
+# The spatial grounding families: tokenizer module -> (its own downsampler module, downsampler kind, input channels, default output channels).
+# {canny,hed,depth,normal}_grounding_net.PositionNet are one ConvNeXt tokenizer; *_grounding_downsampler.py differ in the channels they read and
+# in whether two small convs follow the bicubic resize (hed: none, a hard-coded 64 x 64).  The semantic family (152-channel one-hot input,
+# nearest resize) is not among them.
+SPATIAL_FAMILIES = {
+    "canny_grounding_net": ("canny_grounding_downsampler", "conv", 1, 8),
+    "hed_grounding_net": ("hed_grounding_downsampler", "bicubic", 1, 1),
+    "depth_grounding_net": ("depth_grounding_downsampler", "conv", 1, 8),
+    "normal_grounding_net": ("normal_grounding_downsampler", "conv", 3, 8),
+}
+CONVNEXT_DEPTHS = (3, 3, 9, 3)            # convnext.py: convnext_tiny
+CONVNEXT_DIMS = (96, 192, 384, 768)
+HED_DS_SIZE = 64                          # hed_grounding_downsampler.py:19 resizes to (64, 64) whatever the latent
+
 
 @dataclass(frozen=True)
 class UNetConfig:
@@ -51,16 +65,37 @@ class UNetConfig:
     # (attention_original.py:312-316, no rela_fuse), what every public GLIGEN checkpoint was trained on (gl_unet_config.no_relation).  Not in
     # the config dict of a checkpoint: interface.load_ckpt sets it from the state dict's keys
     relation: bool = True
+    # grounding = "spatial" (GLIGEN's canny / hed / depth / normal checkpoints, gl_unet_config.grounding = 4): a ConvNeXt tokenizer
+    # (spatial.SpatialTokenizer: the map resized to sp_resize_input, (sp_resize_input // 32) ** 2 tokens) and a grounding downsampler whose
+    # ds_out channels are concatenated to the latent in front of the first conv (spatial.SpatialDownsampler).  ds_kind: "" = none, "conv" =
+    # bicubic to ds_resize_input then two 4x4 stride-2 convs (canny, depth, normal), "bicubic" = bicubic to 64 x 64 alone (hed); ds_in = the
+    # channels of the map it reads (1, or 3 for normal).  The defaults leave every other config as it was.
+    ds_kind: str = ""
+    ds_in: int = 1
+    ds_out: int = 0
+    ds_resize_input: int = 256
+    sp_resize_input: int = 256
+    convnext_depths: Tuple[int, ...] = CONVNEXT_DEPTHS
+    convnext_dims: Tuple[int, ...] = CONVNEXT_DIMS
 
     @property
     def first_conv_in(self) -> int:
-        """input channels of input_blocks.0.0: the latent, plus the masked latent and the mask of an inpaint_mode model (4 + 4 + 1)"""
-        return self.in_channels + (self.in_channels + 1 if self.inpaint_mode else 0)
+        """input channels of input_blocks.0.0: the latent, plus the masked latent and the mask of an inpaint_mode model (4 + 4 + 1), or plus the
+        grounding downsampler's channels of a spatial model (4 + 8, hed 4 + 1)"""
+        return self.in_channels + (self.in_channels + 1 if self.inpaint_mode else self.ds_out)
 
     @property
     def n_ground(self) -> int:
-        """grounding tokens per sample, the extra keys of the gated self-attention: max_objs (text, keypoint) or 2 * max_objs (text_image)"""
+        """grounding tokens per sample, the extra keys of the gated self-attention: max_objs (text, keypoint), 2 * max_objs (text_image) or the
+        tokenizer's (sp_resize_input // 32) ** 2 (spatial)"""
+        if self.grounding == "spatial":
+            return (self.sp_resize_input // 32) ** 2
         return self.max_objs * (2 if self.grounding == "text_image" else 1)
+
+    @property
+    def ds_latent(self) -> int:
+        """side of the downsampler's output, which the latent has to match: ds_resize_input / 4, or hed's hard-coded 64"""
+        return HED_DS_SIZE if self.ds_kind == "bicubic" else self.ds_resize_input // 4
 
     @property
     def max_persons(self) -> int:
@@ -79,7 +114,7 @@ class UNetConfig:
         return self.fourier_freqs * 2 * (2 if self.grounding == "keypoint" else 4)
 
     @staticmethod
-    def from_dict(params: dict, allow_inpaint: bool = False, allow_keypoint: bool = False) -> "UNetConfig":
+    def from_dict(params: dict, allow_inpaint: bool = False, allow_keypoint: bool = False, allow_spatial: bool = False) -> "UNetConfig":
         """Accepts the ``config['model']['params']`` dict of a GLIGEN checkpoint.
 
         ``allow_inpaint``: an ``inpaint_mode`` checkpoint (9-channel first conv) shares every parameter name with the layout-to-image UNet but
@@ -87,7 +122,12 @@ class UNetConfig:
         the flag such a config keeps raising, like the other look-alike variants below.
 
         ``allow_keypoint``: the same for a keypoint checkpoint (``keypoint_grounding_net.PositionNet``): it is fed ``points`` and ``masks``
-        where the box families take boxes and embeddings, so a caller has to say that it supplies them (``interface.load_ckpt`` does)."""
+        where the box families take boxes and embeddings, so a caller has to say that it supplies them (``interface.load_ckpt`` does).
+
+        ``allow_spatial``: the same for the canny / hed / depth / normal checkpoints (``*_grounding_net.PositionNet`` with their own
+        ``*_grounding_downsampler.GroundingDownsampler``): they are fed a map and ``grounding_extra_input``.  Every other downsampler config
+        (no flag, another target, the sem family, with inpaint_mode, a tokenizer of another family) raises NotImplementedError naming
+        ``grounding_downsampler``."""
         gt = (params.get("grounding_tokenizer") or {}).get("params", {})
         target = (params.get("grounding_tokenizer") or {}).get("target")
         if target is None or target.endswith(".text_grounding_net.PositionNet") or target == "text_grounding_net.PositionNet":
@@ -96,6 +136,13 @@ class UNetConfig:
             grounding = "text_image"
         elif target.endswith("keypoint_grounding_net.PositionNet") and allow_keypoint:
             grounding = "keypoint"
+        elif _spatial_family(target) is not None and allow_spatial and params.get("grounding_downsampler") is not None:
+            grounding = "spatial"
+        elif _spatial_family(target) is not None or target.endswith("sem_grounding_net.PositionNet"):
+            raise NotImplementedError(f"grounding_tokenizer target {target!r} with grounding_downsampler "
+                                      f"{(params.get('grounding_downsampler') or {}).get('target')!r}: the canny / hed / depth / normal families load "
+                                      "with allow_spatial=True and their own grounding_downsampler (interface.load_ckpt passes the flag); the "
+                                      "semantic family is not supported")
         else:
             raise NotImplementedError(f"grounding_tokenizer target {target!r}: only the text and text_image PositionNets are supported (and the "
                                       "keypoint one with allow_keypoint=True, fed points and masks: interface.load_ckpt / run_one_image do)")
@@ -105,12 +152,32 @@ class UNetConfig:
             raise NotImplementedError(f"fuser_type={params.get('fuser_type')!r}: only 'gatedSA' is on the layout-to-image path")
         if int(params.get("transformer_depth", 1)) != 1:
             raise NotImplementedError("transformer_depth != 1 is not supported")
+        if params.get("inpaint_mode", False) and params.get("grounding_downsampler") is not None:
+            # (the reference itself stops at a breakpoint() there, openaimodel.py:437-438)
+            raise NotImplementedError("grounding_downsampler with inpaint_mode is not supported (the reference stops there too)")
         if params.get("inpaint_mode", False) and not allow_inpaint:
             raise NotImplementedError("inpaint_mode checkpoints (9-channel first conv) are not on the layout-to-image path: pass "
                                       "allow_inpaint=True and feed inpainting_extra_input (interface.load_ckpt / run_one_image do)")
+        sp = {}
         if params.get("grounding_downsampler") is not None:
-            # (together with inpaint_mode the reference itself stops at a breakpoint(), openaimodel.py:437-438)
-            raise NotImplementedError("grounding_downsampler is not on the text_layout path")
+            ds = params["grounding_downsampler"]
+            ds_target, dp = str(ds.get("target")), ds.get("params") or {}
+            if grounding != "spatial":
+                raise NotImplementedError(f"grounding_downsampler {ds_target!r} is not on the text_layout path" +
+                                          ("" if allow_spatial else " (the canny / hed / depth / normal families need allow_spatial=True)"))
+            ds_mod, kind, cin, cout = SPATIAL_FAMILIES[_spatial_family(target)]
+            if not ds_target.endswith(ds_mod + ".GroundingDownsampler"):
+                raise NotImplementedError(f"grounding_downsampler target {ds_target!r} does not go with the tokenizer {target!r}: expected "
+                                          f"{ds_mod}.GroundingDownsampler")
+            if int(dp.get("out_dim", cout)) != cout:
+                raise NotImplementedError(f"grounding_downsampler out_dim = {dp.get('out_dim')}: {ds_mod} has {cout}")
+            sp = dict(ds_kind=kind, ds_in=cin, ds_out=cout, ds_resize_input=int(dp.get("resize_input", 256)),
+                      sp_resize_input=int(gt.get("resize_input", 448)), relation=False)
+            if sp["sp_resize_input"] % 32 or not 32 <= sp["sp_resize_input"] <= 256:
+                raise ValueError(f"grounding_tokenizer resize_input = {sp['sp_resize_input']}: a multiple of 32 up to 256 (at most 64 grounding tokens)")
+            if kind == "conv" and sp["ds_resize_input"] % 4:
+                raise ValueError(f"grounding_downsampler resize_input = {sp['ds_resize_input']}: a multiple of 4")
+            sp["max_objs"] = (sp["sp_resize_input"] // 32) ** 2
         if not params.get("use_spatial_transformer", True):
             raise NotImplementedError("use_spatial_transformer=False is not supported")
         kp = {}
@@ -141,7 +208,16 @@ class UNetConfig:
             grounding=grounding,
             inpaint_mode=bool(params.get("inpaint_mode", False)),
         )
+        kp.update(sp)
         return replace(cfg, **kp) if kp else cfg
+
+
+def _spatial_family(target):
+    """the key of SPATIAL_FAMILIES a grounding_tokenizer target names, or None"""
+    if not target or not target.endswith(".PositionNet"):
+        return None
+    mod = target[:-len(".PositionNet")].rsplit(".", 1)[-1]
+    return mod if mod in SPATIAL_FAMILIES else None
 
 
 # A small config used by tests (CPU goldens and the GPU whole-model parity test).
@@ -318,6 +394,46 @@ def st_params(p: str, C: int, ctx: int, relation: bool = True) -> Dict[str, Tupl
     return out
 
 
+def spatial_tokenizer_params(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
+    """position_net.* of a spatial model ({canny,hed,depth,normal}_grounding_net.py:12-35 + convnext.py), in the order of the module's state
+    dict: its own two parameters, then the ConvNeXt backbone (downsample_layers, stages), then the linears"""
+    dims, depths = cfg.convnext_dims, cfg.convnext_depths
+    p = "position_net"
+    bb = p + ".convnext_tiny_backbone"
+    out: Dict[str, Tuple[int, ...]] = {}
+    out[p + ".pos_embedding"] = (1, cfg.n_ground, dims[3])
+    out[p + ".null_feature"] = (dims[3],)
+    out[bb + ".downsample_layers.0.0.weight"] = (dims[0], 3, 4, 4)
+    out[bb + ".downsample_layers.0.0.bias"] = (dims[0],)
+    out[bb + ".downsample_layers.0.1.weight"] = (dims[0],)
+    out[bb + ".downsample_layers.0.1.bias"] = (dims[0],)
+    for i in range(1, 4):
+        out[bb + f".downsample_layers.{i}.0.weight"] = (dims[i - 1],)
+        out[bb + f".downsample_layers.{i}.0.bias"] = (dims[i - 1],)
+        out[bb + f".downsample_layers.{i}.1.weight"] = (dims[i], dims[i - 1], 2, 2)
+        out[bb + f".downsample_layers.{i}.1.bias"] = (dims[i],)
+    for i in range(4):
+        C = dims[i]
+        for j in range(depths[i]):
+            b = bb + f".stages.{i}.{j}"
+            out[b + ".gamma"] = (C,)
+            out[b + ".dwconv.weight"] = (C, 1, 7, 7)
+            out[b + ".dwconv.bias"] = (C,)
+            out[b + ".norm.weight"] = (C,)
+            out[b + ".norm.bias"] = (C,)
+            out[b + ".pwconv1.weight"] = (4 * C, C)
+            out[b + ".pwconv1.bias"] = (4 * C,)
+            out[b + ".pwconv2.weight"] = (C, 4 * C)
+            out[b + ".pwconv2.bias"] = (C,)
+    out[p + ".linears.0.weight"] = (512, dims[3])
+    out[p + ".linears.0.bias"] = (512,)
+    out[p + ".linears.2.weight"] = (512, 512)
+    out[p + ".linears.2.bias"] = (512,)
+    out[p + ".linears.4.weight"] = (cfg.pos_out_dim, 512)
+    out[p + ".linears.4.bias"] = (cfg.pos_out_dim,)
+    return out
+
+
 def param_shapes(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
     """state_dict name -> shape for the whole UNet, in module registration order."""
     plan = build_plan(cfg)
@@ -327,6 +443,12 @@ def param_shapes(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
     out["time_embed.0.bias"] = (te,)
     out["time_embed.2.weight"] = (te, te)
     out["time_embed.2.bias"] = (te,)
+    if cfg.ds_kind == "conv":
+        # *_grounding_downsampler.py: Conv2d(c, 4, 4, 2, 1), SiLU, Conv2d(4, out_dim, 4, 2, 1); registered right after time_embed
+        out["downsample_net.layers.0.weight"] = (4, cfg.ds_in, 4, 4)
+        out["downsample_net.layers.0.bias"] = (4,)
+        out["downsample_net.layers.2.weight"] = (cfg.ds_out, 4, 4, 4)
+        out["downsample_net.layers.2.bias"] = (cfg.ds_out,)
     for l in plan.all_layers():
         if l.kind == "conv_in":
             out.update(conv_params(l.prefix, cfg.first_conv_in, l.cout))      # 9 input channels on an inpaint_mode model
@@ -352,6 +474,9 @@ def param_shapes(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
         out["position_net.null_text_feature"] = (cfg.pos_in_dim,)
         out["position_net.null_image_feature"] = (cfg.pos_in_dim,)
         out["position_net.null_position_feature"] = (cfg.position_dim,)
+        return out
+    if cfg.grounding == "spatial":
+        out.update(spatial_tokenizer_params(cfg))
         return out
     if cfg.grounding == "keypoint":
         # keypoint_grounding_net.py:15-31, in the order of the module's state dict (its own parameters, then the linears)

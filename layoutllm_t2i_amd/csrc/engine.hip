@@ -166,6 +166,8 @@ struct gl_engine {
     int Bn = 0, R = 0, Lc = 0, lat_h = 0, lat_w = 0;     // (lat_h, lat_w): the latent's rows and columns (gl_set_conditioning_hw)
     // inpaint_mode handles: the inpainting_extra_input [extra_bs, in_channels + 1, lat_h, lat_w] lives in the pool buffer "in.extra" (gl_set_inpaint_extra)
     bool extra_set = false;
+    // spatial handles (grounding = 4): output channels of the grounding downsampler the GLIGEN first conv also reads (gl_set_extra_channels)
+    int ground_extra = 0;
     int extra_bs = 0;
     // graphs
     std::map<GraphKey, hipGraphExec_t> graphs;
@@ -401,6 +403,7 @@ void build_table(gl_engine* e) {
         }
         return;
     }
+    if (c.grounding == 4) return;       // spatial: the ConvNeXt tokenizer runs outside the handle, which takes finished tokens (gl_set_conditioning_tokens)
     if (c.grounding == 2) {
         // keypoint PositionNet (keypoint_grounding_net.py:15-31): two learned tables and two null features (fp32: the input kernel sums and
         // blends them), one MLP whose first layer's K = D + 4 F is zero-padded to the GEMMs' multiple of 64 (800 -> 832)
@@ -420,8 +423,11 @@ void build_table(gl_engine* e) {
     add_lin(e, "position_net.linears.4", c.pos_out_dim, 512);
 }
 
-// input channels of input_blocks.0.0: the latent, + the masked latent and the mask of an inpaint_mode handle (openaimodel.py:293-299)
-inline int first_conv_in(const gl_unet_config& c) { return c.in_channels + (c.inpaint_mode ? c.in_channels + 1 : 0); }
+// channels the GLIGEN first conv reads besides the latent: the masked latent and the mask of an inpaint_mode handle (openaimodel.py:293-299), or
+// the grounding downsampler's output on a spatial handle (openaimodel_original.py: cat([x, downsample_net(grounding_extra_input)], 1))
+inline int extra_channels(const gl_unet_config& c, int ground_extra = 0) { return c.inpaint_mode ? c.in_channels + 1 : ground_extra; }
+// input channels of input_blocks.0.0
+inline int first_conv_in(const gl_unet_config& c, int ground_extra = 0) { return c.in_channels + extra_channels(c, ground_extra); }
 // grounding tokens per sample (the fuser's extra keys): max_objs for the text PositionNet, 2 * max_objs for text_image; a keypoint handle's
 // max_objs already counts tokens (17 per person)
 inline int n_ground(const gl_unet_config& c) { return c.grounding == 1 ? 2 * c.max_objs : c.max_objs; }
@@ -1009,13 +1015,15 @@ int launch_forward(gl_engine* e, int reps, bool fuser_on, bool sd_conv, bool uni
     half_t* xin = e->h16("in.x", (size_t)Bn * sh * sw * CIN_PAD);
     CKP(xin);
     ++r.launches;
-    if (cfg.inpaint_mode) {
+    const int n_extra = extra_channels(cfg, e->ground_extra);
+    if (n_extra != 0 && !sd_conv) {
         // cat([x, inpainting_extra_input], dim=1) (openaimodel.py:439) folded into the pack: one launch, like the text handle's.  Both CFG halves
-        // read the same extra (plms.py:118-121), so the shared prefix stays valid.
-        const float* extra = e->f32("in.extra", (size_t)e->extra_bs * (cfg.in_channels + 1) * sh * sw);
+        // read the same extra (plms.py:118-121), so the shared prefix stays valid.  A spatial handle's downsampled grounding_extra_input goes the
+        // same way while the GLIGEN conv is in place; its SD-conv variant reads the latent alone.
+        const float* extra = e->f32("in.extra", (size_t)e->extra_bs * n_extra * sh * sw);
         CKP(extra);
-        CK(gl_pack_latent_extra(x_lat, extra, Bn / reps, e->extra_bs, cfg.in_channels, cfg.in_channels + 1, sh * sw, CIN_PAD, share ? 1 : reps,
-                                g_in_split && 3 * first_conv_in(cfg) <= CIN_PAD, xin, st));
+        CK(gl_pack_latent_extra(x_lat, extra, Bn / reps, e->extra_bs, cfg.in_channels, n_extra, sh * sw, CIN_PAD, share ? 1 : reps,
+                                g_in_split && 3 * first_conv_in(cfg, e->ground_extra) <= CIN_PAD, xin, st));
     } else {
         CK(gl_pack_latent(x_lat, Bn / reps, cfg.in_channels, sh * sw, CIN_PAD, share ? 1 : reps, g_in_split && 3 * cfg.in_channels <= CIN_PAD, xin, st));
     }
@@ -1121,12 +1129,16 @@ extern "C" int gl_create(const gl_unet_config* cfg, gl_engine** out) {
     if (!cfg || !out) return GL_ERR_BAD_ARG;
     if (cfg->n_levels <= 0 || cfg->n_levels > 8 || cfg->n_attn_res < 0 || cfg->n_attn_res > 8 || cfg->num_heads <= 0) return GL_ERR_BAD_ARG;
     if (cfg->model_channels % 64 || cfg->context_dim % 64 || cfg->pos_in_dim % 8 || cfg->pos_out_dim != cfg->context_dim) return GL_ERR_UNSUPPORTED;
-    if (cfg->grounding < 0 || cfg->grounding > 2 || cfg->max_objs <= 0) return GL_ERR_UNSUPPORTED;
+    if (cfg->grounding < 0 || (cfg->grounding > 2 && cfg->grounding != 4) || cfg->max_objs <= 0) return GL_ERR_UNSUPPORTED;
     if (cfg->grounding == 2) {
         // keypoint: 17 tokens per person, at most 8 persons; the first MLP layer's K is padded (pin_width), so no % 64 rule on it; no relation
         // chain (it pools over boxes) and no inpainting (its mask is drawn from boxes)
         if (cfg->no_relation != 1 || cfg->inpaint_mode != 0 || (cfg->max_objs % 17) != 0 || cfg->max_objs > 136) return GL_ERR_UNSUPPORTED;
         if (cfg->pos_in_dim != cfg->pos_out_dim) return GL_ERR_UNSUPPORTED;
+    } else if (cfg->grounding == 4) {
+        // spatial: finished tokens come in (no PositionNet in the table, so no rule on pos_in_dim + Fourier width); the upstream block only, no
+        // inpainting, no split-fp16 table (the tokenizer has no strict form); max_objs counts tokens, the gated self-attention's 64 at most
+        if (cfg->no_relation != 1 || cfg->inpaint_mode != 0 || cfg->split_weights != 0 || cfg->max_objs > 64) return GL_ERR_UNSUPPORTED;
     } else {
         if ((cfg->pos_in_dim + 8 * cfg->fourier_freqs) % 64) return GL_ERR_UNSUPPORTED;
         if (n_ground(*cfg) > 64) return GL_ERR_UNSUPPORTED;
@@ -1205,11 +1217,15 @@ extern "C" int gl_load_weights(gl_engine* e, const void* packed, int64_t bytes, 
 //   kept_inputs   those of them the family reads, with the pool tags a split_weights handle keeps device copies under for the lazy strict hoists
 //   posnet_input  the kernel that builds the MLP input rows of every chain ([nch, Bn * mo] chain-major rows of pin_width columns)
 //   posnet_chains / posnet_chain   the MLP chains those rows feed
-struct GroundIn { const float *loc = nullptr, *masks = nullptr, *emb = nullptr, *text_masks = nullptr, *image_masks = nullptr, *image_emb = nullptr; };
+//                 tokens: the finished grounding tokens [Bn, mo, D] of a spatial handle, which has no PositionNet of its own
+struct GroundIn {
+    const float *loc = nullptr, *masks = nullptr, *emb = nullptr, *text_masks = nullptr, *image_masks = nullptr, *image_emb = nullptr, *tokens = nullptr;
+};
 struct KeptIn { const char* tag; const float* GroundIn::*field; size_t n; };
 
 static std::vector<KeptIn> kept_inputs(const gl_unet_config& c, int Bn) {
     const size_t rows = (size_t)Bn * c.max_objs;
+    if (c.grounding == 4) return {{"cond.in.tokens", &GroundIn::tokens, rows * c.pos_out_dim}};
     if (c.grounding == 2) return {{"cond.in.points", &GroundIn::loc, rows * 2}, {"cond.in.masks", &GroundIn::masks, rows}};
     std::vector<KeptIn> k{{"cond.in.boxes", &GroundIn::loc, rows * 4}, {"cond.in.masks", &GroundIn::masks, rows}, {"cond.in.posemb", &GroundIn::emb, rows * c.pos_in_dim}};
     if (c.grounding == 1) {
@@ -1356,8 +1372,13 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     half_t* rel16 = rel ? e->h16("cond.rel", (size_t)Bn * R * ctx) : nullptr;
     CKP(pin); CKP(h1); CKP(h2); CKP(objs); CKP(ctx16);
     if (rel) CKP(rel16);
-    CK(posnet_input(e, in, Bn, false, pin, st));
-    for (int c = 0; c < nch; ++c) {
+    if (cfg.grounding == 4) {       // spatial: the tokens are the tokenizer stage's output, fp32 -> the fp16 operand of fuser.linear
+        f32_to_f16_kernel<<<dim3(64), dim3(256), 0, st>>>(in.tokens, objs, crow * D);
+        GL_CHECK_LAUNCH();
+    } else {
+        CK(posnet_input(e, in, Bn, false, pin, st));
+    }
+    for (int c = 0; c < (cfg.grounding == 4 ? 0 : nch); ++c) {
         const std::string pw = posnet_chain(cfg, c);
         const size_t o = c * crow;
         CK(r.gemm({pin + o * pin_dim, pin_dim}, pw + ".0", Bn * mo, h1 + o * 512, 512, {.epi = GL_EPI_SILU}));
@@ -1467,8 +1488,9 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
 // the grounding family is a property of the handle: each family has its own conditioning entries
 static int wrong_family(gl_engine* e, const char* entry, int want) {
     if (e->cfg.grounding == want) return 0;
-    static const char* const made[3] = {"0 (text)", "1 (text_image)", "2 (keypoint)"};
-    static const char* const use[3] = {"gl_set_conditioning / gl_set_conditioning_hw", "gl_set_conditioning_ti", "gl_set_conditioning_kp"};
+    static const char* const made[5] = {"0 (text)", "1 (text_image)", "2 (keypoint)", "3", "4 (spatial)"};
+    static const char* const use[5] = {"gl_set_conditioning / gl_set_conditioning_hw", "gl_set_conditioning_ti", "gl_set_conditioning_kp", "nothing",
+                                       "gl_set_conditioning_tokens"};
     e->err = std::string(entry) + ": the handle was created with grounding = " + made[e->cfg.grounding] + "; use " + use[e->cfg.grounding];
     return GL_ERR_BAD_ARG;
 }
@@ -1517,12 +1539,21 @@ extern "C" int gl_set_conditioning_kp(gl_engine* e, const float* context, const 
     return set_conditioning(e, context, nullptr, GroundIn{points, masks}, Bn, Lc, 0, h, w, stream);
 }
 
-extern "C" int gl_set_inpaint_extra(gl_engine* e, const float* extra, int32_t Bs, void* stream) {
+extern "C" int gl_set_conditioning_tokens(gl_engine* e, const float* context, const float* objs, int32_t Bn, int32_t Lc, int32_t h, int32_t w,
+                                          void* stream) {
     if (!e) return GL_ERR_BAD_ARG;
-    if (!e->cfg.inpaint_mode) { e->err = "gl_set_inpaint_extra: the handle was created with inpaint_mode = 0 (its first conv reads the latent alone)"; return GL_ERR_BAD_ARG; }
-    if (!e->cond_set) { e->err = "gl_set_inpaint_extra: no conditioning call has fixed the latent shape yet"; return GL_ERR_BAD_ARG; }
-    if (!extra || Bs < 1 || Bs > e->Bn) { e->err = "gl_set_inpaint_extra: extra must be a device pointer to Bs = 1 or Bn / reps samples"; return GL_ERR_BAD_ARG; }
-    const size_t n = (size_t)Bs * (e->cfg.in_channels + 1) * e->lat_h * e->lat_w;
+    CK(wrong_family(e, "gl_set_conditioning_tokens", 4));
+    CK(check_hw(e, "gl_set_conditioning_tokens", h, w));
+    GroundIn in;
+    in.tokens = objs;
+    return set_conditioning(e, context, nullptr, in, Bn, Lc, 0, h, w, stream);
+}
+
+// the extra channels of the GLIGEN first conv, by either family's entry: a pool buffer whose address the captured graphs read at replay time
+static int set_extra(gl_engine* e, const std::string& entry, const float* extra, int32_t Bs, void* stream) {
+    if (!e->cond_set) { e->err = entry + ": no conditioning call has fixed the latent shape yet"; return GL_ERR_BAD_ARG; }
+    if (!extra || Bs < 1 || Bs > e->Bn) { e->err = entry + ": extra must be a device pointer to Bs = 1 or Bn / reps samples"; return GL_ERR_BAD_ARG; }
+    const size_t n = (size_t)Bs * extra_channels(e->cfg, e->ground_extra) * e->lat_h * e->lat_w;
     e->pool_changed = false;
     float* dst = e->f32("in.extra", n);
     CKP(dst);
@@ -1534,6 +1565,39 @@ extern "C" int gl_set_inpaint_extra(gl_engine* e, const float* extra, int32_t Bs
     return 0;
 }
 
+extern "C" int gl_set_inpaint_extra(gl_engine* e, const float* extra, int32_t Bs, void* stream) {
+    if (!e) return GL_ERR_BAD_ARG;
+    if (!e->cfg.inpaint_mode) { e->err = "gl_set_inpaint_extra: the handle was created with inpaint_mode = 0 (its first conv reads the latent alone)"; return GL_ERR_BAD_ARG; }
+    return set_extra(e, "gl_set_inpaint_extra", extra, Bs, stream);
+}
+
+extern "C" int gl_set_extra_channels(gl_engine* e, int32_t channels) {
+    if (!e) return GL_ERR_BAD_ARG;
+    if (e->cfg.grounding != 4) {
+        e->err = "gl_set_extra_channels: only a spatial handle (grounding = 4) has a grounding downsampler in front of its first conv";
+        return GL_ERR_UNSUPPORTED;
+    }
+    if (channels < 0 || e->cfg.in_channels + channels > CIN_PAD) {
+        e->err = "gl_set_extra_channels: in_channels + channels must fit the first conv's " + std::to_string(CIN_PAD) + " padded input channels";
+        return GL_ERR_UNSUPPORTED;
+    }
+    if (channels != e->ground_extra) {       // the pack launch of the captured graphs and the extra buffer's size follow the count
+        e->drop_graphs();
+        e->extra_set = false;
+    }
+    e->ground_extra = channels;
+    return 0;
+}
+
+extern "C" int gl_set_grounding_extra(gl_engine* e, const float* extra, int32_t Bs, void* stream) {
+    if (!e) return GL_ERR_BAD_ARG;
+    if (e->ground_extra == 0) {
+        e->err = "gl_set_grounding_extra: the handle has no extra channels (gl_set_extra_channels): its first conv reads the latent alone";
+        return GL_ERR_BAD_ARG;
+    }
+    return set_extra(e, "gl_set_grounding_extra", extra, Bs, stream);
+}
+
 extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev, float t_host, int32_t reps, float fuser_scale, int32_t sd_conv,
                                float* eps, int32_t use_graph, void* stream) {
     if (!e || !e->cond_set || !x || !eps || reps < 1 || (e->Bn % reps) != 0) return GL_ERR_BAD_ARG;
@@ -1542,6 +1606,13 @@ extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev,
         if (!e->extra_set) { e->err = "gl_unet_forward: an inpaint_mode handle needs gl_set_inpaint_extra after the conditioning call that fixed (h, w)"; return GL_ERR_BAD_ARG; }
         if (e->extra_bs != 1 && e->extra_bs != e->Bn / reps) {
             e->err = "gl_unet_forward: the inpainting extra has " + std::to_string(e->extra_bs) + " samples, the latent " + std::to_string(e->Bn / reps);
+            return GL_ERR_BAD_ARG;
+        }
+    }
+    if (e->ground_extra != 0 && !sd_conv) {      // a spatial handle on its GLIGEN conv: the same host-side checks
+        if (!e->extra_set) { e->err = "gl_unet_forward: sd_conv = 0 on a handle with extra channels needs gl_set_grounding_extra after the conditioning call that fixed (h, w)"; return GL_ERR_BAD_ARG; }
+        if (e->extra_bs != 1 && e->extra_bs != e->Bn / reps) {
+            e->err = "gl_unet_forward: the grounding extra has " + std::to_string(e->extra_bs) + " samples, the latent " + std::to_string(e->Bn / reps);
             return GL_ERR_BAD_ARG;
         }
     }

@@ -109,6 +109,8 @@ class UNetEngine:
         given tensor; on every other engine ``None`` raises ValueError before anything is launched."""
         if self.cfg.grounding == "keypoint":
             raise ValueError("a keypoint model is conditioned on points and masks (set_conditioning_kp), not on boxes and embeddings")
+        if self.cfg.grounding == "spatial":
+            raise ValueError("boxes given to a spatial model: it is conditioned on the tokens of its map (set_conditioning_tokens)")
         rel_on = getattr(self.cfg, "relation", True)
         if not rel_on:
             relations = None
@@ -189,6 +191,50 @@ class UNetEngine:
         self.cond = dict(Bn=Bn, mo=mo, R=0, Lc=Lc, hw=hw, H=h, W=w)
 
     @torch.no_grad()
+    def set_conditioning_tokens(self, context, objs, hw) -> None:
+        """The conditioning of a spatial engine (``cfg.grounding == "spatial"``, gl_set_conditioning_tokens): context [Bn,77,ctx] and the
+        finished grounding tokens objs [Bn, n_ground, out_dim] (``spatial.SpatialTokenizer.tokens`` / ``null_tokens``), fp32 tensors (any
+        device).  ``hw``: the latent side or ``(h, w)``.  On an engine of another family: ValueError."""
+        if self.cfg.grounding != "spatial":
+            raise ValueError(f"grounding tokens of a map given to a {self.cfg.grounding} model: spatial grounding needs a canny / hed / depth / "
+                             "normal checkpoint")
+        h, w = (hw, hw) if isinstance(hw, int) else (int(v) for v in hw)
+        check_latent_hw(self.cfg, h, w)
+        dev = self.dev
+        f32 = lambda t: torch.as_tensor(t, dtype=F32).to(dev).contiguous()
+        context, objs = f32(context), f32(objs)
+        Bn, ng = objs.shape[0], self.cfg.n_ground
+        if tuple(objs.shape) != (Bn, ng, self.cfg.pos_out_dim):
+            raise ValueError(f"objs {tuple(objs.shape)}: the model takes [Bn, {ng}, {self.cfg.pos_out_dim}] grounding tokens")
+        if context.dim() != 3 or context.shape[0] != Bn or context.shape[-1] != self.cfg.context_dim:
+            raise ValueError("context does not match the batch or the model config")
+        Lc = context.shape[1]
+        with torch.cuda.device(dev):
+            self._check(self._lib.gl_set_conditioning_tokens(self.handle, context.data_ptr(), objs.data_ptr(), Bn, Lc, h, w, self._stream()),
+                        "gl_set_conditioning_tokens")
+        self._cond_refs = (context, objs)      # read asynchronously by the launched kernels
+        self.cond = dict(Bn=Bn, mo=ng, R=0, Lc=Lc, hw=hw, H=h, W=w)
+
+    @torch.no_grad()
+    def set_grounding_extra(self, extra: torch.Tensor) -> None:
+        """The downsampled ``grounding_extra_input`` of a spatial model (``spatial.SpatialDownsampler``): fp32 [1 | samples, ds_out, h, w] at the
+        conditioning's latent shape (gl_set_grounding_extra); the GLIGEN first conv reads cat([x, extra]), the SD conv the latent alone.  Call
+        it after ``set_conditioning_tokens``, once per image."""
+        if not self.cfg.ds_out:
+            raise ValueError("set_grounding_extra on a model without a grounding downsampler (its first conv reads the latent alone)")
+        c = self.cond
+        if c is None:
+            raise RuntimeError("call set_conditioning_tokens() first")
+        extra = torch.as_tensor(extra, dtype=F32).to(self.dev).contiguous()
+        want = (self.cfg.ds_out, c["H"], c["W"])
+        if extra.dim() != 4 or tuple(extra.shape[1:]) != want or not 1 <= extra.shape[0] <= c["Bn"]:
+            raise ValueError(f"downsampled grounding_extra_input {tuple(extra.shape)}: need [1 | samples, {want[0]}, {want[1]}, {want[2]}] (the "
+                             "latent has to be as large as the downsampler's output)")
+        with torch.cuda.device(self.dev):
+            self._check(self._lib.gl_set_grounding_extra(self.handle, extra.data_ptr(), int(extra.shape[0]), self._stream()), "gl_set_grounding_extra")
+        self._extra_ref = extra             # read asynchronously by the stream-ordered copy
+
+    @torch.no_grad()
     def set_inpaint_extra(self, extra: torch.Tensor) -> None:
         """The ``inpainting_extra_input`` of an inpaint_mode model (gligen_inference.py:406-407: cat([z0 * mask, mask], dim=1)): fp32
         [1 | samples, in_channels + 1, h, w] at the conditioning's latent shape (gl_set_inpaint_extra).  The engine copies it into a pool
@@ -208,7 +254,7 @@ class UNetEngine:
 
     def _check(self, code: int, what: str) -> None:
         """``check`` with the handle's gl_last_error message: the entries of an inpaint_mode handle leave one for every refusal"""
-        if code != 0 and (self.cfg.inpaint_mode or self.cfg.grounding == "keypoint"):
+        if code != 0 and (self.cfg.inpaint_mode or self.cfg.grounding in ("keypoint", "spatial")):
             msg = _lib.last_error(self.handle)
             if msg:
                 raise _lib.HipLibraryError(f"{what} failed with code {code}: {msg}")

@@ -29,6 +29,10 @@ A keypoint checkpoint (``checkpoint_generation_keypoint.pth``, ``keypoint_ground
 list of persons, each a list of 17 ``[x, y]`` in [0, 1] with ``[0, 0]`` for a missing keypoint (gligen_inference.py:199-218, :585-633); it
 needs neither ``phrases`` nor a CLIP model, and ``images`` / ``input_image`` raise ValueError.
 
+A spatial checkpoint (``checkpoint_generation_canny.pth`` / ``_hed`` / ``_depth`` / ``_normal``) takes its map under the reference's own meta
+key (``canny_image`` / ``hed_image`` / ``depth`` / ``normal``: a path or a ``PIL.Image``); it needs neither ``locations`` nor ``phrases`` nor a
+CLIP model, and ``images`` / ``input_image`` / boxes raise ValueError.
+
 A checkpoint without ``rela_fuse`` tensors (every public GLIGEN checkpoint) runs on the upstream transformer block it was trained with
 (attention_original.py:312-316): no relation phrases are parsed or encoded for it.
 """
@@ -63,8 +67,14 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     args = dict(batch_size=bs, no_plms=bool(_get(config, "no_plms", False)), guidance_scale=_get(config, "guidance_scale", 7.5))
     if _get(config, "negative_prompt") is not None:      # gligen_inference.py:379-380; absent / None = the empty prompt
         args["negative_prompt"] = _get(config, "negative_prompt")
-    m = dict(prompt=meta["prompt"], phrases=meta.get("phrases"), locations=meta["locations"],
+    # a spatial checkpoint (canny / hed / depth / normal; the reference routes on the checkpoint's file name, gligen_inference.py:365-372, here
+    # the loaded model decides) is grounded on one map under the reference's own meta key: no locations, no phrases
+    spatial = getattr(getattr(all_models[0], "cfg", None), "grounding", "text") == "spatial"
+    m = dict(prompt=meta["prompt"], phrases=meta.get("phrases"), locations=meta.get("locations") if spatial else meta["locations"],
              alpha_type=meta.get("alpha_type", [0.3, 0.0, 0.7]), input_image=meta.get("input_image"))
+    for k in interface.SPATIAL_META_KEYS:
+        if meta.get(k) is not None:
+            m[k] = meta[k]
     # image grounding (a *_box_text_image checkpoint, gligen_inference.py:350-352): one reference image or None per box
     for k in ("images", "text_mask", "image_mask", "projection_matrix"):
         if meta.get(k) is not None:
@@ -75,7 +85,7 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     # a keypoint checkpoint (the reference routes on "keypoint" in meta["ckpt"], gligen_inference.py:363; here the loaded model decides) is
     # grounded on meta["locations"] = persons of 17 [x, y] alone: no phrases, and no CLIP model to create
     keypoint = getattr(getattr(all_models[0], "cfg", None), "grounding", "text") == "keypoint"
-    if not keypoint and (clip_model is None or clip_processor is None):
+    if not keypoint and not spatial and (clip_model is None or clip_processor is None):
         from transformers import CLIPModel, CLIPProcessor
         version = "openai/clip-vit-large-patch14"
         clip_model = CLIPModel.from_pretrained(version).to(device)

@@ -149,8 +149,18 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
     saved_ckpt = torch.load(ckpt_path, map_location="cpu")
     config = saved_ckpt["config_dict"]["_content"]
     # (_run builds the inpainting extra an inpaint_mode model needs, and the points / masks batch of a keypoint model)
-    cfg = UNetConfig.from_dict(config["model"]["params"], allow_inpaint=True, allow_keypoint=True)
+    # (... and the map batch of a spatial model: canny / hed / depth / normal, whose ConvNeXt tokenizer and grounding downsampler are built
+    # from the checkpoint's own position_net.* / downsample_net.* tensors -- nothing is fetched)
+    cfg = UNetConfig.from_dict(config["model"]["params"], allow_inpaint=True, allow_keypoint=True, allow_spatial=True)
     import dataclasses
+    if cfg.grounding == "spatial" and any(".rela_fuse." in k for k in saved_ckpt["model"]):
+        raise NotImplementedError("a spatial checkpoint with *.rela_fuse.* tensors: the relation chain pools image features over grounding "
+                                  "boxes, and a spatial model has none (it runs on the upstream block only)")
+    if cfg.grounding == "spatial":
+        # the ConvNeXt's depths and widths are the checkpoint's own (its config does not state them; the shipped ones are convnext_tiny's)
+        from .spatial import backbone_of
+        depths, dims = backbone_of(saved_ckpt["model"])
+        cfg = dataclasses.replace(cfg, convnext_depths=depths, convnext_dims=dims)
     if cfg.grounding == "keypoint" and any(".rela_fuse." in k for k in saved_ckpt["model"]):
         raise NotImplementedError("a keypoint checkpoint with *.rela_fuse.* tensors: the relation chain pools image features over grounding "
                                   "boxes, and a keypoint model has none (keypoint grounding runs on the upstream block only)")
@@ -158,6 +168,9 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
     cfg = dataclasses.replace(cfg, relation=checkpoint_has_relation(saved_ckpt["model"], cfg))
     if strict is None:
         strict = os.environ.get("GLIGEN_STRICT") == "1"
+    if strict and cfg.grounding == "spatial":
+        raise NotImplementedError("strict mode (strict=True / GLIGEN_STRICT=1) of a spatial checkpoint: the ConvNeXt tokenizer has no split-fp16 "
+                                  "form; load it in the default mode")
     if strict:
         cfg = dataclasses.replace(cfg, split_weights=True)
     # (an inpaint_mode checkpoint's 9-channel first conv is not restorable, openaimodel.py:296: the SD conv file is neither looked for nor missed)
@@ -406,6 +419,50 @@ def prepare_batch_kp_multiple(meta, batch, max_persons=8, device=None):
     return {k: v.to(device) for k, v in out.items()} if device is not None else out
 
 
+SPATIAL_META_KEYS = ("canny_image", "hed_image", "depth", "normal")       # the reference's own meta keys (gligen_inference.py:226-289)
+
+
+def _spatial_map_of(meta):
+    """the one map a meta dict carries under the reference's keys, or None"""
+    given = [k for k in SPATIAL_META_KEYS if meta.get(k) is not None]
+    if len(given) > 1:
+        raise ValueError(f"meta carries more than one grounding map: {given}")
+    return meta[given[0]] if given else None
+
+
+def load_spatial_map(image) -> torch.Tensor:
+    """gligen_inference.py:190-194 + :226-228: ``Image.open(path).convert("RGB")`` (or a ``PIL.Image``), torchvision's centre crop to the
+    shorter side (top / left = round((side - crop) / 2)), PIL ``resize((512, 512))`` (its default filter), pil_to_tensor, ``/ 255``,
+    ``(v - 0.5) / 0.5`` -> fp32 [3, 512, 512]"""
+    from PIL import Image
+    im = image if isinstance(image, Image.Image) else Image.open(image)
+    im = im.convert("RGB")
+    w, h = im.size
+    crop = min(w, h)
+    top, left = int(round((h - crop) / 2.0)), int(round((w - crop) / 2.0))
+    im = im.crop((left, top, left + crop, top + crop)).resize((512, 512))
+    x = torch.from_numpy(np.array(im, dtype=np.uint8)).permute(2, 0, 1).contiguous()       # torchvision PILToTensor
+    return (x.float() / 255 - 0.5) / 0.5
+
+
+@torch.no_grad()
+def prepare_batch_spatial(meta, batch=1, device=None):
+    """gligen_inference.py:221-297 (prepare_batch_hed / _canny / _depth / _normal, one function here: they differ in the meta key alone).  The
+    map under ``meta["canny_image"]`` / ``["hed_image"]`` / ``["depth"]`` / ``["normal"]`` (a path or a ``PIL.Image``) repeated ``batch`` times:
+    ``map`` [batch, 3, 512, 512] in [-1, 1] and ``mask`` [batch, 1] of ones.  A list of ``batch`` maps gives one map per sample."""
+    src = _spatial_map_of(meta)
+    if src is None:
+        raise ValueError(f"a spatial checkpoint needs its map under one of the meta keys {SPATIAL_META_KEYS}")
+    if isinstance(src, (list, tuple)):
+        if len(src) != batch:
+            raise ValueError(f"{len(src)} grounding maps for a batch of {batch}")
+        maps = torch.stack([load_spatial_map(s) for s in src], 0)
+    else:
+        maps = load_spatial_map(src).unsqueeze(0).repeat(batch, 1, 1, 1)
+    out = {"map": maps, "mask": torch.ones(batch, 1)}
+    return {k: v.to(device) for k, v in out.items()} if device is not None else out
+
+
 @torch.no_grad()
 def prepare_batch_multiple(meta, model, processor, batch=1, max_objs=MAX_OBJS, device=None):
     """interface.py:424-475: one layout per prompt."""
@@ -511,20 +568,21 @@ def build_inpainting_extra(z0, mask):
 
 @torch.no_grad()
 def denoise(all_models, context, uc, relations, grounding_batch, starting_noise, alpha_type=None, guidance_scale=7.5,
-            steps=PLMS_STEPS, mask=None, x0=None, inpainting_extra_input=None):
+            steps=PLMS_STEPS, mask=None, x0=None, inpainting_extra_input=None, grounding_extra_input=None):
     """The denoising hot path proper, from conditioning tensors to the final latent
     (run_batch_images lines interface.py:505-539 without text/VAE stages).  ``mask`` [1|B, 1, h, w] (1 = keep) and ``x0``
     [1|B, 4, h, w] (the encoded input image): inpainting, plms.py:95-99.  The latent's shape [B, 4, h, w] is ``starting_noise``'s
     (plms.py:68-71); h != w needs both to be multiples of 2^(number of UNet downsamples) = 8.  ``inpainting_extra_input`` [1|B, 5, h, w]: the
     extra first-conv input of an inpaint_mode model (required there, ignored by every other model).  ``relations``: None for a model without
-    the relation chain (ignored there); a model with it raises ValueError on None before any kernel runs."""
+    the relation chain (ignored there); a model with it raises ValueError on None before any kernel runs.  ``grounding_extra_input``
+    [B, 3, H, W]: the map a spatial model's grounding downsampler reads (required there, ignored by every other model)."""
     model, autoencoder, text_encoder, diffusion, config = all_models
     _check_noise(model, starting_noise)
     sampler = PLMSSampler(diffusion, model, alpha_generator_func=partial(alpha_generator, type=alpha_type),
                           set_alpha_scale=set_alpha_scale)
     grounding_input = model.grounding_tokenizer_input.prepare(grounding_batch, text_encoder)
     input = dict(x=starting_noise, timesteps=None, context=context, relations=relations, grounding_input=grounding_input,
-                 inpainting_extra_input=inpainting_extra_input, grounding_extra_input=None)
+                 inpainting_extra_input=inpainting_extra_input, grounding_extra_input=grounding_extra_input)
     shape = tuple(starting_noise.shape)
     return sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=mask, x0=x0)
 
@@ -551,6 +609,19 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
         # (the reference would prepare image tokens and drop them silently: text_layout_tokinzer_input.py reads three keys)
         raise ValueError("meta['images'] given to a text-only checkpoint: image grounding needs a *_box_text_image checkpoint "
                          "(grounding_tokenizer target text_image_grounding_net.PositionNet)")
+    spatial = getattr(model.cfg, "grounding", "text") == "spatial"
+    if not spatial and _spatial_map_of(meta) is not None:
+        raise ValueError(f"a grounding map ({[k for k in SPATIAL_META_KEYS if meta.get(k) is not None][0]}) given to a {model.cfg.grounding} "
+                         "checkpoint: maps need a canny / hed / depth / normal checkpoint")
+    if spatial:
+        # (before any encoder or kernel runs)
+        for k, why in (("images", "it is grounded on a map, not on reference images"), ("input_image", "there is no inpainting form of it"),
+                       ("locations", "it takes no boxes")):
+            if meta.get(k) is not None and (k != "locations" or len(meta[k]) > 0):
+                raise ValueError(f"meta[{k!r}] given to a spatial checkpoint: {why}")
+        if _spatial_map_of(meta) is None:
+            raise ValueError(f"a spatial checkpoint needs its map under one of the meta keys {SPATIAL_META_KEYS}")
+        model.grounding_extra_of({"grounding_extra_input": True}, tuple(int(v) for v in starting_noise.shape[-2:]))      # the latent-size rule
     keypoint = getattr(model.cfg, "grounding", "text") == "keypoint"       # the batch builder follows the model, not the checkpoint's file name
     if keypoint and meta.get("images") is not None:
         raise ValueError("meta['images'] given to a keypoint checkpoint: it is grounded on poses (meta['locations'] = persons of 17 [x, y])")
@@ -571,13 +642,15 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     relations = None
     if multiple:
         # (a keypoint model: no phrases, no CLIP model, and -- always on the upstream block -- no relation phrases)
-        batch = prepare_batch_kp_multiple(meta, bs, model.cfg.max_persons, device) if keypoint else \
+        batch = prepare_batch_spatial(meta, bs, device) if spatial else \
+            prepare_batch_kp_multiple(meta, bs, model.cfg.max_persons, device) if keypoint else \
             prepare_batch_multiple(meta, clip_model, clip_processor, bs, device=device)
         context = text_encoder.encode(meta["prompts"])
         if with_rel:
             relations = prepare_relation_phrases_batch(meta["prompts"], max_rel, text_encoder, device=device)
     else:
-        batch = prepare_batch_kp(meta, bs, model.cfg.max_persons, device) if keypoint else \
+        batch = prepare_batch_spatial(meta, bs, device) if spatial else \
+            prepare_batch_kp(meta, bs, model.cfg.max_persons, device) if keypoint else \
             prepare_batch(meta, clip_model, clip_processor, bs, device=device)
         context = text_encoder.encode([meta["prompt"]] * bs)
         if with_rel:
@@ -608,7 +681,8 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     # S is a harness parameter: the reference hard-codes 50 (interface.py:507); ``args["steps"]`` overrides it
     samples = denoise(all_models, context, uc, relations, batch, starting_noise, meta.get("alpha_type"), cfg.guidance_scale,
                       steps=int(args.get("steps", PLMS_STEPS)), mask=mask, x0=z0,   # steps per call: not sticky through the cached config
-                      inpainting_extra_input=extra)
+                      inpainting_extra_input=extra,
+                      grounding_extra_input=batch["map"] if spatial else None)      # *_grounding_downsampler_input.prepare: the map itself
     return _postprocess(autoencoder.decode(samples))
 
 

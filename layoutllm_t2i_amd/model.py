@@ -143,7 +143,32 @@ class KeypointGroundingNetInput:
                 "masks": torch.zeros(batch, self.max_persons_per_image * 17).type(dtype).to(device)}
 
 
-_GROUNDING_INPUTS = {"text": GroundingNetInput, "text_image": TextImageGroundingNetInput, "keypoint": KeypointGroundingNetInput}
+class SpatialGroundingNetInput:
+    """{canny,hed,depth,normal}_grounding_tokinzer_input.py:6-43 under generic keys: pass-through of ``map`` [B, 3, H, W] in [-1, 1] (the
+    reference's canny_edge / hed_edge / depth / normal) and ``mask`` [B]; the null input is a zero map with a zero mask."""
+    KEYS = ("map", "mask")
+
+    def __init__(self):
+        self.set = False
+
+    def prepare(self, batch, text_encoder=None):
+        self.set = True
+        map_, mask = batch["map"], batch["mask"]
+        self.batch, self.C, self.H, self.W = map_.shape
+        self.device = map_.device
+        self.dtype = map_.dtype
+        return {"map": map_, "mask": mask}
+
+    def get_null_input(self, batch=None, device=None, dtype=None):
+        assert self.set, "not set yet, cannot call this funcion"
+        batch = self.batch if batch is None else batch
+        device = self.device if device is None else device
+        dtype = self.dtype if dtype is None else dtype
+        return {"map": torch.zeros(batch, self.C, self.H, self.W).type(dtype).to(device), "mask": torch.zeros(batch).type(dtype).to(device)}
+
+
+_GROUNDING_INPUTS = {"text": GroundingNetInput, "text_image": TextImageGroundingNetInput, "keypoint": KeypointGroundingNetInput,
+                     "spatial": SpatialGroundingNetInput}
 
 
 def grounding_input_for(cfg: UNetConfig):
@@ -176,8 +201,16 @@ class UNetModel:
         self.grounding_tokenizer_input: Optional[GroundingNetInput] = None   # set externally (interface.py:370)
         self.fuser_scale = 1.0          # what set_alpha_scale writes (interface.py:34-38)
         self.training = False
+        if cfg.grounding == "spatial" and getattr(cfg, "split_weights", False):
+            raise NotImplementedError("strict mode (split_weights) of a spatial model: the ConvNeXt tokenizer has no split-fp16 form")
         packed = pack_state_dict(state_dict, cfg, self.device, sd_first_conv)
         self.engine = UNetEngine(packed)
+        self.tokenizer = self.downsampler = None
+        if cfg.grounding == "spatial":
+            # the two stages in front of the UNet, from the checkpoint's own position_net.* / downsample_net.* tensors
+            from .spatial import SpatialDownsampler, SpatialTokenizer
+            self.tokenizer = SpatialTokenizer(state_dict, cfg, self.device)
+            self.downsampler = SpatialDownsampler(state_dict, cfg, self.device)
         self._cond_key = None
         self.strict = False
 
@@ -244,7 +277,9 @@ class UNetModel:
             missing = [k for k in keys if k not in grounding]
             if missing:
                 raise ValueError(f"a {self.cfg.grounding} model needs the grounding keys {keys}; missing {missing}")
-        if self.cfg.grounding == "keypoint":
+        if self.cfg.grounding == "spatial":
+            self.engine.set_conditioning_tokens(context, self.tokenizer.tokens(grounding["map"], grounding["mask"]), hw)
+        elif self.cfg.grounding == "keypoint":
             self.engine.set_conditioning_kp(context, grounding["points"], grounding["masks"], hw)
         elif self.cfg.grounding == "text_image":
             self.engine.set_conditioning(context, relations, grounding["boxes"], grounding["masks"], grounding["text_embeddings"], hw,
@@ -278,10 +313,34 @@ class UNetModel:
                              "(gligen_inference.py:406-407)")
         return extra
 
+    def grounding_extra_of(self, input: dict, hw=None) -> Optional[torch.Tensor]:
+        """``input["grounding_extra_input"]`` (openaimodel_original.py:430-432): the map [B, 3, H, W] the grounding downsampler of a spatial
+        model reads; required there (ValueError before any kernel runs), ignored on every other model, as the reference ignores it.  ``hw``:
+        the latent's (h, w), which has to be the downsampler's output size (the reference fails inside th.cat otherwise)."""
+        if getattr(self, "downsampler", None) is None:
+            return None
+        extra = input.get("grounding_extra_input")
+        if extra is None:
+            raise ValueError("a spatial model needs input['grounding_extra_input'], the map its grounding downsampler reads "
+                             "(gligen_inference.py:412-422)")
+        side = self.cfg.ds_latent
+        if hw is not None and tuple(hw) != (side, side):
+            raise ValueError(f"latent {hw[0]} x {hw[1]}: this model's grounding downsampler yields {side} x {side} (resize_input / 4; 64 for hed), "
+                             "and the latent has to match it")
+        return extra
+
     @torch.no_grad()
     def __call__(self, input: dict) -> torch.Tensor:
         """UNetModel.forward (openaimodel.py:413-459): one B-sized evaluation."""
         x = input["x"]
+        if getattr(self, "downsampler", None) is not None:
+            gextra = None if self.use_sd_conv else self.grounding_extra_of(input, tuple(int(v) for v in x.shape[-2:]))
+            H, W = (int(v) for v in x.shape[-2:])
+            self.set_conditioning(input["context"], None, self.grounding_of(input), H if H == W else (H, W), key=None)
+            if gextra is not None:
+                self.engine.set_grounding_extra(self.downsampler(gextra))
+            return self.engine.forward(x.to(self.device, torch.float32).contiguous(), input["timesteps"], self.fuser_scale, self.use_sd_conv,
+                                       1).clone()
         extra = self.inpaint_extra_of(input)
         rel = self.relations_of(input)
         g = self.grounding_of(input)

@@ -810,3 +810,121 @@ def resample_v_norm(x: torch.Tensor, bounds: torch.Tensor, coeffs: torch.Tensor,
                                         out.data_ptr() if out is not None else None, out_u8.data_ptr() if out_u8 is not None else None,
                                         _stream()), "gl_resample_v_norm")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- spatial grounding (spatial.hip)
+def _c32(t: torch.Tensor, name: str) -> None:
+    _req(t, F32, name, 4)
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def sp_stem_patchify(map_: torch.Tensor, R: int, out: torch.Tensor) -> torch.Tensor:
+    """map fp32 [B, 3, S, S] -> nearest resize to R x R -> fp16 patch rows [B * (R/4)^2, 64] of the 4x4 stride-4 stem conv (gl_sp_stem_patchify)"""
+    _c32(map_, "map")
+    if map_.dim() != 4 or map_.shape[1] != 3 or map_.shape[2] != map_.shape[3] or R % 4:
+        raise ValueError(f"map {tuple(map_.shape)}: need [B, 3, S, S] and R % 4 == 0")
+    B, S = map_.shape[0], map_.shape[2]
+    _req(out, F16, "out")
+    if not out.is_contiguous() or tuple(out.shape) != (B * (R // 4) ** 2, 64):
+        raise ValueError(f"out: need a contiguous [{B * (R // 4) ** 2}, 64] tensor")
+    check(_lib.lib().gl_sp_stem_patchify(map_.data_ptr(), B, S, R, out.data_ptr(), _stream()), "gl_sp_stem_patchify")
+    return out
+
+
+def sp_layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """LayerNorm (eps 1e-6) over the columns of fp32 rows [M, C], fp32 out (``y`` may be ``x``)"""
+    for t, n in ((x, "x"), (gamma, "gamma"), (beta, "beta"), (y, "y")):
+        _c32(t, n)
+    M, C = x.shape
+    if tuple(y.shape) != (M, C) or gamma.numel() != C or beta.numel() != C:
+        raise ValueError("sp_layernorm: inconsistent shapes")
+    check(_lib.lib().gl_sp_layernorm(x.data_ptr(), M, C, gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _stream()), "gl_sp_layernorm")
+    return y
+
+
+def sp_dwconv_ln(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, B: int, H: int, W: int,
+                 out: torch.Tensor) -> torch.Tensor:
+    """x fp32 NHWC rows [B * H * W, C], w fp32 [49, C] (tap-major depthwise 7x7), -> LayerNorm (eps 1e-6) -> fp16 [B * H * W, ldo], ldo = C rounded
+    up to 64 with zero pad columns (gl_sp_dwconv_ln)"""
+    for t, n in ((x, "x"), (w, "w"), (bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        _c32(t, n)
+    C = x.shape[-1]
+    if x.numel() != B * H * W * C or tuple(w.shape) != (49, C) or bias.numel() != C or gamma.numel() != C or beta.numel() != C:
+        raise ValueError("sp_dwconv_ln: inconsistent shapes")
+    _req(out, F16, "out")
+    if out.dim() != 2 or not out.is_contiguous() or out.shape[0] != B * H * W or out.shape[1] % 64 or out.shape[1] < C:
+        raise ValueError(f"out: need a contiguous [{B * H * W}, C rounded up to 64] tensor")
+    check(_lib.lib().gl_sp_dwconv_ln(x.data_ptr(), w.data_ptr(), bias.data_ptr(), gamma.data_ptr(), beta.data_ptr(), B, H, W, C, out.shape[1],
+                                     out.data_ptr(), _stream()), "gl_sp_dwconv_ln")
+    return out
+
+
+def sp_gelu(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """erf-GELU on contiguous fp16 values (gl_sp_gelu); ``y`` may be ``x``"""
+    _req(x, F16, "x", 4)
+    _req(y, F16, "y", 4)
+    if not x.is_contiguous() or not y.is_contiguous() or x.numel() != y.numel() or x.numel() % 2:
+        raise ValueError("sp_gelu: contiguous tensors of one even size")
+    check(_lib.lib().gl_sp_gelu(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "gl_sp_gelu")
+    return y
+
+
+def sp_down_gather(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, B: int, H: int, W: int, out: torch.Tensor) -> torch.Tensor:
+    """x fp32 NHWC rows [B * H * W, C] -> per-pixel LayerNorm -> fp16 [B * H/2 * W/2, 4 C], the operand of the 2x2 stride-2 conv (gl_sp_down_gather)"""
+    for t, n in ((x, "x"), (gamma, "gamma"), (beta, "beta")):
+        _c32(t, n)
+    C = x.shape[-1]
+    _req(out, F16, "out")
+    if x.numel() != B * H * W * C or H % 2 or W % 2 or not out.is_contiguous() or tuple(out.shape) != (B * (H // 2) * (W // 2), 4 * C) or \
+            gamma.numel() != C or beta.numel() != C:
+        raise ValueError("sp_down_gather: inconsistent shapes")
+    check(_lib.lib().gl_sp_down_gather(x.data_ptr(), B, H, W, C, gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), _stream()), "gl_sp_down_gather")
+    return out
+
+
+def sp_assemble(feat: torch.Tensor, mask: torch.Tensor, null_feature: torch.Tensor, pos: torch.Tensor, B: int, T: int, out: torch.Tensor) -> torch.Tensor:
+    """feat fp32 [B * T, C], mask [B], null_feature [C], pos [T, C] -> fp16 [B * T, C] = feat * m + null * (1 - m) + pos (gl_sp_assemble)"""
+    for t, n in ((feat, "feat"), (mask, "mask"), (null_feature, "null_feature"), (pos, "pos")):
+        _c32(t, n)
+    C = feat.shape[-1]
+    _req(out, F16, "out")
+    if tuple(feat.shape) != (B * T, C) or mask.numel() != B or null_feature.numel() != C or pos.numel() != T * C or not out.is_contiguous() or \
+            tuple(out.shape) != (B * T, C):
+        raise ValueError("sp_assemble: inconsistent shapes")
+    check(_lib.lib().gl_sp_assemble(feat.data_ptr(), mask.data_ptr(), null_feature.data_ptr(), pos.data_ptr(), B, T, C, out.data_ptr(), _stream()),
+          "gl_sp_assemble")
+    return out
+
+
+def sp_bicubic(x: torch.Tensor, C: int, iy: torch.Tensor, wy: torch.Tensor, ix: torch.Tensor, wx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """Bicubic resize of the first C channels of x fp32 [B, Ct, Hin, Win] from index / weight tables [Hout | Wout, 4] (spatial.bicubic_table)"""
+    _c32(x, "x")
+    _c32(wy, "wy")
+    _c32(wx, "wx")
+    _c32(out, "out")
+    _req(iy, torch.int32, "iy", 4)
+    _req(ix, torch.int32, "ix", 4)
+    B, Ct, Hin, Win = x.shape
+    Hout, Wout = iy.shape[0], ix.shape[0]
+    if tuple(iy.shape) != (Hout, 4) or tuple(wy.shape) != (Hout, 4) or tuple(ix.shape) != (Wout, 4) or tuple(wx.shape) != (Wout, 4) or \
+            not iy.is_contiguous() or not ix.is_contiguous() or tuple(out.shape) != (B, C, Hout, Wout) or not 1 <= C <= Ct:
+        raise ValueError("sp_bicubic: inconsistent shapes")
+    if int(iy.min()) < 0 or int(iy.max()) >= Hin or int(ix.min()) < 0 or int(ix.max()) >= Win:
+        raise ValueError("sp_bicubic: a table index lies outside the input")
+    check(_lib.lib().gl_sp_bicubic(x.data_ptr(), B, Ct, C, Hin, Win, iy.data_ptr(), wy.data_ptr(), ix.data_ptr(), wx.data_ptr(), Hout, Wout,
+                                   out.data_ptr(), _stream()), "gl_sp_bicubic")
+    return out
+
+
+def sp_conv4x4s2(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, silu: bool, out: torch.Tensor) -> torch.Tensor:
+    """Conv2d(Ci, Co, 4, 2, 1) on fp32 NCHW with an optional SiLU (gl_sp_conv4x4s2); Ci, Co <= 8"""
+    for t, n in ((x, "x"), (w, "w"), (bias, "bias"), (out, "out")):
+        _c32(t, n)
+    B, Ci, H, W = x.shape
+    Co = w.shape[0]
+    if tuple(w.shape) != (Co, Ci, 4, 4) or bias.numel() != Co or H % 2 or W % 2 or tuple(out.shape) != (B, Co, H // 2, W // 2):
+        raise ValueError("sp_conv4x4s2: inconsistent shapes")
+    check(_lib.lib().gl_sp_conv4x4s2(x.data_ptr(), w.data_ptr(), bias.data_ptr(), B, Ci, Co, H, W, int(bool(silu)), out.data_ptr(), _stream()),
+          "gl_sp_conv4x4s2")
+    return out

@@ -57,8 +57,8 @@ def tensor(name: str, shape: Tuple[int, ...], seed: int = 0) -> np.ndarray:
         # non-zero gates, sign and size vary per module: tanh in roughly +-[0.3, 0.6]
         u = float(uniform(name, (1,), seed)[0])
         return np.float32(np.copysign(0.3 + 0.35 * abs(u), u if u != 0 else 1.0)).reshape(())
-    if leaf.startswith("null_") or leaf in ("person_embeddings", "keypoint_embeddings"):
-        # (the keypoint PositionNet's two learned tables: O(1) rows like the null features, none of them zero)
+    if leaf.startswith("null_") or leaf in ("person_embeddings", "keypoint_embeddings", "pos_embedding"):
+        # (the keypoint PositionNet's two learned tables, the spatial tokenizer's position table: O(1) rows like the null features, none zero)
         return uniform(name, shape, seed) * np.float32(0.5)
     is_norm = (".norm" in name or "in_layers.0" in name or "out_layers.0" in name
                or name.startswith("out.0") or "norm_out" in name)

@@ -341,6 +341,10 @@ def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_
     P.emb_total = off
     norm("out.0")
     conv3("out.2")
+    if cfg.grounding == "spatial":
+        # the ConvNeXt tokenizer and the grounding downsampler are stages of their own (spatial.SpatialTokenizer / SpatialDownsampler pack
+        # position_net.* and downsample_net.*): the handle takes finished tokens, its table has no position_net.* entries
+        return P.to_flat()
     if cfg.grounding == "text_image":
         W["position_net.null_text"] = g("position_net.null_text_feature").contiguous()
         W["position_net.null_image"] = g("position_net.null_image_feature").contiguous()
@@ -382,7 +386,7 @@ def random_state_dict(cfg: UNetConfig, device, seed: int = 0) -> Dict[str, torch
         if leaf in ("alpha_attn", "alpha_dense"):
             v = u().reshape(())
             t = torch.sign(v) * (0.3 + 0.35 * v.abs())
-        elif leaf.startswith("null_") or leaf in ("person_embeddings", "keypoint_embeddings"):
+        elif leaf.startswith("null_") or leaf in ("person_embeddings", "keypoint_embeddings", "pos_embedding"):
             t = u() * 0.5
         elif (".norm" in name or "in_layers.0" in name or "out_layers.0" in name or name.startswith("out.0")) and len(shape) == 1:
             t = 1.0 + 0.1 * u() if leaf == "weight" else 0.05 * u()
