@@ -414,25 +414,32 @@ def create_vae(cfg, encoder: bool = False, fold_up=None) -> int:
     return h.value
 
 
-def vae_weight_table(handle: int):
-    l = lib()
+def _read_table(handle: int, prefix: str):
+    """[(name, offset, nbytes, dtype 0 = fp16 / 1 = fp32, shape)] of the flat packed-weight buffer, + total bytes"""
+    num, at, total = (getattr(lib(), prefix + s) for s in ("num_weights", "weight_at", "weights_bytes"))
     out = []
     info = WeightInfo()
-    for i in range(l.gl_vae_num_weights(handle)):
-        check(l.gl_vae_weight_at(handle, i, C.byref(info)), "gl_vae_weight_at")
+    for i in range(num(handle)):
+        check(at(handle, i, C.byref(info)), prefix + "weight_at")
         out.append((info.name.decode(), int(info.offset), int(info.nbytes), int(info.dtype), tuple(int(info.shape[k]) for k in range(info.ndim))))
-    return out, int(l.gl_vae_weights_bytes(handle))
+    return out, int(total(handle))
+
+
+def vae_weight_table(handle: int):
+    return _read_table(handle, "gl_vae_")
 
 
 def weight_table(handle: int):
-    """[(name, offset, nbytes, dtype 0 = fp16 / 1 = fp32, shape)] of the flat packed-weight buffer, + total bytes"""
-    l = lib()
-    out = []
-    info = WeightInfo()
-    for i in range(l.gl_num_weights(handle)):
-        check(l.gl_weight_at(handle, i, C.byref(info)), "gl_weight_at")
-        out.append((info.name.decode(), int(info.offset), int(info.nbytes), int(info.dtype), tuple(int(info.shape[k]) for k in range(info.ndim))))
-    return out, int(l.gl_weights_bytes(handle))
+    return _read_table(handle, "gl_")
+
+
+def engine_table(cfg, fold_up=None):
+    """The weight table of a UNet handle for ``cfg``: create handle, read table, destroy handle.  Needs no GPU."""
+    handle = create_engine(cfg, fold_up)
+    try:
+        return weight_table(handle)
+    finally:
+        check(lib().gl_destroy(handle), "gl_destroy")
 
 
 def last_error(handle) -> str:

@@ -40,7 +40,7 @@ def build(force: bool = False, verbose: bool = True, variant: str = "", defines=
     OBJDIR = os.path.join(HERE, "build_" + variant) if variant else globals()["OBJDIR"]
     LIB = os.path.join(PKG, f"libgligen_hip_{variant}.so") if variant else globals()["LIB"]
     os.makedirs(OBJDIR, exist_ok=True)
-    deps = [os.path.join(HERE, "common.h"), os.path.join(HERE, "gemm_shared.h"), os.path.join(HERE, "opts.h"), os.path.join(REPO, "include", "gligen_hip.h")]
+    deps = [os.path.join(HERE, "common.h"), os.path.join(HERE, "gemm_shared.h"), os.path.join(HERE, "opts.h"), os.path.join(HERE, "handle.h"), os.path.join(REPO, "include", "gligen_hip.h")]
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(REPO, "include"), "-I" + HERE, *["-D" + d for d in defines]]
 
     # per-file extras: attention keeps MFMA results in VGPRs (no v_accvgpr_read/write round trips in the

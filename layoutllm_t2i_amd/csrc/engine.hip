@@ -12,6 +12,7 @@
 //   * one hipGraph per (shape, fuser on/off, first-conv variant), replayed per step.
 #include "common.h"
 #include "gligen_hip.h"
+#include "handle.h"
 #include "opts.h"
 
 #include <cmath>
@@ -26,7 +27,6 @@
 namespace {
 
 constexpr int CIN_PAD = 64;              // the 4-channel latent is zero-padded to one 64-channel K block
-constexpr int64_t ALIGN = 256;
 #define g_fuse_merge_ln gl_opt(25)  // default 1;                 // A/B knob (gl_set_option 25): rela_merge also writes LayerNorm(norm2) of its rows
 #define g_fuse_vt gl_opt(21)  // default 1;                       // A/B knob (gl_set_option 21): V^T written by the QKV GEMM epilogue (1) or by gl_transpose_v (0)
 #define g_force_fuser gl_opt(20)  // default 0;                   // test knob (gl_set_option 20): execute the fuser even at scale 0 (zero gates)
@@ -52,11 +52,7 @@ struct LayerD {
 struct BlockD {
     std::vector<LayerD> layers;
 };
-struct WInfo {
-    int64_t off, bytes;
-    int dtype, ndim;
-    int64_t shape[4];
-};
+using WInfo = gl_weight_table::Entry;
 // everything a captured launch sequence depends on besides the pool addresses and the option generation (which drop every graph)
 struct GraphKey {
     int Bn, lat_h, lat_w, R, Lc;
@@ -147,19 +143,12 @@ struct gl_engine {
     BlockD middle;
     int out_channels_last = 0;
     std::vector<LayerD> st_layers;
-    // packed weights
-    std::vector<std::string> names;
-    std::unordered_map<std::string, WInfo> tab;
-    int64_t total_bytes = 0;
-    const char* wbase = nullptr;
+    gl_weight_table wt;                // packed weights
     bool has_sd = false;
     std::unordered_map<std::string, int> emb_off;
     int emb_total = 0;
     std::vector<float> gate_tanh;      // [n_st][4]: fuser attn, fuser dense, rela attn, rela dense
-    // pool
-    struct Buf { void* p; size_t bytes; };
-    std::unordered_map<std::string, Buf> pool;
-    bool pool_changed = false, capturing = false;
+    gl_pool pool;
     int device = -1;
     // conditioning
     bool cond_set = false;
@@ -169,8 +158,7 @@ struct gl_engine {
     // spatial handles (grounding = 4): output channels of the grounding downsampler the GLIGEN first conv also reads (gl_set_extra_channels)
     int ground_extra = 0;
     int extra_bs = 0;
-    // graphs
-    std::map<GraphKey, hipGraphExec_t> graphs;
+    gl_graph_cache<GraphKey> cache;
     float fuser_scale_cur = -1e30f;
     std::vector<float> gate_host;      // the [n_st][4] array last computed
     float* gate_pin[2] = {nullptr, nullptr};           // pinned double buffer the async upload reads from
@@ -180,61 +168,21 @@ struct gl_engine {
     int gate_pin_next = 0;
     int launches = 0;
     int rel_slots = 0;                 // rows per sample of the relation chain (gl_set_conditioning: max nvalid over samples and levels, rounded up to 8)
-    int opt_epoch = 0;                 // gl_set_option generation the captured graphs were built under
-    int ovr_epoch = 0;                 // ... and the generation of this handle's own overrides
     gl_opt_overrides ovr;              // per-handle option overrides (gl_set_handle_option)
     std::string err;
-    hipStream_t cap_stream = nullptr;  // graphs are captured on an engine-owned stream (the caller's may be the legacy
-                                       // default stream, which cannot be captured) and launched on the caller's
 
     // ------------------------------------------------------------------ helpers
-    const WInfo* wi(const std::string& n) const {
-        auto it = tab.find(n);
-        return it == tab.end() ? nullptr : &it->second;
-    }
-    const void* W(const std::string& n) const {
-        auto it = tab.find(n);
-        if (it == tab.end() || wbase == nullptr) return nullptr;
-        return wbase + it->second.off;
-    }
-    const float* Wf(const std::string& n) const { return reinterpret_cast<const float*>(W(n)); }
-
-    void* buf(const std::string& tag, size_t bytes) {
-        auto it = pool.find(tag);
-        if (it != pool.end() && it->second.bytes >= bytes) return it->second.p;
-        if (capturing) { err = "pool allocation during graph capture: " + tag; return nullptr; }
-        if (it != pool.end()) { (void)hipFree(it->second.p); pool.erase(it); }
-        void* p = nullptr;
-        const size_t rounded = (bytes + 255) / 256 * 256;
-        if (hipMalloc(&p, rounded) != hipSuccess) { err = "hipMalloc failed for " + tag; return nullptr; }
-        pool[tag] = Buf{p, rounded};
-        pool_changed = true;
-        return p;
-    }
+    const WInfo* wi(const std::string& n) const { return wt.find(n); }
+    const void* W(const std::string& n) const { return wt.ptr<void>(n); }
+    const float* Wf(const std::string& n) const { return wt.ptr<float>(n); }
+    void* buf(const std::string& tag, size_t bytes) { return pool.get(tag, bytes, &err); }
     half_t* h16(const std::string& tag, size_t n) { return reinterpret_cast<half_t*>(buf(tag, n * 2)); }
     float* f32(const std::string& tag, size_t n) { return reinterpret_cast<float*>(buf(tag, n * 4)); }
-
-    void drop_graphs() {
-        for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
-        graphs.clear();
-    }
 };
 
 namespace {
 
-void add_w(gl_engine* e, const std::string& name, int dtype, std::initializer_list<int64_t> shape) {
-    WInfo w{};
-    w.dtype = dtype;
-    w.ndim = (int)shape.size();
-    int64_t n = 1;
-    int i = 0;
-    for (int64_t s : shape) { w.shape[i++] = s; n *= s; }
-    w.bytes = n * (dtype == 0 ? 2 : 4);
-    w.off = e->total_bytes;
-    e->total_bytes += (w.bytes + ALIGN - 1) / ALIGN * ALIGN;
-    e->tab[name] = w;
-    e->names.push_back(name);
-}
+void add_w(gl_engine* e, const std::string& name, int dtype, std::initializer_list<int64_t> shape) { e->wt.add(name, dtype, shape); }
 // a matrix [n, k]: with cfg.split_weights stored as rows [Whi | Wlo] (k columns each)
 void add_mat(gl_engine* e, const std::string& name, int64_t n, int64_t k) {
     add_w(e, name, 0, {n, e->cfg.split_weights ? 2 * k : k});
@@ -440,16 +388,6 @@ inline int vt_ld(int Nk) {
 }
 // the per-resolution conditioning buffers (cond.rects.* / nvalid.* / poison.*) are named by rows x columns: 64x96, 96x64 and 64x64 are three levels
 inline std::string level_tag(int h, int w) { return std::to_string(h) + "x" + std::to_string(w); }
-
-#define CK(expr)                                     \
-    do {                                             \
-        const int rc__ = (expr);                     \
-        if (rc__ != 0) return rc__;                  \
-    } while (0)
-#define CKP(ptr)                                     \
-    do {                                             \
-        if ((ptr) == nullptr) return GL_ERR_BAD_ARG; \
-    } while (0)
 
 // the launch sequence of one forward / of the conditioning hoists
 struct Run {
@@ -1156,9 +1094,8 @@ extern "C" int gl_create(const gl_unet_config* cfg, gl_engine** out) {
 
 extern "C" int gl_destroy(gl_engine* e) {
     if (!e) return GL_ERR_BAD_ARG;
-    e->drop_graphs();
-    for (auto& kv : e->pool) (void)hipFree(kv.second.p);
-    if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
+    e->cache.release();
+    e->pool.release();
     for (int k = 0; k < 2; ++k) {
         if (e->gate_pin_ev[k]) { (void)hipEventSynchronize(e->gate_pin_ev[k]); (void)hipEventDestroy(e->gate_pin_ev[k]); }
         if (e->gate_pin[k]) (void)hipHostFree(e->gate_pin[k]);
@@ -1167,34 +1104,24 @@ extern "C" int gl_destroy(gl_engine* e) {
     return 0;
 }
 
-extern "C" int gl_num_weights(const gl_engine* e) { return e ? (int)e->names.size() : GL_ERR_BAD_ARG; }
-extern "C" int64_t gl_weights_bytes(const gl_engine* e) { return e ? e->total_bytes : -1; }
-extern "C" int gl_weight_at(const gl_engine* e, int32_t i, gl_weight_info* info) {
-    if (!e || !info || i < 0 || i >= (int)e->names.size()) return GL_ERR_BAD_ARG;
-    const std::string& n = e->names[i];
-    if (n.size() >= sizeof(info->name)) return GL_ERR_BAD_ARG;
-    const WInfo& w = e->tab.at(n);
-    memset(info, 0, sizeof(*info));
-    memcpy(info->name, n.c_str(), n.size());
-    info->offset = w.off; info->nbytes = w.bytes; info->dtype = w.dtype; info->ndim = w.ndim;
-    for (int k = 0; k < 4; ++k) info->shape[k] = w.shape[k];
-    return 0;
-}
+extern "C" int gl_num_weights(const gl_engine* e) { return e ? (int)e->wt.names.size() : GL_ERR_BAD_ARG; }
+extern "C" int64_t gl_weights_bytes(const gl_engine* e) { return e ? e->wt.total : -1; }
+extern "C" int gl_weight_at(const gl_engine* e, int32_t i, gl_weight_info* info) { return e ? e->wt.info_at(i, info) : GL_ERR_BAD_ARG; }
 
 extern "C" int gl_load_weights(gl_engine* e, const void* packed, int64_t bytes, int32_t has_sd_conv, void* stream) {
-    if (!e || !packed || bytes < e->total_bytes) return GL_ERR_BAD_ARG;
+    if (!e || !packed || bytes < e->wt.total) return GL_ERR_BAD_ARG;
     if (reinterpret_cast<uintptr_t>(packed) % 16) return GL_ERR_BAD_ARG;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return GL_ERR_BAD_ARG;
     e->device = dev;
     CK(gl_init());
-    e->wbase = reinterpret_cast<const char*>(packed);
+    e->wt.wbase = reinterpret_cast<const char*>(packed);
     if (has_sd_conv && e->cfg.inpaint_mode) {
         e->err = "gl_load_weights: an inpaint_mode handle has no sd_first_conv slots (its first conv is not restorable)";
         return GL_ERR_BAD_ARG;
     }
     e->has_sd = has_sd_conv != 0;
-    e->drop_graphs();
+    e->cache.drop();
     // the scalar gates tanh(alpha) live in the packed buffer; fetch them once (tiny, synchronous)
     const size_t n = e->st_layers.size();
     e->gate_tanh.assign(n * 4, 0.0f);
@@ -1342,7 +1269,7 @@ int strict_hoists(gl_engine* e, hipStream_t st) {
 namespace {
 int set_conditioning(gl_engine* e, const float* context, const float* relations, const GroundIn& in, int32_t Bn, int32_t Lc, int32_t R, int32_t h,
                      int32_t w, void* stream) {
-    if (!e || !e->wbase || !context || Bn <= 0 || Lc <= 0 || h <= 0 || w <= 0) return GL_ERR_BAD_ARG;
+    if (!e || !e->wt.wbase || !context || Bn <= 0 || Lc <= 0 || h <= 0 || w <= 0) return GL_ERR_BAD_ARG;
     for (const KeptIn& k : kept_inputs(e->cfg, Bn)) if (in.*(k.field) == nullptr) return GL_ERR_BAD_ARG;      // every tensor the family reads
     const bool rel = e->cfg.no_relation == 0;
     if (rel && (!relations || R <= 0)) return GL_ERR_BAD_ARG;
@@ -1353,9 +1280,9 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
     const int mo = cfg.max_objs, ng = n_ground(cfg), ctx = cfg.context_dim, H = cfg.num_heads;
     const bool ti = cfg.grounding == 1;
     const int nch = posnet_chains(cfg);
-    if (Bn != e->Bn || Lc != e->Lc || R != e->R || h != e->lat_h || w != e->lat_w) e->drop_graphs();     // shapes are part of the graph keys anyway
+    if (Bn != e->Bn || Lc != e->Lc || R != e->R || h != e->lat_h || w != e->lat_w) e->cache.drop();     // shapes are part of the graph keys anyway
     if (h != e->lat_h || w != e->lat_w) e->extra_set = false;       // the inpainting extra was sized for the previous latent shape
-    e->pool_changed = false;
+    e->pool.changed = false;
     e->Bn = Bn; e->Lc = Lc; e->R = R; e->lat_h = h; e->lat_w = w;
     Run r{e, st, e->buf("splitk.ws", GL_WS_BYTES)};
     CKP(r.ws);
@@ -1479,7 +1406,7 @@ int set_conditioning(gl_engine* e, const float* context, const float* relations,
         }
         e->rel_slots = slots;          // part of the graph key: a rollout alternating between <= 8 and 9..16 boxes keeps both sets of graphs
     }
-    if (e->pool_changed) e->drop_graphs();
+    if (e->pool.changed) e->cache.drop();
     e->cond_set = true;
     return 0;
 }
@@ -1554,11 +1481,11 @@ static int set_extra(gl_engine* e, const std::string& entry, const float* extra,
     if (!e->cond_set) { e->err = entry + ": no conditioning call has fixed the latent shape yet"; return GL_ERR_BAD_ARG; }
     if (!extra || Bs < 1 || Bs > e->Bn) { e->err = entry + ": extra must be a device pointer to Bs = 1 or Bn / reps samples"; return GL_ERR_BAD_ARG; }
     const size_t n = (size_t)Bs * extra_channels(e->cfg, e->ground_extra) * e->lat_h * e->lat_w;
-    e->pool_changed = false;
+    e->pool.changed = false;
     float* dst = e->f32("in.extra", n);
     CKP(dst);
     // the captured graphs hold this buffer's address and the broadcast flag of the pack launch: a moved buffer or another Bs makes them stale
-    if (e->pool_changed || (e->extra_set && Bs != e->extra_bs)) { e->drop_graphs(); e->pool_changed = false; }
+    if (e->pool.changed || (e->extra_set && Bs != e->extra_bs)) { e->cache.drop(); e->pool.changed = false; }
     if (hipMemcpyAsync(dst, extra, n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return GL_ERR_BAD_ARG;
     e->extra_bs = Bs;
     e->extra_set = true;
@@ -1582,7 +1509,7 @@ extern "C" int gl_set_extra_channels(gl_engine* e, int32_t channels) {
         return GL_ERR_UNSUPPORTED;
     }
     if (channels != e->ground_extra) {       // the pack launch of the captured graphs and the extra buffer's size follow the count
-        e->drop_graphs();
+        e->cache.drop();
         e->extra_set = false;
     }
     e->ground_extra = channels;
@@ -1624,7 +1551,7 @@ extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev,
     const size_t hw = (size_t)e->lat_h * e->lat_w;
     const size_t nx = (size_t)(Bn / reps) * cfg.in_channels * hw;
     const size_t ne = (size_t)Bn * cfg.out_channels * hw;
-    e->pool_changed = false;
+    e->pool.changed = false;
     float* x_lat = e->f32("in.xlat", nx);
     float* t_buf = e->f32("in.t", Bn);
     float* eps_i = e->f32("out.eps", ne);
@@ -1641,45 +1568,14 @@ extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev,
         // first strict forward since the conditioning was set (or since key 51 changed): the split-fp16 hoists, on the caller's stream, before any
         // capture; their buffers are new to the pool the first time, which makes the captured graphs stale
         CK(strict_hoists(e, st));
-        if (e->pool_changed) { e->drop_graphs(); e->pool_changed = false; }
+        if (e->pool.changed) { e->cache.drop(); e->pool.changed = false; }
     }
     const bool fuser_on = fuser_scale != 0.0f || g_force_fuser != 0;
-    if (e->opt_epoch != g_gl_option_epoch || e->ovr_epoch != e->ovr.epoch) {       // a tuning knob changed: the captured launch sequences may be stale
-        e->drop_graphs();
-        e->opt_epoch = g_gl_option_epoch;
-        e->ovr_epoch = e->ovr.epoch;
-    }
+    e->cache.sync_epochs(e->ovr);
     const bool uniform_t = t_dev == nullptr;
     const GraphKey key{Bn, e->lat_h, e->lat_w, e->R, e->Lc, fuser_on, sd_conv != 0, reps, uniform_t, e->rel_slots, cfg.no_relation != 0};
-    auto it = e->graphs.find(key);
-    if (use_graph && it == e->graphs.end()) {
-        // warm-up run allocates every pooled buffer, then the same launch sequence is captured
-        CK(launch_forward(e, reps, fuser_on, sd_conv != 0, uniform_t, st, &e->launches));
-        if (hipStreamSynchronize(st) != hipSuccess) return GL_ERR_BAD_ARG;
-        if (e->pool_changed) { e->drop_graphs(); e->pool_changed = false; }
-        hipGraph_t graph = nullptr;
-        if (e->cap_stream == nullptr && hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking) != hipSuccess) return GL_ERR_UNSUPPORTED;
-        if (hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return GL_ERR_UNSUPPORTED;
-        e->capturing = true;
-        const int rc = launch_forward(e, reps, fuser_on, sd_conv != 0, uniform_t, e->cap_stream, nullptr);
-        e->capturing = false;
-        const hipError_t ec = hipStreamEndCapture(e->cap_stream, &graph);
-        if (rc != 0 || ec != hipSuccess || graph == nullptr) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc != 0 ? rc : GL_ERR_UNSUPPORTED;
-        }
-        hipGraphExec_t exec = nullptr;
-        const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ei != hipSuccess) return GL_ERR_UNSUPPORTED;
-        it = e->graphs.emplace(key, exec).first;
-    }
-    if (use_graph) {
-        if (hipGraphLaunch(it->second, st) != hipSuccess) return GL_ERR_UNSUPPORTED;
-    } else {
-        CK(launch_forward(e, reps, fuser_on, sd_conv != 0, uniform_t, st, &e->launches));
-        if (e->pool_changed) { e->drop_graphs(); e->pool_changed = false; }
-    }
+    CK(e->cache.run(key, use_graph != 0, st, e->pool,
+                    [&](hipStream_t s, int* nl) { return launch_forward(e, reps, fuser_on, sd_conv != 0, uniform_t, s, nl); }, &e->launches));
     if (eps != eps_i && hipMemcpyAsync(eps, eps_i, ne * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return GL_ERR_BAD_ARG;
     return 0;
 }
@@ -1711,12 +1607,7 @@ extern "C" int gl_plms_step(gl_engine* e, const gl_plms_step_args* a, void* stre
 }
 
 extern "C" int gl_set_handle_option(gl_engine* e, int key, int value) {
-    gl_opts probe{};
-    if (!e || key < 0 || key >= GL_OPT_MAX || !gl_opts_put(probe, key, value)) return GL_ERR_BAD_ARG;
-    e->ovr.mask |= (uint64_t)1 << key;
-    e->ovr.v[key] = value;
-    ++e->ovr.epoch;
-    return 0;
+    return e ? gl_handle_set_option(e->ovr, key, value) : GL_ERR_BAD_ARG;
 }
 
 extern "C" int gl_clear_handle_options(gl_engine* e) {
@@ -1737,10 +1628,7 @@ extern "C" int gl_last_error(const gl_engine* e, char* dst, int32_t bytes) {
 }
 
 extern "C" int64_t gl_pool_bytes(const gl_engine* e) {
-    if (!e) return -1;
-    int64_t s = 0;
-    for (auto& kv : e->pool) s += (int64_t)kv.second.bytes;
-    return s;
+    return e ? e->pool.bytes() : -1;
 }
 extern "C" int gl_num_launches(const gl_engine* e) { return e ? e->launches : GL_ERR_BAD_ARG; }
 extern "C" int gl_sizeof_unet_config(void) { return (int)sizeof(gl_unet_config); }

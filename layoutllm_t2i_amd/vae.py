@@ -31,7 +31,7 @@ import torch
 from . import ops
 from ._lib import EPI_BIAS, EPI_RES, init_device
 from .arch import VAEConfig, vae_decoder_param_shapes, vae_encoder_param_shapes
-from .weights import CIN_PAD, _h, _t, pack_conv3x3, pack_conv_upfold
+from .weights import CIN_PAD, _h, _t, copy_packed, flat_views, pack_conv3x3, pack_conv_upfold
 
 F16, F32 = torch.float16, torch.float32
 _FP32_1X1 = ("post_quant_conv", "quant_conv")      # 1x1 convs on the 4 / 8-channel latent side: kept in fp32
@@ -135,17 +135,9 @@ class _VAEStage:
         """Moves the packed tensors into the C engine's flat layout (gl_vae_weight_at) and rebinds ``W`` to views of it."""
         from . import _lib
         self.handle = _lib.create_vae(self.cfg, encoder=self._encoder_stage, fold_up=getattr(self, "fold_up", None))
-        table, total = _lib.vae_weight_table(self.handle)
-        flat = torch.zeros(total, dtype=torch.uint8, device=self.device)
-        views = {}
-        for name, off, nbytes, dtype, shape in table:
-            td = F16 if dtype == 0 else F32
-            dst = flat[off:off + nbytes].view(td).view(shape)
-            src = self.W[name]
-            if tuple(src.shape) != tuple(shape) or src.dtype != td:
-                raise ValueError(f"{name}: packed {tuple(src.shape)} {src.dtype} != engine table {shape} {td}")
-            dst.copy_(src)
-            views[name] = dst
+        flat, views = flat_views(*_lib.vae_weight_table(self.handle), self.device)
+        for name, dst in views.items():
+            copy_packed(name, dst, self.W[name])
         extra = set(self.W) - set(views)
         if extra:
             raise KeyError(f"packer produced tensors the VAE engine does not know: {sorted(extra)[:3]}")

@@ -126,6 +126,22 @@ def geglu_interleave(t: torch.Tensor) -> torch.Tensor:
     return torch.cat([x, g], dim=1).reshape(t.shape)
 
 
+def flat_views(table, total, device, flat=None):
+    """An engine handle's weight table (_lib.weight_table / vae_weight_table) -> the flat byte buffer of ``total`` bytes (zeros, unless an
+    already filled ``flat`` is given) and its {name: typed view}, in table order."""
+    if flat is None:
+        flat = torch.zeros(total, dtype=torch.uint8, device=device)
+    return flat, {name: flat[off:off + nbytes].view(torch.float16 if dtype == 0 else torch.float32).view(shape)
+                  for name, off, nbytes, dtype, shape in table}
+
+
+def copy_packed(name: str, dst: torch.Tensor, src: torch.Tensor) -> None:
+    """One packed tensor into its view of the flat buffer: the packer and the engine table must agree on shape and dtype."""
+    if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
+        raise ValueError(f"{name}: packed {tuple(src.shape)} {src.dtype} != engine table {tuple(dst.shape)} {dst.dtype}")
+    dst.copy_(src)
+
+
 class PackedWeights:
     """``w[name]`` packed tensors + python scalars ``s[name]``.  After ``to_flat()`` every tensor is a VIEW into one
     flat byte buffer ``flat`` whose layout is defined by the C engine's weight table (gl_weight_at, include/gligen_hip.h):
@@ -147,22 +163,11 @@ class PackedWeights:
     def to_flat(self) -> "PackedWeights":
         """Moves every packed tensor into the flat buffer at the offsets the C engine dictates and rebinds ``w`` to views."""
         from . import _lib
-        handle = _lib.create_engine(self.cfg, self.fold_up)
-        try:
-            table, total = _lib.weight_table(handle)
-        finally:
-            _lib.check(_lib.lib().gl_destroy(handle), "gl_destroy")
-        flat = torch.zeros(total, dtype=torch.uint8, device=self.device)
+        flat, views = flat_views(*_lib.engine_table(self.cfg, self.fold_up), self.device)
         self.has_sd_conv = "sd_first_conv.w" in self.w
-        views: Dict[str, torch.Tensor] = {}
-        for name, off, nbytes, dtype, shape in table:
-            td = torch.float16 if dtype == 0 else torch.float32
-            dst = flat[off:off + nbytes].view(td).view(shape)
+        for name, dst in views.items():
             if name in self.w:
-                src = self.w[name]
-                if tuple(src.shape) != tuple(shape) or src.dtype != td:
-                    raise ValueError(f"{name}: packed {tuple(src.shape)} {src.dtype} != engine table {shape} {td}")
-                dst.copy_(src)
+                copy_packed(name, dst, self.w[name])
             elif name in self.s:
                 dst.fill_(float(self.s[name]))
                 self.s[name] = float(dst.item())       # the gates are fp32 on the device: keep the host copy identical
@@ -170,7 +175,6 @@ class PackedWeights:
                 pass                                   # no SD conv given: slot stays zero, gl_load_weights(has_sd_conv=0)
             else:
                 raise KeyError(f"engine weight table wants {name}, which the packer did not produce")
-            views[name] = dst
         extra = set(self.w) - set(views)
         if extra:
             raise KeyError(f"packer produced tensors the engine does not know: {sorted(extra)[:3]}")
@@ -184,19 +188,11 @@ class PackedWeights:
         from . import _lib
         P = PackedWeights(cfg, build_plan(cfg), device)
         P.fold_up = fold_up = _lib.resolve_fold_up(fold_up, fold_up_rule(cfg))
-        handle = _lib.create_engine(cfg, fold_up)
-        try:
-            table, total = _lib.weight_table(handle)
-        finally:
-            _lib.check(_lib.lib().gl_destroy(handle), "gl_destroy")
+        table, total = _lib.engine_table(cfg, fold_up)
         if flat.numel() != total:
             raise ValueError(f"flat buffer has {flat.numel()} bytes, the engine table needs {total}")
-        for name, off, nbytes, dtype, shape in table:
-            td = torch.float16 if dtype == 0 else torch.float32
-            v = flat[off:off + nbytes].view(td).view(shape)
-            if name.endswith((".tanh_attn", ".tanh_dense")):
-                P.s[name] = float(v.item())
-            P.w[name] = v
+        _, P.w = flat_views(table, total, device, flat)
+        P.s = {name: float(v.item()) for name, v in P.w.items() if name.endswith((".tanh_attn", ".tanh_dense"))}
         off = 0
         for l in P.plan.all_layers():
             if l.kind == "res":

@@ -121,6 +121,33 @@ def test_cpp_engine_graph_replay_eager_and_reconditioning():
         eng.forward(inp3["x"].to(DEV), 1.0)                     # latent does not match the conditioning batch / size
 
 
+def test_graphs_survive_a_growing_pool():
+    """small key first: 8x8 / B = 1 captured and replayed, then 16x16 / B = 2 grows pooled buffers (the earlier graph holds freed
+    addresses and must be dropped), then 8x8 again -- each forward equal to a fresh engine that never captures"""
+    dev = torch.device(DEV)
+    P = pack_state_dict(recipe.state_dict(TINY, 0), TINY, dev, recipe.sd_first_conv(TINY, 0))
+    eng = UNetEngine(P)
+    small = {k: T(v) for k, v in recipe.synth_inputs(TINY, 1, 8, n_boxes=3, n_rel=2, seed=12).items()}
+    big = {k: T(v) for k, v in recipe.synth_inputs(TINY, 2, 16, n_boxes=4, n_rel=3, seed=13).items()}
+
+    def forward(e, inp, hw):
+        e.set_conditioning(inp["context"], inp["relations"], inp["boxes"], inp["masks"], inp["positive_embeddings"], hw)
+        return e.forward(inp["x"].to(DEV), 481.0, 1.0, False, 1).clone()
+
+    def eager(inp, hw):
+        fresh = UNetEngine(P)
+        fresh.use_graphs = False
+        return forward(fresh, inp, hw)
+
+    ref_small, ref_big = eager(small, 8), eager(big, 16)
+    assert torch.isfinite(ref_small).all() and torch.isfinite(ref_big).all()
+    assert torch.equal(forward(eng, small, 8), ref_small)          # warm-up, capture, replay
+    assert torch.equal(forward(eng, small, 8), ref_small)          # replay
+    pool = eng.pool_bytes()
+    assert torch.equal(forward(eng, big, 16), ref_big) and eng.pool_bytes() > pool
+    assert torch.equal(forward(eng, small, 8), ref_small)
+
+
 def test_cpp_engine_equals_python_launch_sequence_full_model():
     """the real 1.26 B-parameter config at 64x64, 2B = 4 (split-K, K-split, 64-row tiles all in play)"""
     cfg = UNetConfig()

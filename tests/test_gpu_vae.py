@@ -103,6 +103,27 @@ def test_c_engine_equals_python_op_sequence_bitwise(cfgname, B, side):
     assert _lib.lib().gl_vae_num_launches(dec.handle) > 20 and _lib.lib().gl_vae_pool_bytes(dec.handle) > 0
 
 
+def test_graphs_survive_a_growing_pool():
+    """small key first: (B = 1, side 8) captured and replayed, then (B = 2, side 16) grows pooled buffers (the earlier graph holds freed
+    addresses and must be dropped), then the small key again -- every result equal to the op-by-op sequence; the encoder likewise"""
+    cfg = VAE_TINY
+    sd = {**recipe.vae_state_dict(cfg, 0), **recipe.vae_encoder_state_dict(cfg, 0)}
+    dec = VAEDecoder(sd, cfg, DEV)
+    zs = {(B, side): T(recipe.normal(f"vae.zg.{B}.{side}", (B, cfg.z_channels, side, side), 3)) * np.float32(0.18215) for B, side in ((1, 8), (2, 16))}
+    refs = {k: dec.decode_oplevel(z).clone() for k, z in zs.items()}
+    assert all(torch.isfinite(r).all() for r in refs.values())
+    for k in ((1, 8), (1, 8), (2, 16), (1, 8)):
+        assert torch.equal(dec.decode(zs[k]), refs[k]), k
+    enc = dec.encoder
+    f = 2 ** (len(cfg.ch_mult) - 1)
+    xs = {(B, side): (T(np.clip(recipe.normal(f"vae.xg.{B}.{side}", (B, 3, side, side), 3) * np.float32(0.5), -1, 1)),
+                      T(recipe.normal(f"vae.ng.{B}.{side}", (B, cfg.embed_dim, side // f, side // f), 3))) for B, side in ((1, 32), (2, 64))}
+    erefs = {k: enc.encode_oplevel(x, n).clone() for k, (x, n) in xs.items()}
+    assert all(torch.isfinite(r).all() for r in erefs.values())
+    for k in ((1, 32), (1, 32), (2, 64), (1, 32)):
+        assert torch.equal(enc.encode(*xs[k]), erefs[k]), k
+
+
 def test_vae_set_option_is_per_decoder():
     """VAEDecoder.set_option (gl_vae_set_option; ADVICE r3: the method used to raise NameError): knobs set on ONE decoder (13 = 0:
     no intra-block K-split conv variants, 30 = 0: no 8-wave kernel -- other fp32 summation orders) leave its result within
