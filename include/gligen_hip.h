@@ -716,6 +716,31 @@ int gl_sp_bicubic(const float* in, int32_t B, int32_t Ct, int32_t C, int32_t Hin
 int gl_sp_conv4x4s2(const float* in, const float* w, const float* bias, int32_t B, int32_t Ci, int32_t Co, int32_t Hin, int32_t Win,
                     int32_t silu, float* out, void* stream);
 
+/*
+ * Semantic-map grounding (GLIGEN's checkpoint_generation_sem.pth), additive to ABI 15.  On the engine a sem model is a spatial handle
+ * (grounding = 4, gl_set_conditioning_tokens, gl_set_extra_channels(8), gl_set_grounding_extra); these three entries are its front end, run
+ * once per image.  The reference convolves a fp32 one-hot tensor [B, classes, 512, 512]; a convolution over a one-hot input is a table
+ * lookup, so the input here is the uint8 class map and the one-hot tensor is never built.
+ *   gl_sem_gather_conv  : map uint8 [B, Hs, Ws] (class ids) -> nearest resize to R x R (the expression of gl_sp_stem_patchify, per axis) ->
+ *                         Conv2d(classes, Co, K, stride, pad) of its one-hot (+ SiLU when silu != 0) -> out fp32 [B, Co, Ro, Ro],
+ *                         Ro = (R + 2 pad - K) / stride + 1:  out[b, co, y, x] = bias[co] + sum over taps inside the R x R image of
+ *                         table[class][ky * K + kx][co].  table fp32 [classes][K * K][CoP], CoP = Co rounded up to a multiple of 4, the pad
+ *                         columns zero, 16-byte aligned (the conv weight [Co, classes, K, K] permuted by the host).  A class id >= classes is
+ *                         clamped to classes - 1, so no read leaves the table (the host refuses such a map).  GL_ERR_BAD_ARG: a null pointer,
+ *                         classes outside 2..256, K outside 1..4, stride not 1 or 2, pad >= K, Co outside 1..16, an odd R with stride 2, a
+ *                         misaligned table, more than 2^31 blocks.
+ *   gl_sem_conv4x4s2    : Conv2d(Ci, Co, 4, 2, 1) on fp32 NCHW, no activation (the downsampler's second conv, 16 -> 8), Ci, Co <= 64, Hin, Win
+ *                         even; gl_sp_conv4x4s2 keeps its limit of 8 channels.
+ *   gl_sem_onehot_index : x fp32 [B, C, H, W] -> out uint8 [B, H, W] = argmax over C (the first maximum), and bad int32 [B] = the number of
+ *                         pixels of each sample that are not exactly one-hot (one channel == 1.0, every other == 0.0); bad is zeroed by the
+ *                         entry, on the stream.  2 <= C <= 256, B <= 65535.
+ */
+int gl_sem_gather_conv(const uint8_t* map, int32_t B, int32_t Hs, int32_t Ws, int32_t R, const float* table, const float* bias,
+                       int32_t classes, int32_t K, int32_t stride, int32_t pad, int32_t Co, int32_t silu, float* out, void* stream);
+int gl_sem_conv4x4s2(const float* in, const float* w, const float* bias, int32_t B, int32_t Ci, int32_t Co, int32_t Hin, int32_t Win,
+                     float* out, void* stream);
+int gl_sem_onehot_index(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, uint8_t* out, int32_t* bad, void* stream);
+
 /* ---- image preprocessing of the reward stage (models/policy.py:108-111: self.processor(images=...), the HuggingFace CLIP
  * feature extractor on PIL images; transformers 4.19.2 image_utils + Pillow) -- on the GPU, so rollout images stay in HBM
  * between the VAE decoder and the CLIP vision tower.

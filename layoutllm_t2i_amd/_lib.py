@@ -207,6 +207,9 @@ PROTOTYPES = {
     "gl_sp_assemble": (i32, [fp, fp, fp, fp, i32, i32, i32, vp, vp]),
     "gl_sp_bicubic": (i32, [fp, i32, i32, i32, i32, i32, vp, fp, vp, fp, i32, i32, fp, vp]),
     "gl_sp_conv4x4s2": (i32, [fp, fp, fp, i32, i32, i32, i32, i32, i32, fp, vp]),
+    "gl_sem_gather_conv": (i32, [vp, i32, i32, i32, i32, fp, fp, i32, i32, i32, i32, i32, i32, fp, vp]),
+    "gl_sem_conv4x4s2": (i32, [fp, fp, fp, i32, i32, i32, i32, i32, fp, vp]),
+    "gl_sem_onehot_index": (i32, [fp, i32, i32, i32, i32, vp, vp, vp]),
     "gl_posnet_input_kp": (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, vp, vp]),
     "gl_posnet_input_kp_f32": (i32, [fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, fp, vp]),
     "gl_posnet_input_ti": (i32, [fp, fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp, vp, vp]),

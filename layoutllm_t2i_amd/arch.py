@@ -19,8 +19,8 @@ MAX_PERSONS = 8          # the shipped checkpoint's max_persons_per_image: 136 g
 
 # The spatial grounding families: tokenizer module -> (its own downsampler module, downsampler kind, input channels, default output channels).
 # {canny,hed,depth,normal}_grounding_net.PositionNet are one ConvNeXt tokenizer; *_grounding_downsampler.py differ in the channels they read and
-# in whether two small convs follow the bicubic resize (hed: none, a hard-coded 64 x 64).  The semantic family (152-channel one-hot input,
-# nearest resize) is not among them.
+# in whether two small convs follow the bicubic resize (hed: none, a hard-coded 64 x 64).  The semantic family (sem_grounding_net: a one-hot
+# class-map input, nearest resize; from_dict(allow_semantic=True), semantic.py) is the same tokenizer behind an in_conv and is NOT in this table.
 SPATIAL_FAMILIES = {
     "canny_grounding_net": ("canny_grounding_downsampler", "conv", 1, 8),
     "hed_grounding_net": ("hed_grounding_downsampler", "bicubic", 1, 1),
@@ -30,6 +30,10 @@ SPATIAL_FAMILIES = {
 CONVNEXT_DEPTHS = (3, 3, 9, 3)            # convnext.py: convnext_tiny
 CONVNEXT_DIMS = (96, 192, 384, 768)
 HED_DS_SIZE = 64                          # hed_grounding_downsampler.py:19 resizes to (64, 64) whatever the latent
+SEM_TOKENIZER = "sem_grounding_net.PositionNet"                                # the semantic-map family (checkpoint_generation_sem.pth)
+SEM_DOWNSAMPLER = "sem_grounding_downsampler.GroundingDownsampler"
+SEM_CLASSES = 152                         # configs/ade_sem.yaml: in_dim of both modules (150 ADE classes + 2)
+SEM_DS_HIDDEN = 16                        # sem_grounding_downsampler.py:16: Conv2d(in_dim, 16, 4, 2, 1)
 
 
 @dataclass(frozen=True)
@@ -70,6 +74,9 @@ class UNetConfig:
     # ds_out channels are concatenated to the latent in front of the first conv (spatial.SpatialDownsampler).  ds_kind: "" = none, "conv" =
     # bicubic to ds_resize_input then two 4x4 stride-2 convs (canny, depth, normal), "bicubic" = bicubic to 64 x 64 alone (hed); ds_in = the
     # channels of the map it reads (1, or 3 for normal).  The defaults leave every other config as it was.
+    # ds_kind "sem" (the semantic-map family, also grounding = "spatial"): ds_in = the number of classes (the in_dim of the tokenizer's in_conv
+    # and of the downsampler's first conv); nearest resize of the class map to ds_resize_input, Conv2d(ds_in, 16, 4, 2, 1), SiLU,
+    # Conv2d(16, ds_out, 4, 2, 1) (semantic.SemDownsampler); the tokenizer is the ConvNeXt one behind in_conv (semantic.SemTokenizer).
     ds_kind: str = ""
     ds_in: int = 1
     ds_out: int = 0
@@ -93,6 +100,11 @@ class UNetConfig:
         return self.max_objs * (2 if self.grounding == "text_image" else 1)
 
     @property
+    def sem_classes(self) -> int:
+        """classes of a semantic-map model's class map (ds_in there), 0 on every other config"""
+        return self.ds_in if self.ds_kind == "sem" else 0
+
+    @property
     def ds_latent(self) -> int:
         """side of the downsampler's output, which the latent has to match: ds_resize_input / 4, or hed's hard-coded 64"""
         return HED_DS_SIZE if self.ds_kind == "bicubic" else self.ds_resize_input // 4
@@ -114,7 +126,8 @@ class UNetConfig:
         return self.fourier_freqs * 2 * (2 if self.grounding == "keypoint" else 4)
 
     @staticmethod
-    def from_dict(params: dict, allow_inpaint: bool = False, allow_keypoint: bool = False, allow_spatial: bool = False) -> "UNetConfig":
+    def from_dict(params: dict, allow_inpaint: bool = False, allow_keypoint: bool = False, allow_spatial: bool = False,
+                  allow_semantic: bool = False) -> "UNetConfig":
         """Accepts the ``config['model']['params']`` dict of a GLIGEN checkpoint.
 
         ``allow_inpaint``: an ``inpaint_mode`` checkpoint (9-channel first conv) shares every parameter name with the layout-to-image UNet but
@@ -127,7 +140,12 @@ class UNetConfig:
         ``allow_spatial``: the same for the canny / hed / depth / normal checkpoints (``*_grounding_net.PositionNet`` with their own
         ``*_grounding_downsampler.GroundingDownsampler``): they are fed a map and ``grounding_extra_input``.  Every other downsampler config
         (no flag, another target, the sem family, with inpaint_mode, a tokenizer of another family) raises NotImplementedError naming
-        ``grounding_downsampler``."""
+        ``grounding_downsampler``.
+
+        ``allow_semantic``: the same for the semantic-map checkpoint (``sem_grounding_net.PositionNet`` with
+        ``sem_grounding_downsampler.GroundingDownsampler``): it is fed a class map under the key ``sem``.  It reads as ``grounding ==
+        "spatial"`` with ``ds_kind == "sem"`` and ``ds_in`` = the classes (both modules' ``in_dim``, which must agree, 2 .. 256); without the
+        flag, or with the downsampler of another family, it raises NotImplementedError naming ``grounding_downsampler`` as before."""
         gt = (params.get("grounding_tokenizer") or {}).get("params", {})
         target = (params.get("grounding_tokenizer") or {}).get("target")
         if target is None or target.endswith(".text_grounding_net.PositionNet") or target == "text_grounding_net.PositionNet":
@@ -137,6 +155,9 @@ class UNetConfig:
         elif target.endswith("keypoint_grounding_net.PositionNet") and allow_keypoint:
             grounding = "keypoint"
         elif _spatial_family(target) is not None and allow_spatial and params.get("grounding_downsampler") is not None:
+            grounding = "spatial"
+        elif target.endswith(SEM_TOKENIZER) and allow_semantic and str((params.get("grounding_downsampler") or {}).get("target")).endswith(
+                SEM_DOWNSAMPLER):
             grounding = "spatial"
         elif _spatial_family(target) is not None or target.endswith("sem_grounding_net.PositionNet"):
             raise NotImplementedError(f"grounding_tokenizer target {target!r} with grounding_downsampler "
@@ -165,7 +186,20 @@ class UNetConfig:
             if grounding != "spatial":
                 raise NotImplementedError(f"grounding_downsampler {ds_target!r} is not on the text_layout path" +
                                           ("" if allow_spatial else " (the canny / hed / depth / normal families need allow_spatial=True)"))
-            ds_mod, kind, cin, cout = SPATIAL_FAMILIES[_spatial_family(target)]
+            sem = target.endswith(SEM_TOKENIZER)
+            if sem:
+                # both in_dims are the number of classes; a uint8 class map holds up to 256
+                cin, tin = int(dp.get("in_dim", SEM_CLASSES)), int(gt.get("in_dim", SEM_CLASSES))
+                if cin != tin:
+                    raise ValueError(f"sem grounding_tokenizer in_dim = {tin} but grounding_downsampler in_dim = {cin}: both are the number of classes")
+                if not 2 <= cin <= 256:
+                    raise ValueError(f"sem in_dim = {cin}: 2 .. 256 classes (the class map is uint8)")
+                cout = int(dp.get("out_dim", 8))
+                if not 1 <= cout <= 60:
+                    raise ValueError(f"sem grounding_downsampler out_dim = {cout}: 1 .. 60")
+                ds_mod, kind = "sem_grounding_downsampler", "sem"
+            else:
+                ds_mod, kind, cin, cout = SPATIAL_FAMILIES[_spatial_family(target)]
             if not ds_target.endswith(ds_mod + ".GroundingDownsampler"):
                 raise NotImplementedError(f"grounding_downsampler target {ds_target!r} does not go with the tokenizer {target!r}: expected "
                                           f"{ds_mod}.GroundingDownsampler")
@@ -175,9 +209,11 @@ class UNetConfig:
                       sp_resize_input=int(gt.get("resize_input", 448)), relation=False)
             if sp["sp_resize_input"] % 32 or not 32 <= sp["sp_resize_input"] <= 256:
                 raise ValueError(f"grounding_tokenizer resize_input = {sp['sp_resize_input']}: a multiple of 32 up to 256 (at most 64 grounding tokens)")
-            if kind == "conv" and sp["ds_resize_input"] % 4:
+            if kind in ("conv", "sem") and (sp["ds_resize_input"] % 4 or sp["ds_resize_input"] <= 0):
                 raise ValueError(f"grounding_downsampler resize_input = {sp['ds_resize_input']}: a multiple of 4")
             sp["max_objs"] = (sp["sp_resize_input"] // 32) ** 2
+            if sem:
+                sp["pos_in_dim"] = UNetConfig.pos_in_dim      # the tokenizer's in_dim counts classes there (ds_in), it is no embedding width
         if not params.get("use_spatial_transformer", True):
             raise NotImplementedError("use_spatial_transformer=False is not supported")
         kp = {}
@@ -403,6 +439,9 @@ def spatial_tokenizer_params(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
     out: Dict[str, Tuple[int, ...]] = {}
     out[p + ".pos_embedding"] = (1, cfg.n_ground, dims[3])
     out[p + ".null_feature"] = (dims[3],)
+    if cfg.ds_kind == "sem":
+        out[p + ".in_conv.weight"] = (3, cfg.sem_classes, 3, 3)       # sem_grounding_net.py:22: from the one-hot classes to 3 channels
+        out[p + ".in_conv.bias"] = (3,)
     out[bb + ".downsample_layers.0.0.weight"] = (dims[0], 3, 4, 4)
     out[bb + ".downsample_layers.0.0.bias"] = (dims[0],)
     out[bb + ".downsample_layers.0.1.weight"] = (dims[0],)
@@ -448,6 +487,12 @@ def param_shapes(cfg: UNetConfig) -> Dict[str, Tuple[int, ...]]:
         out["downsample_net.layers.0.weight"] = (4, cfg.ds_in, 4, 4)
         out["downsample_net.layers.0.bias"] = (4,)
         out["downsample_net.layers.2.weight"] = (cfg.ds_out, 4, 4, 4)
+        out["downsample_net.layers.2.bias"] = (cfg.ds_out,)
+    if cfg.ds_kind == "sem":
+        # sem_grounding_downsampler.py:15-19: Conv2d(classes, 16, 4, 2, 1), SiLU, Conv2d(16, out_dim, 4, 2, 1)
+        out["downsample_net.layers.0.weight"] = (SEM_DS_HIDDEN, cfg.sem_classes, 4, 4)
+        out["downsample_net.layers.0.bias"] = (SEM_DS_HIDDEN,)
+        out["downsample_net.layers.2.weight"] = (cfg.ds_out, SEM_DS_HIDDEN, 4, 4)
         out["downsample_net.layers.2.bias"] = (cfg.ds_out,)
     for l in plan.all_layers():
         if l.kind == "conv_in":

@@ -31,7 +31,8 @@ needs neither ``phrases`` nor a CLIP model, and ``images`` / ``input_image`` rai
 
 A spatial checkpoint (``checkpoint_generation_canny.pth`` / ``_hed`` / ``_depth`` / ``_normal``) takes its map under the reference's own meta
 key (``canny_image`` / ``hed_image`` / ``depth`` / ``normal``: a path or a ``PIL.Image``); it needs neither ``locations`` nor ``phrases`` nor a
-CLIP model, and ``images`` / ``input_image`` / boxes raise ValueError.
+CLIP model, and ``images`` / ``input_image`` / boxes raise ValueError.  The semantic-map checkpoint (``checkpoint_generation_sem.pth``) takes
+an image of class ids under ``meta["sem"]`` in the same way.
 
 A checkpoint without ``rela_fuse`` tensors (every public GLIGEN checkpoint) runs on the upstream transformer block it was trained with
 (attention_original.py:312-316): no relation phrases are parsed or encoded for it.
@@ -72,7 +73,7 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     spatial = getattr(getattr(all_models[0], "cfg", None), "grounding", "text") == "spatial"
     m = dict(prompt=meta["prompt"], phrases=meta.get("phrases"), locations=meta.get("locations") if spatial else meta["locations"],
              alpha_type=meta.get("alpha_type", [0.3, 0.0, 0.7]), input_image=meta.get("input_image"))
-    for k in interface.SPATIAL_META_KEYS:
+    for k in interface.SPATIAL_META_KEYS + (interface.SEM_META_KEY,):
         if meta.get(k) is not None:
             m[k] = meta[k]
     # image grounding (a *_box_text_image checkpoint, gligen_inference.py:350-352): one reference image or None per box

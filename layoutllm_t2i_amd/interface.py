@@ -151,7 +151,9 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
     # (_run builds the inpainting extra an inpaint_mode model needs, and the points / masks batch of a keypoint model)
     # (... and the map batch of a spatial model: canny / hed / depth / normal, whose ConvNeXt tokenizer and grounding downsampler are built
     # from the checkpoint's own position_net.* / downsample_net.* tensors -- nothing is fetched)
-    cfg = UNetConfig.from_dict(config["model"]["params"], allow_inpaint=True, allow_keypoint=True, allow_spatial=True)
+    # (... and the class-map batch of a semantic-map model, sem_grounding_net / sem_grounding_downsampler: the family is read off the config,
+    # not off the file name)
+    cfg = UNetConfig.from_dict(config["model"]["params"], allow_inpaint=True, allow_keypoint=True, allow_spatial=True, allow_semantic=True)
     import dataclasses
     if cfg.grounding == "spatial" and any(".rela_fuse." in k for k in saved_ckpt["model"]):
         raise NotImplementedError("a spatial checkpoint with *.rela_fuse.* tensors: the relation chain pools image features over grounding "
@@ -463,6 +465,46 @@ def prepare_batch_spatial(meta, batch=1, device=None):
     return {k: v.to(device) for k, v in out.items()} if device is not None else out
 
 
+SEM_META_KEY = "sem"                      # the reference's meta key of a semantic map (gligen_inference.py:322)
+SEM_IMAGE_SIZE = 512
+
+
+def load_sem_map(image) -> torch.Tensor:
+    """gligen_inference.py:322-324 + :330: ``Image.open(path).convert("L")`` (or a ``PIL.Image``), torchvision's centre crop to the shorter
+    side (the rounding of ``load_spatial_map``), ``resize((512, 512), Image.NEAREST)``, pil_to_tensor -> the class ids, uint8 [512, 512]"""
+    from PIL import Image
+    im = image if isinstance(image, Image.Image) else Image.open(image)
+    im = im.convert("L")
+    w, h = im.size
+    crop = min(w, h)
+    top, left = int(round((h - crop) / 2.0)), int(round((w - crop) / 2.0))
+    im = im.crop((left, top, left + crop, top + crop)).resize((SEM_IMAGE_SIZE, SEM_IMAGE_SIZE), Image.NEAREST)
+    return torch.from_numpy(np.array(im, dtype=np.uint8)).contiguous()
+
+
+@torch.no_grad()
+def prepare_batch_sem(meta, batch=1, device=None, classes=152):
+    """gligen_inference.py:318-337 without its one-hot: the semantic map under ``meta["sem"]`` (a path or a ``PIL.Image`` of class ids)
+    repeated ``batch`` times as ``sem`` uint8 [batch, 512, 512], the CLASS MAP the reference's ``scatter_`` one-hot [batch, classes, 512, 512]
+    argmaxes to (the kernels of a semantic-map model read it directly), and ``mask`` [batch, 1] of ones.  A list of ``batch`` maps gives one
+    map per sample.  A pixel value >= ``classes`` raises ValueError (the reference's ``scatter_`` raises there too); the colour visualisation
+    side file of the reference is not written."""
+    src = meta.get(SEM_META_KEY)
+    if src is None:
+        raise ValueError(f"a semantic-map checkpoint needs its class map under the meta key {SEM_META_KEY!r}")
+    if isinstance(src, (list, tuple)):
+        if len(src) != batch:
+            raise ValueError(f"{len(src)} semantic maps for a batch of {batch}")
+        maps = torch.stack([load_sem_map(s) for s in src], 0)
+    else:
+        maps = load_sem_map(src).unsqueeze(0).repeat(batch, 1, 1)
+    hi = int(maps.max())
+    if hi >= classes:
+        raise ValueError(f"the semantic map holds the class id {hi}: the model has the classes 0 .. {classes - 1}")
+    out = {"sem": maps, "mask": torch.ones(batch, 1)}
+    return {k: v.to(device) for k, v in out.items()} if device is not None else out
+
+
 @torch.no_grad()
 def prepare_batch_multiple(meta, model, processor, batch=1, max_objs=MAX_OBJS, device=None):
     """interface.py:424-475: one layout per prompt."""
@@ -610,6 +652,13 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
         raise ValueError("meta['images'] given to a text-only checkpoint: image grounding needs a *_box_text_image checkpoint "
                          "(grounding_tokenizer target text_image_grounding_net.PositionNet)")
     spatial = getattr(model.cfg, "grounding", "text") == "spatial"
+    sem = spatial and getattr(model.cfg, "ds_kind", "") == "sem"           # the semantic-map family: a spatial model fed meta["sem"]
+    if not sem and meta.get(SEM_META_KEY) is not None:
+        raise ValueError(f"a semantic map (meta['sem']) given to a {'canny / hed / depth / normal' if spatial else model.cfg.grounding} "
+                         "checkpoint: class maps need a semantic-map checkpoint (grounding_tokenizer target sem_grounding_net.PositionNet)")
+    if sem and _spatial_map_of(meta) is not None:
+        raise ValueError(f"a grounding map ({[k for k in SPATIAL_META_KEYS if meta.get(k) is not None][0]}) given to a semantic-map checkpoint: "
+                         "it is grounded on a class map under meta['sem']")
     if not spatial and _spatial_map_of(meta) is not None:
         raise ValueError(f"a grounding map ({[k for k in SPATIAL_META_KEYS if meta.get(k) is not None][0]}) given to a {model.cfg.grounding} "
                          "checkpoint: maps need a canny / hed / depth / normal checkpoint")
@@ -619,7 +668,9 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
                        ("locations", "it takes no boxes")):
             if meta.get(k) is not None and (k != "locations" or len(meta[k]) > 0):
                 raise ValueError(f"meta[{k!r}] given to a spatial checkpoint: {why}")
-        if _spatial_map_of(meta) is None:
+        if sem and meta.get(SEM_META_KEY) is None:
+            raise ValueError(f"a semantic-map checkpoint needs its class map under the meta key {SEM_META_KEY!r}")
+        if not sem and _spatial_map_of(meta) is None:
             raise ValueError(f"a spatial checkpoint needs its map under one of the meta keys {SPATIAL_META_KEYS}")
         model.grounding_extra_of({"grounding_extra_input": True}, tuple(int(v) for v in starting_noise.shape[-2:]))      # the latent-size rule
     keypoint = getattr(model.cfg, "grounding", "text") == "keypoint"       # the batch builder follows the model, not the checkpoint's file name
@@ -642,14 +693,14 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     relations = None
     if multiple:
         # (a keypoint model: no phrases, no CLIP model, and -- always on the upstream block -- no relation phrases)
-        batch = prepare_batch_spatial(meta, bs, device) if spatial else \
+        batch = prepare_batch_sem(meta, bs, device, model.cfg.sem_classes) if sem else prepare_batch_spatial(meta, bs, device) if spatial else \
             prepare_batch_kp_multiple(meta, bs, model.cfg.max_persons, device) if keypoint else \
             prepare_batch_multiple(meta, clip_model, clip_processor, bs, device=device)
         context = text_encoder.encode(meta["prompts"])
         if with_rel:
             relations = prepare_relation_phrases_batch(meta["prompts"], max_rel, text_encoder, device=device)
     else:
-        batch = prepare_batch_spatial(meta, bs, device) if spatial else \
+        batch = prepare_batch_sem(meta, bs, device, model.cfg.sem_classes) if sem else prepare_batch_spatial(meta, bs, device) if spatial else \
             prepare_batch_kp(meta, bs, model.cfg.max_persons, device) if keypoint else \
             prepare_batch(meta, clip_model, clip_processor, bs, device=device)
         context = text_encoder.encode([meta["prompt"]] * bs)
@@ -682,7 +733,7 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     samples = denoise(all_models, context, uc, relations, batch, starting_noise, meta.get("alpha_type"), cfg.guidance_scale,
                       steps=int(args.get("steps", PLMS_STEPS)), mask=mask, x0=z0,   # steps per call: not sticky through the cached config
                       inpainting_extra_input=extra,
-                      grounding_extra_input=batch["map"] if spatial else None)      # *_grounding_downsampler_input.prepare: the map itself
+                      grounding_extra_input=batch["sem" if sem else "map"] if spatial else None)      # *_grounding_downsampler_input.prepare: the map itself
     return _postprocess(autoencoder.decode(samples))
 
 

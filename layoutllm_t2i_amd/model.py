@@ -167,13 +167,43 @@ class SpatialGroundingNetInput:
         return {"map": torch.zeros(batch, self.C, self.H, self.W).type(dtype).to(device), "mask": torch.zeros(batch).type(dtype).to(device)}
 
 
+class SemGroundingNetInput:
+    """sem_grounding_tokinzer_input.py:6-43: pass-through of ``sem`` and ``mask`` [B].  ``sem`` is the integer class map [B, H, W] (the native
+    form here) or the reference's float one-hot [B, C, H, W] (semantic.ClassMapInput); the null input is a zero tensor of the same form with
+    a zero mask."""
+    KEYS = ("sem", "mask")
+
+    def __init__(self):
+        self.set = False
+
+    def prepare(self, batch, text_encoder=None):
+        self.set = True
+        sem, mask = batch["sem"], batch["mask"]
+        self.batch, self.shape = sem.shape[0], tuple(sem.shape[1:])
+        self.device = sem.device
+        self.dtype = sem.dtype
+        return {"sem": sem, "mask": mask}
+
+    def get_null_input(self, batch=None, device=None, dtype=None):
+        assert self.set, "not set yet, cannot call this funcion"
+        batch = self.batch if batch is None else batch
+        device = self.device if device is None else device
+        dtype = self.dtype if dtype is None else dtype
+        return {"sem": torch.zeros(batch, *self.shape).type(dtype).to(device), "mask": torch.zeros(batch).type(torch.float32).to(device)}
+
+
 _GROUNDING_INPUTS = {"text": GroundingNetInput, "text_image": TextImageGroundingNetInput, "keypoint": KeypointGroundingNetInput,
                      "spatial": SpatialGroundingNetInput}
 
 
+def grounding_input_class(cfg: UNetConfig):
+    """the grounding-tokenizer input class that goes with the config's PositionNet (the semantic-map family is a spatial config with its own
+    keys)"""
+    return SemGroundingNetInput if getattr(cfg, "ds_kind", "") == "sem" else _GROUNDING_INPUTS[cfg.grounding]
+
+
 def grounding_input_for(cfg: UNetConfig):
-    """the grounding-tokenizer input class that goes with the config's PositionNet"""
-    return _GROUNDING_INPUTS[cfg.grounding]()
+    return grounding_input_class(cfg)()
 
 
 class UNetModel:
@@ -208,9 +238,16 @@ class UNetModel:
         self.tokenizer = self.downsampler = None
         if cfg.grounding == "spatial":
             # the two stages in front of the UNet, from the checkpoint's own position_net.* / downsample_net.* tensors
-            from .spatial import SpatialDownsampler, SpatialTokenizer
-            self.tokenizer = SpatialTokenizer(state_dict, cfg, self.device)
-            self.downsampler = SpatialDownsampler(state_dict, cfg, self.device)
+            if cfg.ds_kind == "sem":
+                # the semantic-map family: both stages read one class map (a float one-hot is converted once for the two)
+                from .semantic import ClassMapInput, SemDownsampler, SemTokenizer
+                cm = ClassMapInput(cfg.sem_classes, self.device)
+                self.tokenizer = SemTokenizer(state_dict, cfg, self.device, cm)
+                self.downsampler = SemDownsampler(state_dict, cfg, self.device, cm)
+            else:
+                from .spatial import SpatialDownsampler, SpatialTokenizer
+                self.tokenizer = SpatialTokenizer(state_dict, cfg, self.device)
+                self.downsampler = SpatialDownsampler(state_dict, cfg, self.device)
         self._cond_key = None
         self.strict = False
 
@@ -273,12 +310,12 @@ class UNetModel:
         if key is not None and key == self._cond_key:
             return
         if self.cfg.grounding != "text":
-            keys = _GROUNDING_INPUTS[self.cfg.grounding].KEYS
+            keys = grounding_input_class(self.cfg).KEYS
             missing = [k for k in keys if k not in grounding]
             if missing:
                 raise ValueError(f"a {self.cfg.grounding} model needs the grounding keys {keys}; missing {missing}")
         if self.cfg.grounding == "spatial":
-            self.engine.set_conditioning_tokens(context, self.tokenizer.tokens(grounding["map"], grounding["mask"]), hw)
+            self.engine.set_conditioning_tokens(context, self.tokenizer.tokens(grounding[keys[0]], grounding["mask"]), hw)      # "map" | "sem"
         elif self.cfg.grounding == "keypoint":
             self.engine.set_conditioning_kp(context, grounding["points"], grounding["masks"], hw)
         elif self.cfg.grounding == "text_image":

@@ -928,3 +928,51 @@ def sp_conv4x4s2(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, silu: boo
     check(_lib.lib().gl_sp_conv4x4s2(x.data_ptr(), w.data_ptr(), bias.data_ptr(), B, Ci, Co, H, W, int(bool(silu)), out.data_ptr(), _stream()),
           "gl_sp_conv4x4s2")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- semantic-map grounding (sem.hip)
+def sem_gather_conv(cmap: torch.Tensor, R: int, table: torch.Tensor, bias: torch.Tensor, K: int, stride: int, pad: int, silu: bool,
+                    out: torch.Tensor) -> torch.Tensor:
+    """class map uint8 [B, Hs, Ws] -> nearest resize to R x R -> Conv2d(classes, Co, K, stride, pad) of its one-hot as a gather from ``table``
+    fp32 [classes, K * K, Co padded to 4] (semantic.gather_table) (+ SiLU) -> fp32 [B, Co, Ro, Ro] (gl_sem_gather_conv)"""
+    _req(cmap, torch.uint8, "cmap", 1)
+    _req(table, F32, "table", 16)
+    _c32(bias, "bias")
+    _c32(out, "out")
+    Co = bias.numel()
+    if cmap.dim() != 3 or not cmap.is_contiguous() or table.dim() != 3 or not table.is_contiguous() or table.shape[1] != K * K or \
+            table.shape[2] != (Co + 3) // 4 * 4:
+        raise ValueError(f"sem_gather_conv: need a contiguous uint8 [B, Hs, Ws] map and a contiguous table [classes, {K * K}, {(Co + 3) // 4 * 4}]")
+    B, Hs, Ws = cmap.shape
+    Ro = (R + 2 * pad - K) // stride + 1
+    if tuple(out.shape) != (B, Co, Ro, Ro):
+        raise ValueError(f"out: need [{B}, {Co}, {Ro}, {Ro}]")
+    check(_lib.lib().gl_sem_gather_conv(cmap.data_ptr(), B, Hs, Ws, R, table.data_ptr(), bias.data_ptr(), table.shape[0], K, stride, pad, Co,
+                                        int(bool(silu)), out.data_ptr(), _stream()), "gl_sem_gather_conv")
+    return out
+
+
+def sem_conv4x4s2(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """Conv2d(Ci, Co, 4, 2, 1) on fp32 NCHW (gl_sem_conv4x4s2); Ci, Co <= 64"""
+    for t, n in ((x, "x"), (w, "w"), (bias, "bias"), (out, "out")):
+        _c32(t, n)
+    B, Ci, H, W = x.shape
+    Co = w.shape[0]
+    if tuple(w.shape) != (Co, Ci, 4, 4) or bias.numel() != Co or H % 2 or W % 2 or tuple(out.shape) != (B, Co, H // 2, W // 2):
+        raise ValueError("sem_conv4x4s2: inconsistent shapes")
+    check(_lib.lib().gl_sem_conv4x4s2(x.data_ptr(), w.data_ptr(), bias.data_ptr(), B, Ci, Co, H, W, out.data_ptr(), _stream()), "gl_sem_conv4x4s2")
+    return out
+
+
+def sem_onehot_index(x: torch.Tensor, out: torch.Tensor, bad: torch.Tensor) -> torch.Tensor:
+    """fp32 one-hot [B, C, H, W] -> uint8 class map [B, H, W] (argmax) and ``bad`` int32 [B], the pixels of each sample that are not exactly
+    one-hot (gl_sem_onehot_index)"""
+    _c32(x, "x")
+    _req(out, torch.uint8, "out", 1)
+    _req(bad, torch.int32, "bad", 4)
+    if x.dim() != 4 or not out.is_contiguous() or tuple(out.shape) != (x.shape[0], x.shape[2], x.shape[3]) or not bad.is_contiguous() or \
+            bad.numel() != x.shape[0]:
+        raise ValueError("sem_onehot_index: need x [B, C, H, W], out uint8 [B, H, W] and bad int32 [B]")
+    B, C, H, W = x.shape
+    check(_lib.lib().gl_sem_onehot_index(x.data_ptr(), B, C, H, W, out.data_ptr(), bad.data_ptr(), _stream()), "gl_sem_onehot_index")
+    return out

@@ -15,7 +15,8 @@ switch on every scale-0 step, step-0 double evaluation, Adams-Bashforth history 
     to the engine once per ``sample()``, not per step;
   * a spatial model (canny / hed / depth / normal) takes ``input["grounding_extra_input"]`` (required there, ValueError before any kernel runs;
     every other model ignores it): its ConvNeXt tokenizer runs once per ``sample()`` on the conditional maps, the unconditional half takes
-    the model's cached null tokens, and both halves read the same downsampled extra (plms.py:118-121), handed to the engine once;
+    the model's cached null tokens, and both halves read the same downsampled extra (plms.py:118-121), handed to the engine once; a
+    semantic-map model reads its class map (or the reference's float one-hot, converted once) under the key ``sem`` where the others read ``map``;
   * inpainting (``mask`` / ``x0``, plms.py:95-99): each step first replaces the known region,
     x = q_sample(x0, t) * mask + (1 - mask) * x, as one fused in-place fp32 HIP kernel (gl_latent_blend, bit-identical to
     the torch expression), with the q_sample noise drawn by ``torch.randn_like(x0)`` before the step's own draws.
@@ -95,10 +96,12 @@ class PLMSSampler(object):
         if spatial:
             # the ConvNeXt tokenizer once per sample() on the conditional maps; the unconditional half takes the model's cached null tokens
             # (a zero map with mask 0: linears(null_feature + pos_embedding) whatever the image) and the SAME downsampled extra (plms.py:118-121)
-            missing = [k for k in ("map", "mask") if k not in g]
+            from .model import grounding_input_class
+            keys = grounding_input_class(model.cfg).KEYS      # ("map", "mask"); ("sem", "mask") on a semantic-map model
+            missing = [k for k in keys if k not in g]
             if missing:
-                raise ValueError(f"a spatial model needs the grounding keys ('map', 'mask'); missing {missing}")
-            objs = model.tokenizer.tokens(g["map"], g["mask"])
+                raise ValueError(f"a spatial model needs the grounding keys {keys}; missing {missing}")
+            objs = model.tokenizer.tokens(g[keys[0]], g["mask"])
             ctx = f32(input["context"])
             if cfg_on:
                 objs = torch.cat([objs, model.tokenizer.null_tokens().expand(objs.shape[0], -1, -1)], 0)
