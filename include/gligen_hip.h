@@ -521,7 +521,7 @@ int gl_set_grounding_extra(gl_engine* e, const float* extra, int32_t Bs, void* s
 /* gl_last_error: the message of the handle's last GL_ERR_BAD_ARG that carries one (a conditioning entry of the wrong grounding family, a
  * latent shape that breaks the shape rule, strict mode without split weights, the inpaint_mode checks of gl_set_inpaint_extra), copied NUL-terminated into dst (at most bytes - 1
  * characters).  Returns the message's full length, 0 when there is none.  With e == NULL it returns the calling thread's last message of
- * the entries that take no handle (gl_layout_reward).  Additive to ABI 15. */
+ * the entries that take no handle (gl_layout_reward, gl_policy_select).  Additive to ABI 15. */
 int gl_last_error(const gl_engine* e, char* dst, int32_t bytes);
 /* gl_unet_forward: eps[Bn, out_ch, hw, hw] fp32 = UNet(x, t | conditioning).  x fp32 NCHW [Bn / reps, in_ch, hw, hw]:
  * with reps = 2 both CFG halves of a [cond ; uncond] conditioning batch share the latent.  t_dev: fp32 [Bn] device
@@ -600,6 +600,51 @@ int gl_layout_reward(const gl_layout_reward_args* a, void* stream);
 /* sizeof(gl_layout_reward_args), for the binding's layout check (tests/test_layout_host.py).  Replaces nothing of the reference (the
  * arguments of metrics.py:77-82,146-151 are Python lists).  Additive to ABI 15. */
 int gl_sizeof_layout_reward_args(void);
+
+/*
+ * gl_policy_select: the scoring and ranking half of the policy's example selection (models/policy.py:11-33 with train_rl.py:167-172 and
+ * txt2img.py:472-474, :429), which the reference runs as two nn.Linear calls and a torch.mm in fp32 and a Python sort on the host.
+ *   scores[p, n] = (W prompt_p + bias) . (W cand_n + bias)                    fp32 [P, N]
+ *   topk[p, 0 .. k)  = the k best candidate indices of prompt p, best first; equal scores: the lower index first (the stable
+ *                      sorted(..., reverse=True)[:k] of txt2img.py:429); with k > N the first N slots are filled, the rest hold -1.
+ *                      A NaN score ranks below every number, -inf included, lower index first (the reference's order with a NaN is
+ *                      unspecified: Python's sort under an inconsistent comparison).  -0 and +0 rank as equal.
+ *   probs[p, :]      = softmax(scores[p, :] / temperature) (train_rl.py:172), when probs != NULL: computed from the scores in DOUBLE (a second
+ *                      pass over the pool with the unrounded fold) and rounded to fp32 once, so that the fp32 scores' rounding does not enter
+ * The product is linear in the candidate, so the pool is not projected: q_p = W prompt_p + bias, v_p = W^T q_p and c_p = q_p . bias are
+ * computed per call (summed in double, v and c stored as fp32) and scores[p, n] = v_p . cand_n + c_p streams the pool once per group of 8
+ * prompts with 16-byte loads, fp32 fmaf and a 64-lane butterfly sum.  A row's score does not depend on its position, on N or on the grid: equal rows get bit-equal scores.  The top-k
+ * runs in two stages (per 64-row block into scratch, then one merge block per prompt) without atomics; the result is deterministic.
+ * W == NULL is the identity (add_linear=False): E must equal D, bias is not read.
+ * Stream-ordered, no host synchronisation; the caller provides the scratch: gl_policy_scratch_bytes(P, N, D, E, k, W == NULL, probs != NULL) bytes of
+ * device memory, 16-byte aligned like prompt, cand and W.  GL_ERR_BAD_ARG, before anything is launched and with a message
+ * gl_last_error(NULL, ...) returns: a null pointer (args, prompt, cand, scores, bias with W, topk with k > 0, scratch), P outside
+ * [1, GL_POLICY_MAX_PROMPTS], N < 1, D not a multiple of 4 or above GL_POLICY_MAX_DIM, E outside [1, GL_POLICY_MAX_DIM] (or != D with
+ * W == NULL), k outside [0, GL_POLICY_MAX_SHOTS], temperature <= 0 (or NaN) with probs, a scratch that is too small, a misaligned pointer.
+ * Additive to ABI 15.
+ */
+#define GL_POLICY_MAX_PROMPTS 64
+#define GL_POLICY_MAX_DIM 1024
+#define GL_POLICY_MAX_SHOTS 32
+typedef struct gl_policy_args {
+    const float* prompt;        /* device [P, D] */
+    const float* cand;          /* device [N, D] */
+    const float* W;             /* device [E, D], NULL = identity */
+    const float* bias;          /* device [E] (not read when W == NULL) */
+    int32_t P, N, D, E, k;
+    double temperature;         /* read when probs != NULL */
+    float* scores;              /* device [P, N] */
+    int32_t* topk;              /* device [P, k] (may be NULL when k == 0) */
+    float* probs;               /* device [P, N] or NULL */
+    void* scratch; int64_t scratch_bytes;
+} gl_policy_args;
+int gl_policy_select(const gl_policy_args* a, void* stream);
+/* sizeof(gl_policy_args), for the binding's layout check (tests/test_policy_host.py).  Additive to ABI 15. */
+int gl_sizeof_policy_args(void);
+/* bytes of scratch gl_policy_select needs for these sizes (identity != 0: W == NULL; probs != 0: probabilities asked for); GL_ERR_BAD_ARG for a
+ * size below 1 (k below 0).
+ * Replaces nothing of the reference.  Additive to ABI 15. */
+int64_t gl_policy_scratch_bytes(int32_t P, int32_t N, int32_t D, int32_t E, int32_t k, int32_t identity, int32_t probs);
 
 int gl_gemm(const gl_gemm_args* a, void* stream);
 int gl_conv3x3(const gl_conv_args* a, void* stream);

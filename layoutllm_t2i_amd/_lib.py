@@ -145,6 +145,12 @@ class LayoutRewardArgs(C.Structure):
                 ("n_gt_host", vp), ("n_pred_host", vp), ("B", i32), ("miou", vp), ("docsim", vp)]
 
 
+class PolicyArgs(C.Structure):
+    """gl_policy_args"""
+    _fields_ = [("prompt", vp), ("cand", vp), ("W", vp), ("bias", vp), ("P", i32), ("N", i32), ("D", i32), ("E", i32), ("k", i32),
+                ("temperature", C.c_double), ("scores", vp), ("topk", vp), ("probs", vp), ("scratch", vp), ("scratch_bytes", i64)]
+
+
 class FFArgs(C.Structure):
     """gl_ff_args"""
     _fields_ = [("x", vp), ("ldx", i32), ("w1", vp), ("b1", vp), ("w2", vp), ("b2", vp), ("res", vp), ("ldres", i32), ("res_f32", i32),
@@ -228,6 +234,9 @@ PROTOTYPES = {
     "gl_sizeof_reward_args": (i32, []),
     "gl_layout_reward": (i32, [C.POINTER(LayoutRewardArgs), vp]),
     "gl_sizeof_layout_reward_args": (i32, []),
+    "gl_policy_select": (i32, [C.POINTER(PolicyArgs), vp]),
+    "gl_sizeof_policy_args": (i32, []),
+    "gl_policy_scratch_bytes": (i64, [i32, i32, i32, i32, i32, i32, i32]),
     "gl_ff_fused": (i32, [C.POINTER(FFArgs), vp]),
     "gl_ff_fused_supported": (i32, [i32]),
     "gl_ff_fused_applicable": (i32, [i32, i32]),
@@ -299,7 +308,7 @@ def lib() -> C.CDLL:
                     (UNetConfigC, l.gl_sizeof_unet_config), (WeightInfo, l.gl_sizeof_weight_info),
                     (PlmsStepArgs, l.gl_sizeof_plms_step_args), (RewardArgs, l.gl_sizeof_reward_args), (FFArgs, l.gl_sizeof_ff_args),
                     (VaeConfigC, l.gl_sizeof_vae_config), (GnArgs, l.gl_sizeof_gn_args),
-                    (LayoutRewardArgs, l.gl_sizeof_layout_reward_args)):
+                    (LayoutRewardArgs, l.gl_sizeof_layout_reward_args), (PolicyArgs, l.gl_sizeof_policy_args)):
         if C.sizeof(cls) != fn():
             raise HipLibraryError(f"struct size mismatch for {cls.__name__}: host {C.sizeof(cls)} vs lib {fn()}")
     _lib = l
@@ -447,7 +456,7 @@ def engine_table(cfg, fold_up=None):
 
 def last_error(handle) -> str:
     """gl_last_error: the message the handle's last failing entry left (empty when there is none); ``None``: the calling thread's last
-    message of the entries that take no handle (gl_layout_reward)"""
+    message of the entries that take no handle (gl_layout_reward, gl_policy_select)"""
     buf = C.create_string_buffer(512)
     n = lib().gl_last_error(handle, buf, len(buf))
     return buf.value.decode() if n > 0 else ""

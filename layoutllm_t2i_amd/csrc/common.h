@@ -80,8 +80,10 @@ static inline int gn_nchunk(int HW) {
     return c > 512 ? 512 : c;
 }
 
-// The calling thread's last refusal message of an entry that takes no handle (layout_reward.hip); gl_last_error(NULL, ...) reads it
+// The calling thread's last refusal message of an entry that takes no handle (layout_reward.hip keeps it, policy.hip sets it too);
+// gl_last_error(NULL, ...) reads it
 const char* gl_handleless_error();
+void gl_set_handleless_error(const char* msg);
 
 #define GL_CHECK_LAUNCH()                                   \
     do {                                                    \

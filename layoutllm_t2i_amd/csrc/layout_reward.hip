@@ -203,6 +203,7 @@ int refuse(const char* fmt, int a0 = 0, int a1 = 0) {
 }  // namespace
 
 const char* gl_handleless_error() { return g_layout_err.c_str(); }
+void gl_set_handleless_error(const char* msg) { g_layout_err = msg; }
 
 extern "C" int gl_layout_reward(const gl_layout_reward_args* a, void* stream) {
     if (!a) return refuse("null args");
