@@ -521,7 +521,7 @@ int gl_set_grounding_extra(gl_engine* e, const float* extra, int32_t Bs, void* s
 /* gl_last_error: the message of the handle's last GL_ERR_BAD_ARG that carries one (a conditioning entry of the wrong grounding family, a
  * latent shape that breaks the shape rule, strict mode without split weights, the inpaint_mode checks of gl_set_inpaint_extra), copied NUL-terminated into dst (at most bytes - 1
  * characters).  Returns the message's full length, 0 when there is none.  With e == NULL it returns the calling thread's last message of
- * the entries that take no handle (gl_layout_reward, gl_policy_select).  Additive to ABI 15. */
+ * the entries that take no handle (gl_layout_reward, gl_policy_select, gl_policy_grad, gl_policy_adam_step).  Additive to ABI 15. */
 int gl_last_error(const gl_engine* e, char* dst, int32_t bytes);
 /* gl_unet_forward: eps[Bn, out_ch, hw, hw] fp32 = UNet(x, t | conditioning).  x fp32 NCHW [Bn / reps, in_ch, hw, hw]:
  * with reps = 2 both CFG halves of a [cond ; uncond] conditioning batch share the latent.  t_dev: fp32 [Bn] device
@@ -645,6 +645,73 @@ int gl_sizeof_policy_args(void);
  * size below 1 (k below 0).
  * Replaces nothing of the reference.  Additive to ABI 15. */
 int64_t gl_policy_scratch_bytes(int32_t P, int32_t N, int32_t D, int32_t E, int32_t k, int32_t identity, int32_t probs);
+
+/*
+ * gl_policy_grad: the REINFORCE loss of one rollout batch and its gradient to the policy layer (train_rl.py:167-172, :85-95 followed by
+ * loss.backward(), :183), which the reference builds from two nn.Linear calls, a torch.mm, F.softmax and torch.log in fp32 and autograd.
+ *   q_p = W prompt_p + bias,  c_n = W cand_n + bias,  z[p, n] = q_p . c_n / temperature
+ *   logp[p]  = sum_j (z[p, sel[p, j]] - logsumexp_n z[p, :])                  double [P]
+ *   loss     = -sum_p reward[p] logp[p]                                        double [1]
+ *   grad_W   = d loss / d W  fp32 [E, D],   grad_b = d loss / d bias  fp32 [E]
+ * with G[p, n] = -(reward[p] / temperature) (m[p, n] - k_p pi[p, n]), m[p, n] = how often n occurs in sel[p, :], k_p = the valid entries of
+ * sel[p, :], pi = softmax(z): dQ = G C, dC = G^T Q, grad_W = dQ^T prompt + dC^T cand, grad_b = the column sums of dQ and dC.
+ * An entry of sel outside [0, N) is skipped: it contributes nothing and is not counted in k_p (a row with fewer examples, a padded row);
+ * no index read from device memory addresses outside the pool.  A repeated index counts as often as it occurs, as the reference's loop does.
+ * reward is double, as the reference's is (its mIoU term comes from numpy).
+ * All arithmetic is in double from the fp32 operands; the log-softmax is z - logsumexp(z), finite where the reference's fp32
+ * log(softmax(z)) is -inf; grad_W and grad_b are rounded to fp32 once.  Four launches, no atomics, every sum in an order fixed by the sizes:
+ * two calls on the same inputs give bit-equal outputs, and logp[p] does not depend on the row's index.
+ * Stream-ordered, no host synchronisation; the caller provides gl_policy_grad_scratch_bytes(P, N, D, E, k) bytes of device memory, 16-byte
+ * aligned like prompt, cand and W: three arrays of doubles, each rounded up to 256 bytes: [P + N, E] projections, [P, N] scores / G, [P + N, E] dQ and dC.
+ * GL_ERR_BAD_ARG, before anything is launched and with a message gl_last_error(NULL, ...) returns: a null pointer (W included: the identity
+ * policy has nothing to train), P outside [1, GL_POLICY_MAX_PROMPTS], N outside [1, GL_POLICY_TRAIN_MAX_CANDS], D not a multiple of 4 or above
+ * GL_POLICY_MAX_DIM, E outside [1, GL_POLICY_MAX_DIM], k outside [1, GL_POLICY_MAX_SHOTS], temperature <= 0 (or NaN), a scratch that is too
+ * small, a misaligned prompt / cand / W / scratch.  Additive to ABI 15.
+ */
+#define GL_POLICY_TRAIN_MAX_CANDS 4096
+typedef struct gl_policy_grad_args {
+    const float* prompt;        /* device [P, D] */
+    const float* cand;          /* device [N, D] */
+    const float* W;             /* device [E, D] */
+    const float* bias;          /* device [E] */
+    const int32_t* sel;         /* device [P, k]: the sampled candidate indices; outside [0, N) = skipped */
+    const double* reward;       /* device [P] */
+    int32_t P, N, D, E, k;
+    double temperature;
+    double* loss;               /* device [1] */
+    double* logp;               /* device [P] */
+    float* grad_W;              /* device [E, D] */
+    float* grad_b;              /* device [E] */
+    void* scratch; int64_t scratch_bytes;
+} gl_policy_grad_args;
+int gl_policy_grad(const gl_policy_grad_args* a, void* stream);
+/* sizeof(gl_policy_grad_args), for the binding's layout check (tests/test_policy_train_host.py).  Additive to ABI 15. */
+int gl_sizeof_policy_grad_args(void);
+/* bytes of scratch gl_policy_grad needs for these sizes; GL_ERR_BAD_ARG for a size gl_policy_grad refuses.  Additive to ABI 15. */
+int64_t gl_policy_grad_scratch_bytes(int32_t P, int32_t N, int32_t D, int32_t E, int32_t k);
+
+/*
+ * gl_policy_adam_step: one torch.optim.Adam step with the reference's settings (train_rl.py:119: weight_decay = 0, no amsgrad) on the policy
+ * layer, in place, with the fp32 state exp_avg / exp_avg_sq of both tensors.  step is the step number AFTER the increment (>= 1).  Per
+ * element, in double from the fp32 values, each stored value rounded to fp32 once:
+ *   m = m + (g - m) (1 - beta1);   v = beta2 v + (1 - beta2) g^2
+ *   p = p - (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * One elementwise launch over the E D + E elements, stream-ordered.  GL_ERR_BAD_ARG, before anything is launched and with a message
+ * gl_last_error(NULL, ...) returns: a null pointer, D or E out of gl_policy_grad's range, step < 1, lr or eps negative, infinite or NaN, a beta
+ * outside [0, 1).  Additive to ABI 15.
+ */
+typedef struct gl_policy_adam_args {
+    float* W; float* bias;                          /* device [E, D], [E]: updated in place */
+    const float* grad_W; const float* grad_b;
+    float* exp_avg_W; float* exp_avg_sq_W;          /* device [E, D] */
+    float* exp_avg_b; float* exp_avg_sq_b;          /* device [E] */
+    int32_t D, E;
+    int64_t step;
+    double lr, beta1, beta2, eps;
+} gl_policy_adam_args;
+int gl_policy_adam_step(const gl_policy_adam_args* a, void* stream);
+/* sizeof(gl_policy_adam_args), for the binding's layout check.  Additive to ABI 15. */
+int gl_sizeof_policy_adam_args(void);
 
 int gl_gemm(const gl_gemm_args* a, void* stream);
 int gl_conv3x3(const gl_conv_args* a, void* stream);

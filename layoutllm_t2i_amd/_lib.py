@@ -151,6 +151,20 @@ class PolicyArgs(C.Structure):
                 ("temperature", C.c_double), ("scores", vp), ("topk", vp), ("probs", vp), ("scratch", vp), ("scratch_bytes", i64)]
 
 
+class PolicyGradArgs(C.Structure):
+    """gl_policy_grad_args"""
+    _fields_ = [("prompt", vp), ("cand", vp), ("W", vp), ("bias", vp), ("sel", vp), ("reward", vp),
+                ("P", i32), ("N", i32), ("D", i32), ("E", i32), ("k", i32), ("temperature", C.c_double),
+                ("loss", vp), ("logp", vp), ("grad_W", vp), ("grad_b", vp), ("scratch", vp), ("scratch_bytes", i64)]
+
+
+class PolicyAdamArgs(C.Structure):
+    """gl_policy_adam_args"""
+    _fields_ = [("W", vp), ("bias", vp), ("grad_W", vp), ("grad_b", vp), ("exp_avg_W", vp), ("exp_avg_sq_W", vp), ("exp_avg_b", vp),
+                ("exp_avg_sq_b", vp), ("D", i32), ("E", i32), ("step", i64), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double)]
+
+
 class FFArgs(C.Structure):
     """gl_ff_args"""
     _fields_ = [("x", vp), ("ldx", i32), ("w1", vp), ("b1", vp), ("w2", vp), ("b2", vp), ("res", vp), ("ldres", i32), ("res_f32", i32),
@@ -237,6 +251,11 @@ PROTOTYPES = {
     "gl_policy_select": (i32, [C.POINTER(PolicyArgs), vp]),
     "gl_sizeof_policy_args": (i32, []),
     "gl_policy_scratch_bytes": (i64, [i32, i32, i32, i32, i32, i32, i32]),
+    "gl_policy_grad": (i32, [C.POINTER(PolicyGradArgs), vp]),
+    "gl_sizeof_policy_grad_args": (i32, []),
+    "gl_policy_grad_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
+    "gl_policy_adam_step": (i32, [C.POINTER(PolicyAdamArgs), vp]),
+    "gl_sizeof_policy_adam_args": (i32, []),
     "gl_ff_fused": (i32, [C.POINTER(FFArgs), vp]),
     "gl_ff_fused_supported": (i32, [i32]),
     "gl_ff_fused_applicable": (i32, [i32, i32]),
@@ -308,7 +327,8 @@ def lib() -> C.CDLL:
                     (UNetConfigC, l.gl_sizeof_unet_config), (WeightInfo, l.gl_sizeof_weight_info),
                     (PlmsStepArgs, l.gl_sizeof_plms_step_args), (RewardArgs, l.gl_sizeof_reward_args), (FFArgs, l.gl_sizeof_ff_args),
                     (VaeConfigC, l.gl_sizeof_vae_config), (GnArgs, l.gl_sizeof_gn_args),
-                    (LayoutRewardArgs, l.gl_sizeof_layout_reward_args), (PolicyArgs, l.gl_sizeof_policy_args)):
+                    (LayoutRewardArgs, l.gl_sizeof_layout_reward_args), (PolicyArgs, l.gl_sizeof_policy_args),
+                    (PolicyGradArgs, l.gl_sizeof_policy_grad_args), (PolicyAdamArgs, l.gl_sizeof_policy_adam_args)):
         if C.sizeof(cls) != fn():
             raise HipLibraryError(f"struct size mismatch for {cls.__name__}: host {C.sizeof(cls)} vs lib {fn()}")
     _lib = l
@@ -456,7 +476,7 @@ def engine_table(cfg, fold_up=None):
 
 def last_error(handle) -> str:
     """gl_last_error: the message the handle's last failing entry left (empty when there is none); ``None``: the calling thread's last
-    message of the entries that take no handle (gl_layout_reward, gl_policy_select)"""
+    message of the entries that take no handle (gl_layout_reward, gl_policy_select, gl_policy_grad, gl_policy_adam_step)"""
     buf = C.create_string_buffer(512)
     n = lib().gl_last_error(handle, buf, len(buf))
     return buf.value.decode() if n > 0 else ""

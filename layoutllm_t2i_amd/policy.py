@@ -10,7 +10,8 @@ The reference projects the CLIP text features of the prompts and of the whole ca
 * ``CandidatePool`` keeps the candidate records with their CLIP text features, embedded once on the HIP text tower;
 * ``sample_examples`` is the host part of the rollout, from numpy's stream like the reference.
 
-The log-probability sum and the policy gradient (train_rl.py:50-75, :183-190) need autograd and stay the caller's torch code.
+The log-probability sum, the policy gradient and the optimiser step (train_rl.py:85-95, :182-184) are ``policy_train.PolicyTrainer``, which
+updates this network's layer in place; the trainer's loop is ``train_rl``.
 No fallback: without a GPU / the library the scoring raises.
 """
 from __future__ import annotations
