@@ -361,10 +361,10 @@ def unet_config_c(cfg) -> UNetConfigC:
         c.attention_resolutions[i] = int(m)
     c.num_heads, c.context_dim = cfg.num_heads, cfg.context_dim
     c.pos_in_dim, c.pos_out_dim, c.fourier_freqs, c.max_objs = cfg.pos_in_dim, cfg.pos_out_dim, cfg.fourier_freqs, cfg.max_objs
-    c.split_weights = int(bool(getattr(cfg, "split_weights", False)))
-    c.grounding = GROUNDING_IDS[getattr(cfg, "grounding", "text")]
-    c.inpaint_mode = int(bool(getattr(cfg, "inpaint_mode", False)))
-    c.no_relation = int(not getattr(cfg, "relation", True))
+    c.split_weights = int(bool(cfg.split_weights))
+    c.grounding = GROUNDING_IDS[cfg.grounding]
+    c.inpaint_mode = int(bool(cfg.inpaint_mode))
+    c.no_relation = int(not cfg.relation)
     if c.grounding == GROUNDING_IDS["spatial"]:
         # max_objs counts the tokenizer's tokens (the downsampler's channels are not in the struct: create_engine, gl_set_extra_channels)
         c.max_objs = cfg.n_ground
@@ -419,7 +419,7 @@ def create_engine(cfg, fold_up=None) -> int:
     cc = unet_config_c(cfg)
     with _fold_up_scope(fold_up):
         check(lib().gl_create(C.byref(cc), C.byref(h)), "gl_create")
-    if getattr(cfg, "ds_out", 0):
+    if cfg.ds_out:
         # a spatial config: the channels its grounding downsampler adds in front of the first conv
         rc = lib().gl_set_extra_channels(h, int(cfg.ds_out))
         if rc != 0:

@@ -111,7 +111,7 @@ class UNetEngine:
             raise ValueError("a keypoint model is conditioned on points and masks (set_conditioning_kp), not on boxes and embeddings")
         if self.cfg.grounding == "spatial":
             raise ValueError("boxes given to a spatial model: it is conditioned on the tokens of its map (set_conditioning_tokens)")
-        rel_on = getattr(self.cfg, "relation", True)
+        rel_on = self.cfg.relation
         if not rel_on:
             relations = None
         elif relations is None:

@@ -44,6 +44,7 @@ import os
 import torch
 
 from . import interface
+from .family import family_of
 
 _MODELS = {}
 
@@ -68,10 +69,10 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     args = dict(batch_size=bs, no_plms=bool(_get(config, "no_plms", False)), guidance_scale=_get(config, "guidance_scale", 7.5))
     if _get(config, "negative_prompt") is not None:      # gligen_inference.py:379-380; absent / None = the empty prompt
         args["negative_prompt"] = _get(config, "negative_prompt")
-    # a spatial checkpoint (canny / hed / depth / normal; the reference routes on the checkpoint's file name, gligen_inference.py:365-372, here
-    # the loaded model decides) is grounded on one map under the reference's own meta key: no locations, no phrases
-    spatial = getattr(getattr(all_models[0], "cfg", None), "grounding", "text") == "spatial"
-    m = dict(prompt=meta["prompt"], phrases=meta.get("phrases"), locations=meta.get("locations") if spatial else meta["locations"],
+    # the reference routes on the checkpoint's file name (gligen_inference.py:363-372); here the loaded model's family decides.  A map family
+    # (canny / hed / depth / normal, sem) is grounded on one map under the reference's own meta key: no locations, no phrases
+    fam = family_of(getattr(all_models[0], "cfg", None))
+    m = dict(prompt=meta["prompt"], phrases=meta.get("phrases"), locations=meta.get("locations") if fam.extra_key else meta["locations"],
              alpha_type=meta.get("alpha_type", [0.3, 0.0, 0.7]), input_image=meta.get("input_image"))
     for k in interface.SPATIAL_META_KEYS + (interface.SEM_META_KEY,):
         if meta.get(k) is not None:
@@ -83,10 +84,8 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     if starting_noise is None:
         h, w = interface.latent_hw(_get(config, "height"), _get(config, "width"), all_models[1])
         starting_noise = torch.randn(bs, 4, h, w).to(device)
-    # a keypoint checkpoint (the reference routes on "keypoint" in meta["ckpt"], gligen_inference.py:363; here the loaded model decides) is
-    # grounded on meta["locations"] = persons of 17 [x, y] alone: no phrases, and no CLIP model to create
-    keypoint = getattr(getattr(all_models[0], "cfg", None), "grounding", "text") == "keypoint"
-    if not keypoint and not spatial and (clip_model is None or clip_processor is None):
+    # (a keypoint checkpoint is grounded on meta["locations"] = persons of 17 [x, y] alone: no phrases, and no CLIP model to create)
+    if fam.clip and (clip_model is None or clip_processor is None):
         from transformers import CLIPModel, CLIPProcessor
         version = "openai/clip-vit-large-patch14"
         clip_model = CLIPModel.from_pretrained(version).to(device)

@@ -34,6 +34,7 @@ import torch
 from . import host
 from .arch import UNetConfig
 from .arch import VAEConfig
+from .family import family_of
 from .model import LatentDiffusion, UNetModel, grounding_input_for, load_sd_first_conv
 from .vae import VAEDecoder
 from .sampler import PLMSSampler
@@ -148,29 +149,24 @@ def load_ckpt(ckpt_path, device="cuda", strict=None):
     keeps the GLIGEN conv.  ``GLIGEN_ALLOW_NO_SD_CONV=1`` opts out explicitly (first_conv_restorable = False)."""
     saved_ckpt = torch.load(ckpt_path, map_location="cpu")
     config = saved_ckpt["config_dict"]["_content"]
-    # (_run builds the inpainting extra an inpaint_mode model needs, and the points / masks batch of a keypoint model)
-    # (... and the map batch of a spatial model: canny / hed / depth / normal, whose ConvNeXt tokenizer and grounding downsampler are built
-    # from the checkpoint's own position_net.* / downsample_net.* tensors -- nothing is fetched)
-    # (... and the class-map batch of a semantic-map model, sem_grounding_net / sem_grounding_downsampler: the family is read off the config,
-    # not off the file name)
+    # every family loads (family.py): _run builds the batch and the extras each needs; the family is read off the config, not off the file name,
+    # and a map family's ConvNeXt tokenizer and grounding downsampler are built from the checkpoint's own tensors -- nothing is fetched
     cfg = UNetConfig.from_dict(config["model"]["params"], allow_inpaint=True, allow_keypoint=True, allow_spatial=True, allow_semantic=True)
     import dataclasses
-    if cfg.grounding == "spatial" and any(".rela_fuse." in k for k in saved_ckpt["model"]):
-        raise NotImplementedError("a spatial checkpoint with *.rela_fuse.* tensors: the relation chain pools image features over grounding "
-                                  "boxes, and a spatial model has none (it runs on the upstream block only)")
-    if cfg.grounding == "spatial":
+    fam = family_of(cfg)
+    if not fam.relation and any(".rela_fuse." in k for k in saved_ckpt["model"]):
+        raise NotImplementedError(f"a {cfg.grounding} checkpoint with *.rela_fuse.* tensors: the relation chain pools image features over grounding "
+                                  f"boxes, and a {cfg.grounding} model has none (it runs on the upstream block only)")
+    if fam.extra_key is not None:
         # the ConvNeXt's depths and widths are the checkpoint's own (its config does not state them; the shipped ones are convnext_tiny's)
         from .spatial import backbone_of
         depths, dims = backbone_of(saved_ckpt["model"])
         cfg = dataclasses.replace(cfg, convnext_depths=depths, convnext_dims=dims)
-    if cfg.grounding == "keypoint" and any(".rela_fuse." in k for k in saved_ckpt["model"]):
-        raise NotImplementedError("a keypoint checkpoint with *.rela_fuse.* tensors: the relation chain pools image features over grounding "
-                                  "boxes, and a keypoint model has none (keypoint grounding runs on the upstream block only)")
     # a checkpoint without rela_fuse tensors (GLIGEN's own) runs on the upstream block, not on a default-initialised relation chain
     cfg = dataclasses.replace(cfg, relation=checkpoint_has_relation(saved_ckpt["model"], cfg))
     if strict is None:
         strict = os.environ.get("GLIGEN_STRICT") == "1"
-    if strict and cfg.grounding == "spatial":
+    if strict and fam.extra_key is not None:
         raise NotImplementedError("strict mode (strict=True / GLIGEN_STRICT=1) of a spatial checkpoint: the ConvNeXt tokenizer has no split-fp16 "
                                   "form; load it in the default mode")
     if strict:
@@ -432,6 +428,19 @@ def _spatial_map_of(meta):
     return meta[given[0]] if given else None
 
 
+def _need_spatial_map(meta):
+    src = _spatial_map_of(meta)
+    if src is None:
+        raise ValueError(f"a spatial checkpoint needs its map under one of the meta keys {SPATIAL_META_KEYS}")
+    return src
+
+
+def _need_sem_map(meta):
+    if meta.get(SEM_META_KEY) is None:
+        raise ValueError(f"a semantic-map checkpoint needs its class map under the meta key {SEM_META_KEY!r}")
+    return meta[SEM_META_KEY]
+
+
 def load_spatial_map(image) -> torch.Tensor:
     """gligen_inference.py:190-194 + :226-228: ``Image.open(path).convert("RGB")`` (or a ``PIL.Image``), torchvision's centre crop to the
     shorter side (top / left = round((side - crop) / 2)), PIL ``resize((512, 512))`` (its default filter), pil_to_tensor, ``/ 255``,
@@ -452,9 +461,7 @@ def prepare_batch_spatial(meta, batch=1, device=None):
     """gligen_inference.py:221-297 (prepare_batch_hed / _canny / _depth / _normal, one function here: they differ in the meta key alone).  The
     map under ``meta["canny_image"]`` / ``["hed_image"]`` / ``["depth"]`` / ``["normal"]`` (a path or a ``PIL.Image``) repeated ``batch`` times:
     ``map`` [batch, 3, 512, 512] in [-1, 1] and ``mask`` [batch, 1] of ones.  A list of ``batch`` maps gives one map per sample."""
-    src = _spatial_map_of(meta)
-    if src is None:
-        raise ValueError(f"a spatial checkpoint needs its map under one of the meta keys {SPATIAL_META_KEYS}")
+    src = _need_spatial_map(meta)
     if isinstance(src, (list, tuple)):
         if len(src) != batch:
             raise ValueError(f"{len(src)} grounding maps for a batch of {batch}")
@@ -489,9 +496,7 @@ def prepare_batch_sem(meta, batch=1, device=None, classes=152):
     argmaxes to (the kernels of a semantic-map model read it directly), and ``mask`` [batch, 1] of ones.  A list of ``batch`` maps gives one
     map per sample.  A pixel value >= ``classes`` raises ValueError (the reference's ``scatter_`` raises there too); the colour visualisation
     side file of the reference is not written."""
-    src = meta.get(SEM_META_KEY)
-    if src is None:
-        raise ValueError(f"a semantic-map checkpoint needs its class map under the meta key {SEM_META_KEY!r}")
+    src = _need_sem_map(meta)
     if isinstance(src, (list, tuple)):
         if len(src) != batch:
             raise ValueError(f"{len(src)} semantic maps for a batch of {batch}")
@@ -644,68 +649,53 @@ def _has_images(images, multiple) -> bool:
     return any(im is not None for im in flat)
 
 
-def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple):
-    model, autoencoder, text_encoder, diffusion, config = all_models
-    _check_noise(model, starting_noise)
-    if _has_images(meta.get("images"), multiple) and getattr(model.cfg, "grounding", "text") != "text_image":
+_OWN_MAP = {"map": _need_spatial_map, "sem": _need_sem_map}       # Family.extra_key -> the map under the family's own meta key(s), or ValueError
+
+
+def _refuse_foreign_meta(model, fam, meta, multiple, hw) -> None:
+    """Every refusal of ``_run``, before any encoder or kernel runs: what the meta dict carries against what the family (family.Family) takes.
+    Reads ``model.cfg`` alone, plus ``model.grounding_extra_of`` (the latent-size rule) on a map family."""
+    if _has_images(meta.get("images"), multiple) and not fam.images:
         # (the reference would prepare image tokens and drop them silently: text_layout_tokinzer_input.py reads three keys)
         raise ValueError("meta['images'] given to a text-only checkpoint: image grounding needs a *_box_text_image checkpoint "
                          "(grounding_tokenizer target text_image_grounding_net.PositionNet)")
-    spatial = getattr(model.cfg, "grounding", "text") == "spatial"
-    sem = spatial and getattr(model.cfg, "ds_kind", "") == "sem"           # the semantic-map family: a spatial model fed meta["sem"]
-    if not sem and meta.get(SEM_META_KEY) is not None:
-        raise ValueError(f"a semantic map (meta['sem']) given to a {'canny / hed / depth / normal' if spatial else model.cfg.grounding} "
-                         "checkpoint: class maps need a semantic-map checkpoint (grounding_tokenizer target sem_grounding_net.PositionNet)")
-    if sem and _spatial_map_of(meta) is not None:
-        raise ValueError(f"a grounding map ({[k for k in SPATIAL_META_KEYS if meta.get(k) is not None][0]}) given to a semantic-map checkpoint: "
-                         "it is grounded on a class map under meta['sem']")
-    if not spatial and _spatial_map_of(meta) is not None:
-        raise ValueError(f"a grounding map ({[k for k in SPATIAL_META_KEYS if meta.get(k) is not None][0]}) given to a {model.cfg.grounding} "
-                         "checkpoint: maps need a canny / hed / depth / normal checkpoint")
-    if spatial:
-        # (before any encoder or kernel runs)
-        for k, why in (("images", "it is grounded on a map, not on reference images"), ("input_image", "there is no inpainting form of it"),
-                       ("locations", "it takes no boxes")):
-            if meta.get(k) is not None and (k != "locations" or len(meta[k]) > 0):
-                raise ValueError(f"meta[{k!r}] given to a spatial checkpoint: {why}")
-        if sem and meta.get(SEM_META_KEY) is None:
-            raise ValueError(f"a semantic-map checkpoint needs its class map under the meta key {SEM_META_KEY!r}")
-        if not sem and _spatial_map_of(meta) is None:
-            raise ValueError(f"a spatial checkpoint needs its map under one of the meta keys {SPATIAL_META_KEYS}")
-        model.grounding_extra_of({"grounding_extra_input": True}, tuple(int(v) for v in starting_noise.shape[-2:]))      # the latent-size rule
-    keypoint = getattr(model.cfg, "grounding", "text") == "keypoint"       # the batch builder follows the model, not the checkpoint's file name
-    if keypoint and meta.get("images") is not None:
-        raise ValueError("meta['images'] given to a keypoint checkpoint: it is grounded on poses (meta['locations'] = persons of 17 [x, y])")
-    if keypoint and meta.get("input_image") is not None:
-        raise ValueError("meta['input_image'] given to a keypoint checkpoint: the inpainting mask is drawn from boxes, and poses have none")
-    inpaint_model = bool(getattr(model.cfg, "inpaint_mode", False))
-    if inpaint_model and meta.get("input_image") is None:
+    if fam.extra_key != "sem" and meta.get(SEM_META_KEY) is not None:
+        raise ValueError(f"a semantic map (meta['sem']) given to a {fam.label} checkpoint: class maps need a semantic-map checkpoint "
+                         "(grounding_tokenizer target sem_grounding_net.PositionNet)")
+    if fam.extra_key != "map" and _spatial_map_of(meta) is not None:
+        raise ValueError(f"a grounding map ({[k for k in SPATIAL_META_KEYS if meta.get(k) is not None][0]}) given to a {fam.label} checkpoint: " +
+                         ("it is grounded on a class map under meta['sem']" if fam.extra_key else "maps need a canny / hed / depth / normal checkpoint"))
+    for k, why in fam.refuses:
+        if meta.get(k) is not None and (k != "locations" or len(meta[k]) > 0):
+            raise ValueError(f"meta[{k!r}] given to a {model.cfg.grounding} checkpoint: {why}")
+    if fam.extra_key is not None:
+        _OWN_MAP[fam.extra_key](meta)
+        model.grounding_extra_of({"grounding_extra_input": True}, hw)      # the latent-size rule
+    if model.cfg.inpaint_mode and meta.get("input_image") is None:
         # (the reference would fail inside the first forward, on th.cat([h, None]), openaimodel.py:439)
         raise ValueError("an inpaint_mode checkpoint needs meta['input_image']: its first conv reads the masked image latent and the mask "
                          "(layout-to-image without an input image runs on the 4-channel checkpoints)")
+
+
+def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple):
+    model, autoencoder, text_encoder, diffusion, config = all_models
+    _check_noise(model, starting_noise)
+    fam = family_of(model.cfg)           # the batch builder follows the model, not the checkpoint's file name
+    _refuse_foreign_meta(model, fam, meta, multiple, tuple(int(v) for v in starting_noise.shape[-2:]) if fam.extra_key else None)
     config.update(args)                      # mutates the caller's dict, like interface.py:297/484
     cfg = _AttrDict(config)
     if cfg.get("no_plms", False):
         raise NotImplementedError("the DDIM path is broken in the reference with this UNet (SURVEY App-B#8); PLMS only")
     bs = cfg.batch_size
     max_rel = cfg.get("max_relations", 10)
-    with_rel = bool(getattr(model.cfg, "relation", True))       # a checkpoint without rela_fuse: no scene-graph parse, no relation phrases
+    # (a keypoint model: no phrases, no CLIP model, and -- always on the upstream block -- no relation phrases)
+    batch = fam.build(globals()[fam.batch[multiple]], meta, model.cfg, clip_model, clip_processor, bs, device)
+    prompts = meta["prompts"] if multiple else [meta["prompt"]] * bs
+    context = text_encoder.encode(prompts)
     relations = None
-    if multiple:
-        # (a keypoint model: no phrases, no CLIP model, and -- always on the upstream block -- no relation phrases)
-        batch = prepare_batch_sem(meta, bs, device, model.cfg.sem_classes) if sem else prepare_batch_spatial(meta, bs, device) if spatial else \
-            prepare_batch_kp_multiple(meta, bs, model.cfg.max_persons, device) if keypoint else \
-            prepare_batch_multiple(meta, clip_model, clip_processor, bs, device=device)
-        context = text_encoder.encode(meta["prompts"])
-        if with_rel:
-            relations = prepare_relation_phrases_batch(meta["prompts"], max_rel, text_encoder, device=device)
-    else:
-        batch = prepare_batch_sem(meta, bs, device, model.cfg.sem_classes) if sem else prepare_batch_spatial(meta, bs, device) if spatial else \
-            prepare_batch_kp(meta, bs, model.cfg.max_persons, device) if keypoint else \
-            prepare_batch(meta, clip_model, clip_processor, bs, device=device)
-        context = text_encoder.encode([meta["prompt"]] * bs)
-        if with_rel:
-            relations = prepare_relation_phrases(meta["prompt"], bs, max_rel, text_encoder, device=device)
+    if model.cfg.relation:                   # a checkpoint without rela_fuse: no scene-graph parse, no relation phrases
+        relations = prepare_relation_phrases_batch(meta["prompts"], max_rel, text_encoder, device=device) if multiple else \
+            prepare_relation_phrases(meta["prompt"], bs, max_rel, text_encoder, device=device)
     # the reference encodes bs copies of "" (interface.py:496); args["negative_prompt"] (gligen_inference.py:379-380) replaces it, per call
     neg = args.get("negative_prompt")
     if neg is not None and not isinstance(neg, str):
@@ -725,7 +715,7 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
             img = load_input_image(ims, side, device)
         z0 = autoencoder.encode(img)
         mask = host.draw_masks_from_boxes(batch["boxes"], L).to(starting_noise.device)
-        if inpaint_model:
+        if model.cfg.inpaint_mode:
             # an inpaint_mode checkpoint (gligen_inference.py:406-407): the first conv also reads [z0 * mask | mask]; the sampler keeps
             # replacing the known region as well (:430 passes mask and x0 too).  A 4-channel model runs the latent blend alone.
             extra = build_inpainting_extra(z0, mask)
@@ -733,7 +723,7 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     samples = denoise(all_models, context, uc, relations, batch, starting_noise, meta.get("alpha_type"), cfg.guidance_scale,
                       steps=int(args.get("steps", PLMS_STEPS)), mask=mask, x0=z0,   # steps per call: not sticky through the cached config
                       inpainting_extra_input=extra,
-                      grounding_extra_input=batch["sem" if sem else "map"] if spatial else None)      # *_grounding_downsampler_input.prepare: the map itself
+                      grounding_extra_input=batch[fam.extra_key] if fam.extra_key else None)      # *_grounding_downsampler_input.prepare: the map itself
     return _postprocess(autoencoder.decode(samples))
 
 
@@ -805,20 +795,6 @@ def generate_batch_images_sized(all_models, captions, labels, bboxes, clip_model
 # per-PROMPT seeds make a sample's result independent of the rank that ran it, and the uint8 images are gathered on rank 0.
 # One process per GPU under torch.distributed ("nccl" = RCCL over xGMI on ROCm; "gloo" in the tests).
 # ------------------------------------------------------------------------------------------------------------------
-def _unet_facade(packed, cfg, device, allow_missing_sd_conv=False):
-    from .engine import UNetEngine
-    m = UNetModel.__new__(UNetModel)
-    m.cfg, m.device = cfg, torch.device(device)
-    m.image_size, m.in_channels, m.out_channels, m.model_channels = cfg.image_size, cfg.in_channels, cfg.out_channels, cfg.model_channels
-    m.first_conv_restorable, m.allow_missing_sd_conv, m.first_conv_type = bool(packed.has_sd_conv), bool(allow_missing_sd_conv), "GLIGEN"
-    m.grounding_tokenizer_input = grounding_input_for(cfg)
-    m.fuser_scale, m.training, m._cond_key = 1.0, False, None
-    m.inpaint_mode = bool(getattr(cfg, "inpaint_mode", False))
-    m.engine = UNetEngine(packed)
-    m.strict = False
-    return m
-
-
 def load_all_models_sharded(ckpt, device, src=0, strict=None):
     """``load_all_models`` for a torch.distributed job: only rank ``src`` touches the checkpoint file; the others receive the
     packed UNet (the C engine's flat weight buffer), the packed VAE decoder and -- when the checkpoint's text encoder runs on the HIP
@@ -833,13 +809,13 @@ def load_all_models_sharded(ckpt, device, src=0, strict=None):
     if rank == src:
         am = load_all_models(ckpt, device, strict=strict)
         model, autoencoder, text_encoder, diffusion, config = am
-        if model.cfg.grounding != "text":
+        if family_of(model.cfg).name != "text":
             raise NotImplementedError(f"the sharded entry is text-only: a {model.cfg.grounding} checkpoint runs through load_all_models / "
                                       "run_batch_images")
         if model.cfg.inpaint_mode:
             raise NotImplementedError("the sharded entry has no input image: an inpaint_mode checkpoint runs through load_all_models / "
                                       "run_one_image / run_batch_images with meta['input_image']")
-        if not getattr(model.cfg, "relation", True):
+        if not model.cfg.relation:
             raise NotImplementedError("the sharded entry prepares and scatters relation phrases: a checkpoint without rela_fuse runs through "
                                       "load_all_models / run_one_image / run_batch_images")
         if not isinstance(autoencoder, VAEDecoder):
@@ -851,12 +827,12 @@ def load_all_models_sharded(ckpt, device, src=0, strict=None):
         te_extra = dict(tokenizer=text_encoder.tokenizer, heads=text_encoder.heads, max_length=text_encoder.max_length) if hip_te else None
         broadcast_bundle(model.engine.P, autoencoder.W, model.cfg, device, src,
                          extra=dict(config=config, vcfg=autoencoder.cfg, diffusion=dcfg, text_encoder=te_extra,
-                                    allow_missing_sd_conv=bool(getattr(model, "allow_missing_sd_conv", False)),
-                                    strict=bool(getattr(model, "strict", False))),
+                                    allow_missing_sd_conv=bool(model.allow_missing_sd_conv),
+                                    strict=bool(model.strict)),
                          aux=dict(text_encoder=text_encoder.towers_state_dict()) if hip_te else None)
         return am
     P, vw, extra, aux = broadcast_bundle(None, None, None, device, src, want_aux=True)
-    model = _unet_facade(P, P.cfg, device, extra.get("allow_missing_sd_conv", False))     # src's GLIGEN_ALLOW_NO_SD_CONV applies to every rank
+    model = UNetModel.from_packed(P, P.cfg, device, extra.get("allow_missing_sd_conv", False))     # src's GLIGEN_ALLOW_NO_SD_CONV applies to every rank
     if extra.get("strict"):                 # ... and so does its strict mode (the split weight layout travelled in the broadcast)
         model.set_strict(True)
     autoencoder = VAEDecoder.from_packed(vw, extra["vcfg"], device)

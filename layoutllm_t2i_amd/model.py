@@ -17,6 +17,7 @@ import torch
 from . import host
 from .arch import UNetConfig
 from .engine import UNetEngine
+from .family import FAMILIES, family_of
 from .weights import pack_state_dict
 
 
@@ -55,151 +56,104 @@ class LatentDiffusion:
         return a * x_start + s * noise
 
 
-class GroundingNetInput:
-    """text_layout_tokinzer_input.py:6-62: pass-through of boxes/masks/text embeddings, zeros as null."""
+class _GroundingInput:
+    """The one implementation behind the reference's five ``*_tokinzer_input`` classes: ``prepare`` passes the family's tensors through and
+    notes the payload's batch / device / dtype and the null shapes; ``get_null_input`` is zeros of those.  ``prepare`` also accepts the
+    two-argument call of interface.py:516.  KEYS are the family record's."""
+    KEYS = ()
+    PAYLOAD = ""                # the key whose tensor gives batch, device and dtype
+    NULL_DTYPES = {}            # keys whose null tensor has a dtype of its own
 
     def __init__(self):
         self.set = False
 
+    def _tensors(self, batch, text_encoder):
+        return {k: batch[k] for k in self.KEYS}
+
     def prepare(self, batch, text_encoder=None):
         self.set = True
+        out = self._tensors(batch, text_encoder)
+        payload = out[self.PAYLOAD]
+        self.batch, self.device, self.dtype = payload.shape[0], payload.device, payload.dtype
+        self._null_shapes = self._shapes(out)       # per key, behind the batch axis
+        return out
+
+    def get_null_input(self, batch=None, device=None, dtype=None):
+        assert self.set, "not set yet, cannot call this funcion"
+        batch = self.batch if batch is None else batch
+        device = self.device if device is None else device
+        dtype = self.dtype if dtype is None else dtype
+        return {k: torch.zeros(batch, *shape).type(self.NULL_DTYPES.get(k, dtype)).to(device) for k, shape in self._null_shapes.items()}
+
+
+class GroundingNetInput(_GroundingInput):
+    """text_layout_tokinzer_input.py:6-62: boxes / masks / text embeddings (or ``labels``, encoded token by token) -> ``positive_embeddings``."""
+    KEYS, PAYLOAD = FAMILIES["text"].keys, "positive_embeddings"
+
+    def _tensors(self, batch, text_encoder):
         boxes, masks = batch["boxes"], batch["masks"]
-        self.batch, self.max_box, _ = boxes.shape
-        self.device = boxes.device
-        self.in_dim = 768
         if "text_embeddings" in batch:
             positive_embeddings = batch["text_embeddings"]
         else:
             labels = [s.split("|") for s in batch["labels"]]
             box_list = torch.sum(masks, dim=-1).tolist()
-            positive_embeddings = torch.zeros((self.batch, self.max_box, self.in_dim)).to(self.device)
-            for b in range(self.batch):
+            positive_embeddings = torch.zeros((boxes.shape[0], boxes.shape[1], 768)).to(boxes.device)
+            for b in range(boxes.shape[0]):
                 for i in range(int(box_list[b])):
                     positive_embeddings[b, i] = text_encoder.encode_one_token(labels[b][i])
-        self.dtype = positive_embeddings.dtype
         return {"boxes": boxes, "masks": masks, "positive_embeddings": positive_embeddings}
 
-    def get_null_input(self, batch=None, device=None, dtype=None):
-        assert self.set, "not set yet, cannot call this funcion"
-        batch = self.batch if batch is None else batch
-        device = self.device if device is None else device
-        dtype = self.dtype if dtype is None else dtype
-        boxes = torch.zeros(batch, self.max_box, 4).type(dtype).to(device)
-        masks = torch.zeros(batch, self.max_box).type(dtype).to(device)
-        positive_embeddings = torch.zeros(batch, self.max_box, self.in_dim).type(dtype).to(device)
-        return {"boxes": boxes, "masks": masks, "positive_embeddings": positive_embeddings}
+    def _shapes(self, out):
+        (_, self.max_box, _), self.in_dim = out["boxes"].shape, 768
+        return {"boxes": (self.max_box, 4), "masks": (self.max_box,), "positive_embeddings": (self.max_box, self.in_dim)}
 
 
-class TextImageGroundingNetInput:
-    """text_image_grounding_tokinzer_input.py:5-61: pass-through of the six grounding tensors of a ``*_box_text_image`` checkpoint, zeros
-    as null.  ``prepare`` also accepts the two-argument call of interface.py:516."""
-    KEYS = ("boxes", "masks", "text_masks", "image_masks", "text_embeddings", "image_embeddings")
+class TextImageGroundingNetInput(_GroundingInput):
+    """text_image_grounding_tokinzer_input.py:5-61: the six grounding tensors of a ``*_box_text_image`` checkpoint."""
+    KEYS, PAYLOAD = FAMILIES["text_image"].keys, "text_embeddings"
 
-    def __init__(self):
-        self.set = False
-
-    def prepare(self, batch, text_encoder=None):
-        self.set = True
-        text_embeddings = batch["text_embeddings"]
-        self.batch, self.max_box, self.in_dim = text_embeddings.shape
-        self.device = text_embeddings.device
-        self.dtype = text_embeddings.dtype
-        return {k: batch[k] for k in self.KEYS}
-
-    def get_null_input(self, batch=None, device=None, dtype=None):
-        assert self.set, "not set yet, cannot call this funcion"
-        batch = self.batch if batch is None else batch
-        device = self.device if device is None else device
-        dtype = self.dtype if dtype is None else dtype
-        z = lambda *shape: torch.zeros(*shape).type(dtype).to(device)
-        return {"boxes": z(batch, self.max_box, 4), "masks": z(batch, self.max_box), "text_masks": z(batch, self.max_box),
-                "image_masks": z(batch, self.max_box), "text_embeddings": z(batch, self.max_box, self.in_dim),
-                "image_embeddings": z(batch, self.max_box, self.in_dim)}
+    def _shapes(self, out):
+        _, self.max_box, self.in_dim = out["text_embeddings"].shape
+        return {k: (self.max_box,) + {"boxes": (4,), "text_embeddings": (self.in_dim,), "image_embeddings": (self.in_dim,)}.get(k, ())
+                for k in self.KEYS}
 
 
-class KeypointGroundingNetInput:
-    """keypoint_grounding_tokinzer_input.py:6-44: pass-through of ``points`` [B, 17 P, 2] and ``masks`` [B, 17 P] of a keypoint checkpoint,
-    zeros as null.  ``prepare`` also accepts the two-argument call of interface.py:516."""
-    KEYS = ("points", "masks")
+class KeypointGroundingNetInput(_GroundingInput):
+    """keypoint_grounding_tokinzer_input.py:6-44: ``points`` [B, 17 P, 2] and ``masks`` [B, 17 P] of a keypoint checkpoint."""
+    KEYS, PAYLOAD = FAMILIES["keypoint"].keys, "points"
 
-    def __init__(self):
-        self.set = False
-
-    def prepare(self, batch, text_encoder=None):
-        self.set = True
-        points, masks = batch["points"], batch["masks"]
-        self.batch, tokens, _ = points.shape
-        self.max_persons_per_image = int(tokens / 17)
-        self.device = points.device
-        self.dtype = points.dtype
-        return {"points": points, "masks": masks}
-
-    def get_null_input(self, batch=None, device=None, dtype=None):
-        assert self.set, "not set yet, cannot call this funcion"
-        batch = self.batch if batch is None else batch
-        device = self.device if device is None else device
-        dtype = self.dtype if dtype is None else dtype
-        return {"points": torch.zeros(batch, self.max_persons_per_image * 17, 2).type(dtype).to(device),
-                "masks": torch.zeros(batch, self.max_persons_per_image * 17).type(dtype).to(device)}
+    def _shapes(self, out):
+        self.max_persons_per_image = int(out["points"].shape[1] / 17)
+        return {"points": (self.max_persons_per_image * 17, 2), "masks": (self.max_persons_per_image * 17,)}
 
 
-class SpatialGroundingNetInput:
-    """{canny,hed,depth,normal}_grounding_tokinzer_input.py:6-43 under generic keys: pass-through of ``map`` [B, 3, H, W] in [-1, 1] (the
-    reference's canny_edge / hed_edge / depth / normal) and ``mask`` [B]; the null input is a zero map with a zero mask."""
-    KEYS = ("map", "mask")
+class SpatialGroundingNetInput(_GroundingInput):
+    """{canny,hed,depth,normal}_grounding_tokinzer_input.py:6-43 under generic keys: ``map`` [B, 3, H, W] in [-1, 1] (the reference's
+    canny_edge / hed_edge / depth / normal) and ``mask``; the null input is a zero map with a zero mask [B]."""
+    KEYS, PAYLOAD = FAMILIES["spatial"].keys, "map"
 
-    def __init__(self):
-        self.set = False
-
-    def prepare(self, batch, text_encoder=None):
-        self.set = True
-        map_, mask = batch["map"], batch["mask"]
-        self.batch, self.C, self.H, self.W = map_.shape
-        self.device = map_.device
-        self.dtype = map_.dtype
-        return {"map": map_, "mask": mask}
-
-    def get_null_input(self, batch=None, device=None, dtype=None):
-        assert self.set, "not set yet, cannot call this funcion"
-        batch = self.batch if batch is None else batch
-        device = self.device if device is None else device
-        dtype = self.dtype if dtype is None else dtype
-        return {"map": torch.zeros(batch, self.C, self.H, self.W).type(dtype).to(device), "mask": torch.zeros(batch).type(dtype).to(device)}
+    def _shapes(self, out):
+        _, self.C, self.H, self.W = out["map"].shape
+        return {"map": (self.C, self.H, self.W), "mask": ()}
 
 
-class SemGroundingNetInput:
-    """sem_grounding_tokinzer_input.py:6-43: pass-through of ``sem`` and ``mask`` [B].  ``sem`` is the integer class map [B, H, W] (the native
-    form here) or the reference's float one-hot [B, C, H, W] (semantic.ClassMapInput); the null input is a zero tensor of the same form with
-    a zero mask."""
-    KEYS = ("sem", "mask")
+class SemGroundingNetInput(_GroundingInput):
+    """sem_grounding_tokinzer_input.py:6-43: ``sem``, the integer class map [B, H, W] (the native form here) or the reference's float
+    one-hot [B, C, H, W] (semantic.ClassMapInput), and ``mask``; the null input is a zero tensor of the same form with a float32 zero mask [B]."""
+    KEYS, PAYLOAD, NULL_DTYPES = FAMILIES["sem"].keys, "sem", {"mask": torch.float32}
 
-    def __init__(self):
-        self.set = False
-
-    def prepare(self, batch, text_encoder=None):
-        self.set = True
-        sem, mask = batch["sem"], batch["mask"]
-        self.batch, self.shape = sem.shape[0], tuple(sem.shape[1:])
-        self.device = sem.device
-        self.dtype = sem.dtype
-        return {"sem": sem, "mask": mask}
-
-    def get_null_input(self, batch=None, device=None, dtype=None):
-        assert self.set, "not set yet, cannot call this funcion"
-        batch = self.batch if batch is None else batch
-        device = self.device if device is None else device
-        dtype = self.dtype if dtype is None else dtype
-        return {"sem": torch.zeros(batch, *self.shape).type(dtype).to(device), "mask": torch.zeros(batch).type(torch.float32).to(device)}
+    def _shapes(self, out):
+        self.shape = tuple(out["sem"].shape[1:])
+        return {"sem": self.shape, "mask": ()}
 
 
 _GROUNDING_INPUTS = {"text": GroundingNetInput, "text_image": TextImageGroundingNetInput, "keypoint": KeypointGroundingNetInput,
-                     "spatial": SpatialGroundingNetInput}
+                     "spatial": SpatialGroundingNetInput, "sem": SemGroundingNetInput}
 
 
 def grounding_input_class(cfg: UNetConfig):
-    """the grounding-tokenizer input class that goes with the config's PositionNet (the semantic-map family is a spatial config with its own
-    keys)"""
-    return SemGroundingNetInput if getattr(cfg, "ds_kind", "") == "sem" else _GROUNDING_INPUTS[cfg.grounding]
+    """the grounding-tokenizer input class that goes with the config's PositionNet"""
+    return _GROUNDING_INPUTS[family_of(cfg).name]
 
 
 def grounding_input_for(cfg: UNetConfig):
@@ -214,40 +168,46 @@ class UNetModel:
     switches to, permanently, exactly like the reference (openaimodel.py:393-411).
     """
 
+    # what an instance assembled by hand around an engine (bench.py's facade) leaves unset
+    tokenizer = downsampler = None
+    inpaint_mode = allow_missing_sd_conv = strict = _told_not_restorable = False
+
     def __init__(self, cfg: UNetConfig, state_dict: Mapping[str, object], device="cuda:0",
                  sd_first_conv: Optional[Mapping[str, object]] = None, allow_missing_sd_conv: bool = False):
-        self.cfg = cfg
-        self.device = torch.device(device)
-        self.image_size = cfg.image_size
-        self.in_channels = cfg.in_channels
-        self.out_channels = cfg.out_channels
-        self.model_channels = cfg.model_channels
         if cfg.inpaint_mode and sd_first_conv is not None:
             raise ValueError("an inpaint_mode model has no SD first conv: its 9-channel first conv is not restorable (openaimodel.py:296)")
+        maps = family_of(cfg).extra_key is not None
+        if maps and cfg.split_weights:
+            raise NotImplementedError("strict mode (split_weights) of a spatial model: the ConvNeXt tokenizer has no split-fp16 form")
+        self._assemble(pack_state_dict(state_dict, cfg, torch.device(device), sd_first_conv), cfg, device, allow_missing_sd_conv,
+                       sd_first_conv is not None)
+        if maps:
+            # the two stages in front of the UNet, from the checkpoint's own position_net.* / downsample_net.* tensors
+            from .spatial import map_stages
+            self.tokenizer, self.downsampler = map_stages(state_dict, cfg, self.device)
+
+    @classmethod
+    def from_packed(cls, packed, cfg: UNetConfig, device, allow_missing_sd_conv: bool = False) -> "UNetModel":
+        """A model around already-packed weights (a broadcast pack, another model's): every attribute ``__init__`` sets, the family's
+        grounding input included.  ``packed=None``: no engine, for host-side use of the model's checks."""
+        self = cls.__new__(cls)
+        self._assemble(packed, cfg, device, allow_missing_sd_conv, packed is not None and bool(packed.has_sd_conv))
+        self.grounding_tokenizer_input = grounding_input_for(cfg)
+        return self
+
+    def _assemble(self, packed, cfg, device, allow_missing_sd_conv, restorable):
+        self.cfg = cfg
+        self.device = torch.device(device)
+        self.image_size, self.in_channels, self.out_channels, self.model_channels = cfg.image_size, cfg.in_channels, cfg.out_channels, cfg.model_channels
         self.inpaint_mode = cfg.inpaint_mode
-        self.first_conv_restorable = sd_first_conv is not None
-        self.allow_missing_sd_conv = allow_missing_sd_conv
+        self.first_conv_restorable = restorable
+        self.allow_missing_sd_conv = bool(allow_missing_sd_conv)
         self.first_conv_type = "GLIGEN"
         self.grounding_tokenizer_input: Optional[GroundingNetInput] = None   # set externally (interface.py:370)
         self.fuser_scale = 1.0          # what set_alpha_scale writes (interface.py:34-38)
         self.training = False
-        if cfg.grounding == "spatial" and getattr(cfg, "split_weights", False):
-            raise NotImplementedError("strict mode (split_weights) of a spatial model: the ConvNeXt tokenizer has no split-fp16 form")
-        packed = pack_state_dict(state_dict, cfg, self.device, sd_first_conv)
-        self.engine = UNetEngine(packed)
+        self.engine = UNetEngine(packed) if packed is not None else None
         self.tokenizer = self.downsampler = None
-        if cfg.grounding == "spatial":
-            # the two stages in front of the UNet, from the checkpoint's own position_net.* / downsample_net.* tensors
-            if cfg.ds_kind == "sem":
-                # the semantic-map family: both stages read one class map (a float one-hot is converted once for the two)
-                from .semantic import ClassMapInput, SemDownsampler, SemTokenizer
-                cm = ClassMapInput(cfg.sem_classes, self.device)
-                self.tokenizer = SemTokenizer(state_dict, cfg, self.device, cm)
-                self.downsampler = SemDownsampler(state_dict, cfg, self.device, cm)
-            else:
-                from .spatial import SpatialDownsampler, SpatialTokenizer
-                self.tokenizer = SpatialTokenizer(state_dict, cfg, self.device)
-                self.downsampler = SpatialDownsampler(state_dict, cfg, self.device)
         self._cond_key = None
         self.strict = False
 
@@ -255,7 +215,7 @@ class UNetModel:
         """STRICT mode of the engine (gl_set_handle_option 50; include/gligen_hip.h): every matrix product on split-fp16 operands, output
         within north_star's rtol 1e-3 / atol 1e-4 of the fp32 reference.  Needs weights packed in the split layout
         (``UNetConfig.split_weights``; ``interface.load_ckpt(..., strict=True)`` does both)."""
-        if on and not getattr(self.cfg, "split_weights", False):
+        if on and not self.cfg.split_weights:
             raise RuntimeError("strict mode needs the split weight layout: build the model with dataclasses.replace(cfg, split_weights=True) "
                                "(interface.load_ckpt(..., strict=True) / GLIGEN_STRICT=1 do)")
         self.engine.set_option(50, 1 if on else 0)
@@ -275,15 +235,15 @@ class UNetModel:
         """openaimodel.py:393-408.  The reference's non-restorable branch exists for inpainting models only; for this
         (non-inpainting) UNet a missing SD conv would silently change 35 of 50 steps, so it is an error unless the
         model was built with ``allow_missing_sd_conv=True`` (then the reference's message is printed)."""
-        if getattr(self, "inpaint_mode", False):
+        if self.inpaint_mode:
             # the reference's non-restorable branch (openaimodel.py:406-408): nothing is switched, nothing raises, every step keeps the
             # checkpoint's 9-channel conv (the reference prints its message on every scale-0 step; here once per model)
-            if not getattr(self, "_told_not_restorable", False):
+            if not self._told_not_restorable:
                 print("First conv layer is not restorable and skipped this process, probably because this is an inpainting model?")
                 self._told_not_restorable = True
         elif self.first_conv_restorable:
             self.first_conv_type = "SD"
-        elif getattr(self, "allow_missing_sd_conv", False):
+        elif self.allow_missing_sd_conv:
             print("First conv layer is not restorable and skipped this process, probably because this is an inpainting model?")
         else:
             raise RuntimeError("restore_first_conv_from_SD: the SD first-conv weights (GLIGEN/SD_input_conv_weight_bias.pth) were "
@@ -302,36 +262,65 @@ class UNetModel:
             raise RuntimeError("model.grounding_tokenizer_input is not set (interface.py:370)")
         return self.grounding_tokenizer_input.get_null_input()      # (the family's own keys: grounding_input_for)
 
+    def tokens_of(self, grounding: dict) -> dict:
+        """What the family's engine entry reads of a grounding dict: the dict itself, or -- a map family -- the tokens of its tokenizer.
+        The one check that the family's keys are all there."""
+        fam = family_of(self.cfg)
+        missing = [k for k in fam.keys if k not in grounding]
+        if missing:
+            raise ValueError(f"a {self.cfg.grounding} model needs the grounding keys {fam.keys}; missing {missing}")
+        if fam.extra_key is None:
+            return grounding
+        return {"tokens": self.tokenizer.tokens(grounding[fam.extra_key], grounding["mask"])}
+
     def set_conditioning(self, context, relations, grounding: dict, hw, key=None) -> None:
         """``hw``: the latent side, or (h, w) for a rectangular latent (UNetEngine.set_conditioning).  ``relations``: None on a model without
         the relation chain (a given tensor is ignored there); None on any other model raises ValueError before the engine is touched."""
-        if getattr(self.cfg, "relation", True) and relations is None:
+        if self.cfg.relation and relations is None:
             self.relations_of({})
         if key is not None and key == self._cond_key:
             return
-        if self.cfg.grounding != "text":
-            keys = grounding_input_class(self.cfg).KEYS
-            missing = [k for k in keys if k not in grounding]
-            if missing:
-                raise ValueError(f"a {self.cfg.grounding} model needs the grounding keys {keys}; missing {missing}")
-        if self.cfg.grounding == "spatial":
-            self.engine.set_conditioning_tokens(context, self.tokenizer.tokens(grounding[keys[0]], grounding["mask"]), hw)      # "map" | "sem"
-        elif self.cfg.grounding == "keypoint":
-            self.engine.set_conditioning_kp(context, grounding["points"], grounding["masks"], hw)
-        elif self.cfg.grounding == "text_image":
-            self.engine.set_conditioning(context, relations, grounding["boxes"], grounding["masks"], grounding["text_embeddings"], hw,
-                                         text_masks=grounding["text_masks"], image_masks=grounding["image_masks"],
-                                         image_embeddings=grounding["image_embeddings"])
-        else:
-            self.engine.set_conditioning(context, relations, grounding["boxes"], grounding["masks"],
-                                         grounding["positive_embeddings"], hw)
+        family_of(self.cfg).condition(self.engine, context, relations, self.tokens_of(grounding), hw)
         self._cond_key = key
+
+    def condition(self, input: dict, uc=None, always_extra: bool = False) -> int:
+        """Everything the engine holds per image, from the reference's ``input`` dict: the family's conditioning entry, then the downsampled
+        ``grounding_extra_input`` of a map family and the ``inpainting_extra_input`` of an inpaint_mode model.  Every missing input raises
+        before the engine is touched.  ``uc``: the unconditional context of classifier-free guidance -- the conditioning batch becomes
+        [cond ; uncond] over whatever keys the family has, the unconditional half on the null grounding (a map family: the tokenizer's cached
+        null tokens) and, where there are relations, on the same ones (plms.py:115-124).  ``always_extra``: hand the grounding extra over
+        even while the SD first conv, which does not read it, is switched in (a sampler switches convs between steps).  Returns the batch
+        multiple, 2 with ``uc`` and 1 without."""
+        H, W = (int(v) for v in input["x"].shape[-2:])
+        extra = self.inpaint_extra_of(input)
+        gextra = self.grounding_extra_of(input, (H, W)) if always_extra or not self.use_sd_conv else None
+        rel = self.relations_of(input)
+        g = self.tokens_of(self.grounding_of(input))
+        ctx = input["context"]
+        if uc is not None:
+            if "tokens" in g:
+                null = {"tokens": self.tokenizer.null_tokens().expand(g["tokens"].shape[0], -1, -1)}
+            elif self.grounding_tokenizer_input is None:
+                raise RuntimeError("model.grounding_tokenizer_input is not set (interface.py:370)")
+            else:
+                null = self.grounding_tokenizer_input.get_null_input()
+            f32 = lambda t: t.to(self.device, torch.float32)
+            ctx = torch.cat([f32(ctx), f32(uc)], 0)
+            rel = torch.cat([f32(rel)] * 2, 0) if rel is not None else None
+            g = {k: torch.cat([f32(g[k]), f32(null[k])], 0) for k in null}
+        family_of(self.cfg).condition(self.engine, ctx, rel, g, H if H == W else (H, W))      # (H, W): the rectangular entry and its shape check
+        self._cond_key = None
+        if gextra is not None:
+            self.engine.set_grounding_extra(self.downsampler(gextra))
+        if extra is not None:
+            self.engine.set_inpaint_extra(extra)
+        return 1 if uc is None else 2
 
     def relations_of(self, input: dict):
         """``input["relations"]``: required on a model with the rela_fuse chain (ValueError before any kernel runs); a model loaded from a
         checkpoint without it (``cfg.relation`` False, the upstream GLIGEN block) takes no relations -- the upstream ``input`` dict has no such
         key -- and ignores a given tensor."""
-        if not getattr(self.cfg, "relation", True):
+        if not self.cfg.relation:
             return None
         rel = input.get("relations")
         if rel is None:
@@ -342,7 +331,7 @@ class UNetModel:
     def inpaint_extra_of(self, input: dict) -> Optional[torch.Tensor]:
         """``input["inpainting_extra_input"]`` (openaimodel.py:436-439): required on an inpaint_mode model, ignored on every other (as the
         reference ignores it)."""
-        if not getattr(self, "inpaint_mode", False):
+        if not self.inpaint_mode:
             return None
         extra = input.get("inpainting_extra_input")
         if extra is None:
@@ -354,7 +343,7 @@ class UNetModel:
         """``input["grounding_extra_input"]`` (openaimodel_original.py:430-432): the map [B, 3, H, W] the grounding downsampler of a spatial
         model reads; required there (ValueError before any kernel runs), ignored on every other model, as the reference ignores it.  ``hw``:
         the latent's (h, w), which has to be the downsampler's output size (the reference fails inside th.cat otherwise)."""
-        if getattr(self, "downsampler", None) is None:
+        if self.downsampler is None:
             return None
         extra = input.get("grounding_extra_input")
         if extra is None:
@@ -369,24 +358,9 @@ class UNetModel:
     @torch.no_grad()
     def __call__(self, input: dict) -> torch.Tensor:
         """UNetModel.forward (openaimodel.py:413-459): one B-sized evaluation."""
-        x = input["x"]
-        if getattr(self, "downsampler", None) is not None:
-            gextra = None if self.use_sd_conv else self.grounding_extra_of(input, tuple(int(v) for v in x.shape[-2:]))
-            H, W = (int(v) for v in x.shape[-2:])
-            self.set_conditioning(input["context"], None, self.grounding_of(input), H if H == W else (H, W), key=None)
-            if gextra is not None:
-                self.engine.set_grounding_extra(self.downsampler(gextra))
-            return self.engine.forward(x.to(self.device, torch.float32).contiguous(), input["timesteps"], self.fuser_scale, self.use_sd_conv,
-                                       1).clone()
-        extra = self.inpaint_extra_of(input)
-        rel = self.relations_of(input)
-        g = self.grounding_of(input)
-        H, W = (int(v) for v in x.shape[-2:])
-        self.set_conditioning(input["context"], rel, g, H if H == W else (H, W), key=None)
-        if extra is not None:
-            self.engine.set_inpaint_extra(extra)
-        t = input["timesteps"]
-        return self.engine.forward(x.to(self.device, torch.float32).contiguous(), t, self.fuser_scale, self.use_sd_conv, 1).clone()
+        self.condition(input)
+        return self.engine.forward(input["x"].to(self.device, torch.float32).contiguous(), input["timesteps"], self.fuser_scale, self.use_sd_conv,
+                                   1).clone()
 
     forward = __call__
 

@@ -19,6 +19,7 @@ from typing import Dict, Tuple
 
 import numpy as np
 
+from .family import family_of
 from .arch import UNetConfig, VAEConfig, param_shapes, vae_decoder_param_shapes, vae_encoder_param_shapes
 
 
@@ -120,7 +121,7 @@ def synth_inputs(cfg: UNetConfig, batch: int, hw, n_boxes: int = 8, n_rel: int =
     """
     mo = cfg.max_objs
     lh, lw = (hw, hw) if isinstance(hw, int) else (int(v) for v in hw)
-    if getattr(cfg, "grounding", "text") == "keypoint":
+    if "points" in family_of(cfg).keys:
         return synth_inputs_kp(cfg, batch, (lh, lw), seed=seed)
     x = normal("in.x", (batch, cfg.in_channels, lh, lw), seed)
     context = normal("in.context", (batch, 77, cfg.context_dim), seed)
@@ -141,7 +142,7 @@ def synth_inputs(cfg: UNetConfig, batch: int, hw, n_boxes: int = 8, n_rel: int =
                 bx[b, i] = (g[0] + s, g[1] + s, g[2] - s, g[3] - s)
         masks[b, :n_boxes] = 1.0
     emb[:, :n_boxes] = normal("in.text_embeddings", (batch, n_boxes, cfg.pos_in_dim), seed)
-    if getattr(cfg, "grounding", "text") == "text_image":
+    if family_of(cfg).images:
         # the six grounding tensors of a text_image checkpoint (text_image_grounding_net.py:41): box i of sample b is grounded on a phrase,
         # on a reference image, or on both, in rotation (text only, image only, both), so every blend of the PositionNet is exercised
         iemb = np.zeros((batch, mo, cfg.pos_in_dim), np.float32)

@@ -13,10 +13,8 @@ switch on every scale-0 step, step-0 double evaluation, Adams-Bashforth history 
   * the schedule tables are computed once per S;
   * an inpaint_mode model's ``input["inpainting_extra_input"]`` (the same tensor for the cond and the uncond pass, plms.py:118-121) is handed
     to the engine once per ``sample()``, not per step;
-  * a spatial model (canny / hed / depth / normal) takes ``input["grounding_extra_input"]`` (required there, ValueError before any kernel runs;
-    every other model ignores it): its ConvNeXt tokenizer runs once per ``sample()`` on the conditional maps, the unconditional half takes
-    the model's cached null tokens, and both halves read the same downsampled extra (plms.py:118-121), handed to the engine once; a
-    semantic-map model reads its class map (or the reference's float one-hot, converted once) under the key ``sem`` where the others read ``map``;
+  * a map model (canny / hed / depth / normal, sem) takes ``input["grounding_extra_input"]`` (required there, ignored elsewhere): its tokenizer
+    runs once per ``sample()``, the unconditional half takes the cached null tokens, both halves read the same extra (UNetModel.condition);
   * inpainting (``mask`` / ``x0``, plms.py:95-99): each step first replaces the known region,
     x = q_sample(x0, t) * mask + (1 - mask) * x, as one fused in-place fp32 HIP kernel (gl_latent_blend, bit-identical to
     the torch expression), with the q_sample noise drawn by ``torch.randn_like(x0)`` before the step's own draws.
@@ -78,7 +76,6 @@ class PLMSSampler(object):
             img = torch.randn(shape, device=dev)
             input["x"] = img
         x = img.to(dev, torch.float32).contiguous().clone()
-        H, W = (int(v) for v in x.shape[-2:])
         n = x.numel()
 
         time_range = np.flip(self.ddim_timesteps)
@@ -86,46 +83,8 @@ class PLMSSampler(object):
         alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
 
         # ---- conditioning, once per image: [cond ; uncond] when CFG is active (plms.py:115-124)
-        extra = model.inpaint_extra_of(input)      # raises on an inpaint_mode model without the extra, before any kernel runs
-        spatial = getattr(model, "downsampler", None) is not None
-        gextra = model.grounding_extra_of(input, (H, W)) if spatial else None      # likewise, on a spatial model; every other model ignores it
-        rel_in = model.relations_of(input)         # None on a model without the relation chain; raises where the chain needs them
-        cfg_on = uc is not None and guidance_scale != 1
-        g = model.grounding_of(input)
-        f32 = lambda t: t.to(dev, torch.float32)
-        if spatial:
-            # the ConvNeXt tokenizer once per sample() on the conditional maps; the unconditional half takes the model's cached null tokens
-            # (a zero map with mask 0: linears(null_feature + pos_embedding) whatever the image) and the SAME downsampled extra (plms.py:118-121)
-            from .model import grounding_input_class
-            keys = grounding_input_class(model.cfg).KEYS      # ("map", "mask"); ("sem", "mask") on a semantic-map model
-            missing = [k for k in keys if k not in g]
-            if missing:
-                raise ValueError(f"a spatial model needs the grounding keys {keys}; missing {missing}")
-            objs = model.tokenizer.tokens(g[keys[0]], g["mask"])
-            ctx = f32(input["context"])
-            if cfg_on:
-                objs = torch.cat([objs, model.tokenizer.null_tokens().expand(objs.shape[0], -1, -1)], 0)
-                ctx = torch.cat([ctx, f32(uc)], 0)
-            reps = 2 if cfg_on else 1
-            eng.set_conditioning_tokens(ctx, objs, H if H == W else (H, W))
-            model._cond_key = None
-            eng.set_grounding_extra(model.downsampler(gextra))
-        elif cfg_on:
-            if model.grounding_tokenizer_input is None:
-                raise RuntimeError("model.grounding_tokenizer_input is not set (interface.py:370)")
-            gn = model.grounding_tokenizer_input.get_null_input()
-            ctx = torch.cat([f32(input["context"]), f32(uc)], 0)
-            rel = torch.cat([f32(rel_in)] * 2, 0) if rel_in is not None else None
-            grounding = {k: torch.cat([f32(g[k]), f32(gn[k])], 0) for k in gn}      # whatever keys the grounding tokenizer input has (3 for text, 6 for text_image)
-            reps = 2
-        else:
-            ctx, rel = f32(input["context"]), (f32(rel_in) if rel_in is not None else None)
-            grounding = {k: f32(v) for k, v in g.items() if torch.is_tensor(v)}
-            reps = 1
-        if not spatial:
-            model.set_conditioning(ctx, rel, grounding, H if H == W else (H, W), key=None)      # (H, W): the rectangular entry and its shape check
-        if extra is not None:
-            eng.set_inpaint_extra(extra)
+        # every missing input raises before any kernel runs; the grounding extra of a map family is handed over whatever conv is switched in
+        reps = model.condition(input, uc if uc is not None and guidance_scale != 1 else None, always_extra=True)
 
         ring = [eng.buf(f"plms.e{j}", tuple(x.shape), torch.float32) for j in range(4)]
         x_a = eng.buf("plms.x", tuple(x.shape), torch.float32)    # running latent (the engine copies it per forward)

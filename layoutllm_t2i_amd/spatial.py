@@ -281,3 +281,13 @@ class SpatialDownsampler:
                 return r
             h = ops.sp_conv4x4s2(r, self.w["layers.0.weight"], self.w["layers.0.bias"], True, e(B, 4, R // 2, R // 2))
             return ops.sp_conv4x4s2(h, self.w["layers.2.weight"], self.w["layers.2.bias"], False, e(B, cfg.ds_out, R // 4, R // 4))
+
+
+def map_stages(state_dict, cfg: UNetConfig, device):
+    """(tokenizer, downsampler) of a map family, the two stages in front of the UNet.  The semantic-map family's both read one class map (a
+    float one-hot is converted once for the two)."""
+    if cfg.ds_kind == "sem":
+        from .semantic import ClassMapInput, SemDownsampler, SemTokenizer
+        cm = ClassMapInput(cfg.sem_classes, device)
+        return SemTokenizer(state_dict, cfg, device, cm), SemDownsampler(state_dict, cfg, device, cm)
+    return SpatialTokenizer(state_dict, cfg, device), SpatialDownsampler(state_dict, cfg, device)

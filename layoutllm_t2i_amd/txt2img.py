@@ -22,10 +22,11 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from . import interface
+from .family import FAMILIES, family_of
 from .policy import CandidatePool, PolicyNetwork, embed_texts
 from .prompting import build_prompt, convert_xcycwh_to_ltrb, convert_xywh_to_ltrb, extract_prediction
 
-BOX_FAMILIES = ("text", "text_image")
+BOX_FAMILIES = tuple(f.name for f in FAMILIES.values() if f.boxes)
 
 
 def _save(images, folder: str, prompt: str, locations, phrases, draw_boxes: bool) -> None:
@@ -57,9 +58,8 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
     layout drawn on the saved copies).  ``instruction``: the wording of the LLM prompt (prompting.build_prompt).
     Returns dict(images, categories, bboxes_ltrb, cids, prompt_text, llm_output)."""
     model = all_models[0]
-    family = getattr(model.cfg, "grounding", "text")
-    if family not in BOX_FAMILIES:
-        raise ValueError(f"the prompt-to-image entry generates from boxes: a {family} checkpoint cannot run it "
+    if not family_of(model.cfg).boxes:
+        raise ValueError(f"the prompt-to-image entry generates from boxes: a {model.cfg.grounding} checkpoint cannot run it "
                          f"(box-grounded families: {BOX_FAMILIES})")
     if num_per_prompt < 1 or batch_size < 1:
         raise ValueError(f"num_per_prompt = {num_per_prompt}, batch_size = {batch_size}: both must be >= 1")

@@ -81,7 +81,7 @@ UPFOLD_MIN_CHANNELS = 512
 
 def fold_up_rule(cfg: UNetConfig) -> bool:
     ups = [l.cin for l in build_plan(cfg).all_layers() if l.kind == "up"]
-    return bool(ups) and min(ups) >= UPFOLD_MIN_CHANNELS and not getattr(cfg, "split_weights", False)
+    return bool(ups) and min(ups) >= UPFOLD_MIN_CHANNELS and not cfg.split_weights
 
 
 def pack_conv_upfold(w32: torch.Tensor) -> torch.Tensor:
@@ -215,13 +215,13 @@ def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_
     for k, shp in need.items():
         if tuple(sd[k].shape) != tuple(shp):
             raise ValueError(f"{k}: shape {tuple(sd[k].shape)} != expected {shp}")
-    if sd_first_conv is not None and getattr(cfg, "inpaint_mode", False):
+    if sd_first_conv is not None and cfg.inpaint_mode:
         # openaimodel.py:296: first_conv_restorable = False -- the 4-channel SD conv cannot take the 9-channel input
         raise ValueError("an inpaint_mode model has no SD first conv (its first conv is not restorable, openaimodel.py:296)")
     P = PackedWeights(cfg, plan, device)
     W, S = P.w, P.s
     g = lambda k: _t(sd[k], device)
-    split_all = bool(getattr(cfg, "split_weights", False))
+    split_all = bool(cfg.split_weights)
     from . import _lib
     P.fold_up = _lib.resolve_fold_up(fold_up, fold_up_rule(cfg))
     fold = P.fold_up and not split_all
@@ -323,7 +323,7 @@ def pack_state_dict(sd: Mapping[str, object], cfg: UNetConfig, device, sd_first_
             norm(f + ".norm2")
             S[f + ".tanh_attn"] = math.tanh(float(g(f + ".alpha_attn")))
             S[f + ".tanh_dense"] = math.tanh(float(g(f + ".alpha_dense")))
-            if not getattr(cfg, "relation", True):
+            if not cfg.relation:
                 continue                                # the upstream block (attention_original.py:312-316): no rela_fuse entries in the table either
             r = t + ".rela_fuse"
             cross_attn(r + ".attn", l.d_head)

@@ -16,9 +16,8 @@ import torch.distributed as dist
 from layoutllm_t2i_amd import recipe
 from layoutllm_t2i_amd.arch import TINY
 from layoutllm_t2i_amd.dist import broadcast_packed, checksum, shard_indices
-from layoutllm_t2i_amd.engine import UNetEngine
 from layoutllm_t2i_amd.interface import denoise
-from layoutllm_t2i_amd.model import GroundingNetInput, LatentDiffusion, UNetModel
+from layoutllm_t2i_amd.model import LatentDiffusion, UNetModel
 from layoutllm_t2i_amd.weights import pack_state_dict
 
 N_PROMPTS, HW, STEPS = 6, 16, 6
@@ -39,14 +38,7 @@ def run_shard(model, indices, dev):
 
 
 def model_from_packed(P, dev):
-    m = UNetModel.__new__(UNetModel)
-    m.cfg, m.device = TINY, torch.device(dev)
-    m.image_size, m.in_channels, m.out_channels, m.model_channels = TINY.image_size, TINY.in_channels, TINY.out_channels, TINY.model_channels
-    m.first_conv_restorable, m.first_conv_type, m.allow_missing_sd_conv = True, "GLIGEN", False
-    m.grounding_tokenizer_input = GroundingNetInput()
-    m.fuser_scale, m.training, m._cond_key = 1.0, False, None
-    m.engine = UNetEngine(P)
-    return m
+    return UNetModel.from_packed(P, TINY, dev)
 
 
 def main():

@@ -1,6 +1,7 @@
 """The prompt-to-image entry EXECUTED (txt2img.generate, the reference's txt2img.py:460-508) on the synthetic tiny checkpoint and the
 stubs of test_boundary.py (16 x 16 latent, 4 PLMS steps): a toy CLIP text tower embeds the pool and the prompt, the policy kernel
 selects, a stub ``llm`` answers with a canned layout, and the images must be the ones ``run_one_image`` makes from that layout."""
+import dataclasses
 import os
 import sys
 import types
@@ -135,7 +136,7 @@ def test_generate_refuses_a_model_that_is_not_box_grounded_before_the_llm_is_cal
     llm = StubLLM(ANSWER)
     pool = CandidatePool(EXAMPLES, torch.zeros(6, 768))
     for family in ("keypoint", "spatial"):
-        am = (types.SimpleNamespace(cfg=types.SimpleNamespace(grounding=family)), None, None, None, {})
+        am = (types.SimpleNamespace(cfg=dataclasses.replace(TINY, grounding=family)), None, None, None, {})
         with pytest.raises(ValueError, match=family):
             txt2img.generate(am, PolicyNetwork(device="cpu"), pool, PROMPT, llm, tokenize)
     assert llm.seen == []

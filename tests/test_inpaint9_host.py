@@ -227,9 +227,7 @@ class _M:
 
 
 def _bare_model(cfg):
-    m = UNetModel.__new__(UNetModel)
-    m.cfg, m.inpaint_mode, m.first_conv_restorable, m.allow_missing_sd_conv, m.first_conv_type = cfg, cfg.inpaint_mode, False, False, "GLIGEN"
-    return m
+    return UNetModel.from_packed(None, cfg, "cpu")
 
 
 def test_missing_extra_names_the_key():

@@ -246,8 +246,8 @@ class _Engine:
 
 
 def test_model_dispatches_on_the_family():
-    m = UNetModel.__new__(UNetModel)
-    m.cfg, m.engine, m._cond_key, m.grounding_tokenizer_input = kc.KP_TINY[3], _Engine(), None, None
+    m = UNetModel.from_packed(None, kc.KP_TINY[3], "cpu")
+    m.engine, m.grounding_tokenizer_input = _Engine(), None
     pts, msk = torch.zeros(2, 51, 2), torch.zeros(2, 51)
     m.set_conditioning(torch.zeros(2, 77, 768), None, {"points": pts, "masks": msk}, (16, 24))
     assert m.engine.calls == [("kp", (2, 51, 2), (2, 51), (16, 24))]

@@ -19,7 +19,7 @@ from layoutllm_t2i_amd import gligen_inference as gi
 from layoutllm_t2i_amd import interface as itf
 from layoutllm_t2i_amd.arch import TINY, VAE_TINY, UNetConfig
 from layoutllm_t2i_amd.engine import UNetEngine
-from layoutllm_t2i_amd.model import GroundingNetInput, LatentDiffusion, UNetModel
+from layoutllm_t2i_amd.model import LatentDiffusion, UNetModel
 from layoutllm_t2i_amd.sampler import PLMSSampler
 from oracle import plms_ref
 
@@ -276,10 +276,7 @@ class _Untouchable:
 
 
 def _bare_model(cfg):
-    m = UNetModel.__new__(UNetModel)
-    m.cfg, m.inpaint_mode, m.first_conv_restorable, m.allow_missing_sd_conv, m.first_conv_type = cfg, cfg.inpaint_mode, False, False, "GLIGEN"
-    m.device, m.fuser_scale, m._cond_key = torch.device("cpu"), 1.0, None
-    m.grounding_tokenizer_input = GroundingNetInput()
+    m = UNetModel.from_packed(None, cfg, "cpu")
     m.engine = _Untouchable()
     return m
 

@@ -263,8 +263,8 @@ def test_spatial_grounding_net_input_round_trip():
 
 
 def test_model_refusals_without_a_device():
-    m = UNetModel.__new__(UNetModel)
-    m.cfg, m.downsampler, m.tokenizer = sc.CANNY_TINY, object(), None
+    m = UNetModel.from_packed(None, sc.CANNY_TINY, "cpu")
+    m.downsampler = object()
     with pytest.raises(ValueError, match="grounding_extra_input"):
         m.grounding_extra_of({})
     with pytest.raises(ValueError, match="16 x 16"):
