@@ -351,6 +351,15 @@ int gl_cfg_combine(const float* eps2b, float guidance, int64_t n, float* e_out, 
 int gl_plms_update(const float* x, const float* e, const float* e1, const float* e2, const float* e3,
                    float c0, float c1, float c2, float c3, float div, float sqrt_at, float s1m,
                    float sqrt_aprev, float dir_coef, int64_t n, float* x_prev, void* stream);
+/* gl_ddim_update: everything of one DDIM step behind the UNet (ddim.py:115-135) in ONE launch, additive to ABI 15.  eps = the UNet output
+ * fp32 [reps * n]: reps == 2 = the [cond ; uncond] batch, e = e_u + guidance * (e_c - e_u) (ddim.py:118); reps == 1: e = eps, guidance is
+ * not read.  Then pred_x0 = (x - s1m * e) / sqrt_at (:128) and x_out = (sqrt_aprev * pred_x0 + dir_coef * e) + sigma * noise (:131-133, left
+ * to right), in the reference's operation order with FP contraction off: given the same eps, bit-identical to the torch fp32 expression.
+ * noise fp32 [n], or NULL = the reference's 0 * randn: the term is skipped (for finite values the bits of adding the zero), sigma is not
+ * read.  pred_x0 fp32 [n] receives the x0 prediction, or NULL.  x_out may be x (the normal use), pred_x0 may be any operand: every element
+ * is read before the same element is written.  n % 4 == 0 and 16-byte pointers take the float4 path, everything else the scalar one. */
+int gl_ddim_update(const float* eps, const float* x, const float* noise, int32_t reps, float guidance, float sqrt_at, float s1m,
+                   float sqrt_aprev, float dir_coef, float sigma, int64_t n, float* x_out, float* pred_x0, void* stream);
 int gl_pack_latent(const float* x, int32_t B, int32_t C, int32_t hw, int32_t Cpad, int32_t reps, int32_t split, void* out,
                    void* stream);
 /* gl_pack_latent_extra: gl_pack_latent over the channel concatenation of TWO sources (the first-conv input of an inpaint_mode UNet,
@@ -545,6 +554,20 @@ typedef struct gl_plms_step_args {
     int32_t use_graph;
 } gl_plms_step_args;
 int gl_plms_step(gl_engine* e, const gl_plms_step_args* a, void* stream);
+/* gl_ddim_step: one denoiser evaluation + one gl_ddim_update launch (ddim.py:111-135), additive to ABI 15: eps = UNet(x, t) into the handle's
+ * own output buffer (graph-cached like gl_unet_forward), then x_out / pred_x0 from (eps, x, noise) as gl_ddim_update describes -- the CFG
+ * combine is part of that launch, there is no guided-eps buffer.  x fp32 [Bn / reps, C, h, w]; x_out may be x; noise and pred_x0 may be
+ * NULL.  Refuses what gl_plms_step refuses: NULL x / x_out, reps other than 1 or 2 (GL_ERR_BAD_ARG), in_channels != out_channels
+ * (GL_ERR_UNSUPPORTED), and everything gl_unet_forward refuses. */
+typedef struct gl_ddim_step_args {
+    const float* x;  float* x_out;                                   /* fp32 [B, C, h, w] */
+    const float* noise;  float* pred_x0;                             /* fp32 [B, C, h, w] or NULL */
+    float t;  int32_t reps;  float guidance;  float fuser_scale;  int32_t sd_conv;
+    float sqrt_at, s1m, sqrt_aprev, dir_coef, sigma;
+    int32_t use_graph;
+} gl_ddim_step_args;
+int gl_ddim_step(gl_engine* e, const gl_ddim_step_args* a, void* stream);
+int gl_sizeof_ddim_step_args(void);
 /* introspection for tests / tools */
 int64_t gl_pool_bytes(const gl_engine* e);
 int gl_num_launches(const gl_engine* e);       /* kernel launches of the last eagerly executed / captured forward */

@@ -247,6 +247,55 @@ __global__ __launch_bounds__(256) void latent_blend_kernel(float* x, const float
         else x[i] = o[0];
     }
 }
+
+// One DDIM step behind the UNet (ddim.py:115-135) as ONE launch: the CFG combine of the [cond ; uncond] output (reps == 2), pred_x0 and
+// x_prev, in the reference's operation order: e = e_u + g * (e_c - e_u); pred_x0 = (x - s1m * e) / sqrt_at;
+// x_prev = (sqrt_aprev * pred_x0 + dir_coef * e) + sigma * noise.  noise == NULL (the reference's 0 * randn): the last term is SKIPPED, which
+// gives the bits of adding the zero for every finite value.  No __restrict__ on x / x_out / pred_x0: the update runs in place; every thread
+// reads all of its operands before it stores.  VEC = 4: n % 4 == 0 and 16-byte pointers, one float4 per operand per thread.
+template <int VEC>
+__global__ __launch_bounds__(256) void ddim_update_kernel(const float* eps, const float* x, const float* noise, int reps, float guidance,
+                                                          float sqrt_at, float s1m, float sqrt_aprev, float dir_coef, float sigma, size_t n,
+                                                          float* x_out, float* pred_out) {
+    const size_t nvec = n / VEC;
+    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = v * VEC;
+        float ec[VEC], eu[VEC], xv[VEC], nv[VEC];
+        if constexpr (VEC == 4) {
+            const float4 tc = *reinterpret_cast<const float4*>(eps + i), tx = *reinterpret_cast<const float4*>(x + i);
+            ec[0] = tc.x; ec[1] = tc.y; ec[2] = tc.z; ec[3] = tc.w;
+            xv[0] = tx.x; xv[1] = tx.y; xv[2] = tx.z; xv[3] = tx.w;
+            if (reps == 2) {
+                const float4 tu = *reinterpret_cast<const float4*>(eps + n + i);
+                eu[0] = tu.x; eu[1] = tu.y; eu[2] = tu.z; eu[3] = tu.w;
+            }
+            if (noise) {
+                const float4 tn = *reinterpret_cast<const float4*>(noise + i);
+                nv[0] = tn.x; nv[1] = tn.y; nv[2] = tn.z; nv[3] = tn.w;
+            }
+        } else {
+            ec[0] = eps[i]; xv[0] = x[i];
+            if (reps == 2) eu[0] = eps[n + i];
+            if (noise) nv[0] = noise[i];
+        }
+        float o[VEC], p[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            const float e = reps == 2 ? eu[j] + guidance * (ec[j] - eu[j]) : ec[j];
+            p[j] = (xv[j] - s1m * e) / sqrt_at;
+            const float dir_xt = dir_coef * e;
+            o[j] = sqrt_aprev * p[j] + dir_xt;
+            if (noise) o[j] = o[j] + sigma * nv[j];
+        }
+        if constexpr (VEC == 4) {
+            *reinterpret_cast<float4*>(x_out + i) = make_float4(o[0], o[1], o[2], o[3]);
+            if (pred_out) *reinterpret_cast<float4*>(pred_out + i) = make_float4(p[0], p[1], p[2], p[3]);
+        } else {
+            x_out[i] = o[0];
+            if (pred_out) pred_out[i] = p[0];
+        }
+    }
+}
 #pragma clang fp contract(fast)
 
 // DiagonalGaussianDistribution(quant_conv(h)).sample() * scale_factor (autoencoder.py:34-38, distributions.py:24-36) per pixel:
@@ -510,6 +559,21 @@ extern "C" int gl_plms_update(const float* x, const float* e, const float* e1, c
     if (!x || !e || !x_prev || n <= 0) return GL_ERR_BAD_ARG;
     plms_update_kernel<<<dim3(ew_blocks((size_t)n)), dim3(256), 0, (hipStream_t)stream>>>(
         x, e, e1, e2, e3, c0, c1, c2, c3, div, sqrt_at, s1m, sqrt_aprev, dir_coef, (size_t)n, x_prev);
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_ddim_update(const float* eps, const float* x, const float* noise, int32_t reps, float guidance, float sqrt_at, float s1m,
+                              float sqrt_aprev, float dir_coef, float sigma, int64_t n, float* x_out, float* pred_x0, void* stream) {
+    if (!eps || !x || !x_out || n <= 0 || (reps != 1 && reps != 2)) return GL_ERR_BAD_ARG;
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(noise) |
+                           reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(pred_x0);
+    if ((n % 4) == 0 && (ptrs % 16) == 0)
+        ddim_update_kernel<4><<<dim3(ew_blocks((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream>>>(
+            eps, x, noise, reps, guidance, sqrt_at, s1m, sqrt_aprev, dir_coef, sigma, (size_t)n, x_out, pred_x0);
+    else
+        ddim_update_kernel<1><<<dim3(ew_blocks((size_t)n)), dim3(256), 0, (hipStream_t)stream>>>(
+            eps, x, noise, reps, guidance, sqrt_at, s1m, sqrt_aprev, dir_coef, sigma, (size_t)n, x_out, pred_x0);
     GL_CHECK_LAUNCH();
     return 0;
 }

@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import PlmsStepArgs, check, init_device
+from ._lib import DdimStepArgs, PlmsStepArgs, check, init_device
 from .arch import UNetConfig
 from .weights import PackedWeights
 
@@ -323,4 +323,28 @@ class UNetEngine:
             raise RuntimeError("SD first-conv weights were not packed")
         with torch.cuda.device(self.dev):
             self._check(self._lib.gl_plms_step(self.handle, C.byref(a), self._stream()), "gl_plms_step")
+        return x_out
+
+    @torch.no_grad()
+    def ddim_step(self, x: torch.Tensor, x_out: torch.Tensor, *, t: float, reps: int, guidance: float, fuser_scale: float, sd_conv: bool,
+                  sqrt_at: float, s1m: float, sqrt_aprev: float, dir_coef: float, sigma: float = 0.0, noise: Optional[torch.Tensor] = None,
+                  pred_x0: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One gl_ddim_step: UNet(x, t) into the engine's own eps buffer, then ONE launch for the CFG combine, pred_x0 and
+        x_out = sqrt_aprev * pred_x0 + dir_coef * e + sigma * noise (ddim.py:111-135).  ``x_out`` may be ``x``; ``noise`` None = the
+        reference's ``0 * randn`` (skipped); ``pred_x0`` optionally receives the x0 prediction."""
+        self._check_x(x, reps)
+        for tns, name in ((x_out, "x_out"), (noise, "noise"), (pred_x0, "pred_x0")):
+            if tns is not None and (not tns.is_cuda or tns.dtype != F32 or not tns.is_contiguous() or tns.shape != x.shape):
+                raise _lib.HipLibraryError(f"{name}: need a contiguous fp32 GPU tensor of the latent's shape")
+        if sd_conv and not self.P.has_sd_conv:
+            raise RuntimeError("SD first-conv weights were not packed")
+        a = DdimStepArgs()
+        a.x, a.x_out = x.data_ptr(), x_out.data_ptr()
+        a.noise = None if noise is None else noise.data_ptr()
+        a.pred_x0 = None if pred_x0 is None else pred_x0.data_ptr()
+        a.t, a.reps, a.guidance, a.fuser_scale, a.sd_conv = float(t), int(reps), float(guidance), float(fuser_scale), int(bool(sd_conv))
+        a.sqrt_at, a.s1m, a.sqrt_aprev, a.dir_coef, a.sigma = float(sqrt_at), float(s1m), float(sqrt_aprev), float(dir_coef), float(sigma)
+        a.use_graph = int(self.use_graphs)
+        with torch.cuda.device(self.dev):
+            self._check(self._lib.gl_ddim_step(self.handle, C.byref(a), self._stream()), "gl_ddim_step")
         return x_out

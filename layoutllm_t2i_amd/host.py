@@ -1,5 +1,5 @@
 """Host-side (CPU, once per image) pieces of the denoising path: integer box rectangles for the
-relation injection, the alpha (fuser-scale) schedule and the PLMS schedule tables.
+relation injection, the alpha (fuser-scale) schedule and the PLMS / DDIM schedule tables.
 
 Everything here is tiny scalar/table work that the reference redoes inside its hot loop
 (attention.py:321-346 with 4 ``.tolist()`` device syncs per call x 16 layers x 102 forwards;
@@ -100,6 +100,53 @@ def step_coefs(sched: Dict[str, np.ndarray], index: int) -> Tuple[float, float, 
     a_prev = np.float32(sched["ddim_alphas_prev"][index])
     s1m = np.float32(sched["ddim_sqrt_one_minus_alphas"][index])
     return (float(np.sqrt(a_t)), float(s1m), float(np.sqrt(a_prev)), float(np.sqrt(np.float32(1.0) - a_prev)))
+
+
+DDIM_DISCRETIZE = ("uniform", "quad")
+
+
+def check_ddim_eta(eta) -> float:
+    """eta of the DDIM variance schedule: a finite number >= 0, else ValueError"""
+    if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or not np.isfinite(eta) or eta < 0:
+        raise ValueError(f"ddim_eta = {eta!r}: must be a finite number >= 0")
+    return float(eta)
+
+
+def make_ddim_schedule(S: int, acp: np.ndarray, discretize: str = "uniform", eta: float = 0.0) -> Dict[str, np.ndarray]:
+    """DDIMSampler.make_schedule (ddim.py:27-50): make_ddim_timesteps (util.py:55-69) and make_ddim_sampling_parameters (util.py:72-83) in the
+    reference's dtypes.  ``acp``: the float32 alphas_cumprod buffer.
+
+    ddim_timesteps int64: 'uniform' = range(0, T, T // S) + 1 (S = 6 gives 7 of them), 'quad' = int(linspace(0, sqrt(0.8 T), S) ** 2) + 1
+    (neighbours may coincide).  ddim_alphas float32 = acp[t]; ddim_alphas_prev float64 = [acp[0], acp[t[:-1]]];
+    ddim_sqrt_one_minus_alphas float32 = sqrt(1 - alphas) in float32; ddim_sigmas float64 =
+    eta * sqrt((1 - a_prev) / (1 - a) * (1 - a / a_prev)).  The reference divides a float64 numpy array by a float32 torch tensor there, which
+    torch evaluates as ``reciprocal(1 - a) * (1 - a_prev)``: the difference and the reciprocal in float32, everything else in float64."""
+    acp = np.asarray(acp, dtype=np.float32)
+    T = acp.shape[0]
+    if discretize == "uniform":
+        ts = np.asarray(list(range(0, T, T // S)))
+    elif discretize == "quad":
+        ts = ((np.linspace(0, np.sqrt(T * .8), S)) ** 2).astype(int)
+    else:
+        raise ValueError(f"ddim_discretize = {discretize!r}: one of {DDIM_DISCRETIZE}")
+    eta = check_ddim_eta(eta)
+    ts = ts + 1
+    a = acp[ts]
+    a_prev = np.asarray([acp[0]] + acp[ts[:-1]].tolist(), dtype=np.float64)
+    recip = (np.float32(1.0) / (np.float32(1.0) - a)).astype(np.float64)
+    sigmas = eta * np.sqrt(recip * (1.0 - a_prev) * (1.0 - a.astype(np.float64) / a_prev))
+    return dict(ddim_timesteps=ts, ddim_alphas=a, ddim_alphas_prev=a_prev, ddim_sqrt_one_minus_alphas=np.sqrt(np.float32(1.0) - a),
+                ddim_sigmas=sigmas)
+
+
+def ddim_step_coefs(sched: Dict[str, np.ndarray], index: int) -> Tuple[float, float, float, float, float]:
+    """The float32 scalars of p_sample_ddim (ddim.py:121-133), each table entry rounded to float32 first (``torch.full``), the arithmetic in
+    float32: (sqrt(a_t), sqrt(1 - a_t) from its table, sqrt(a_prev), sqrt(1 - a_prev - sigma_t ** 2), sigma_t)."""
+    f = np.float32
+    a_t, a_prev, sigma = f(sched["ddim_alphas"][index]), f(sched["ddim_alphas_prev"][index]), f(sched["ddim_sigmas"][index])
+    s1m = f(sched["ddim_sqrt_one_minus_alphas"][index])
+    dir_coef = np.sqrt(f(f(f(1.0) - a_prev) - f(sigma * sigma)))
+    return (float(np.sqrt(a_t)), float(s1m), float(np.sqrt(a_prev)), float(dir_coef), float(sigma))
 
 
 def draw_masks_from_boxes(boxes, size):

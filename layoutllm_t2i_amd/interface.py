@@ -37,10 +37,11 @@ from .arch import VAEConfig
 from .family import family_of
 from .model import LatentDiffusion, UNetModel, grounding_input_for, load_sd_first_conv
 from .vae import VAEDecoder
-from .sampler import PLMSSampler
+from .sampler import DDIMSampler, PLMSSampler
 
 MAX_OBJS = 30
 PLMS_STEPS = 50
+SAMPLERS = ("plms", "ddim")      # args["sampler"]; "plms" is the default
 
 
 def set_alpha_scale(model, alpha_scale):
@@ -613,20 +614,41 @@ def build_inpainting_extra(z0, mask):
     return torch.cat([z0 * mask, mask], dim=1)
 
 
+def check_sampler_args(sampler="plms", ddim_eta=0.0, ddim_discretize="uniform"):
+    """The sampler switch (``args["sampler"]`` / ``args["ddim_eta"]`` / ``args["ddim_discretize"]``), checked before any encoder or kernel
+    runs: an unknown sampler, a negative or non-finite eta, an unknown discretisation, or eta / "quad" together with PLMS (which has neither)
+    raise ValueError.  Returns (sampler, eta, discretize)."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"sampler = {sampler!r}: one of {SAMPLERS}")
+    eta = host.check_ddim_eta(ddim_eta)
+    if ddim_discretize not in host.DDIM_DISCRETIZE:
+        raise ValueError(f"ddim_discretize = {ddim_discretize!r}: one of {host.DDIM_DISCRETIZE}")
+    if sampler == "plms" and (eta != 0 or ddim_discretize != "uniform"):
+        raise ValueError(f"ddim_eta = {eta} / ddim_discretize = {ddim_discretize!r} with sampler = 'plms': PLMS is deterministic on uniform "
+                         "steps; eta and 'quad' need sampler = 'ddim'")
+    return sampler, eta, ddim_discretize
+
+
 @torch.no_grad()
 def denoise(all_models, context, uc, relations, grounding_batch, starting_noise, alpha_type=None, guidance_scale=7.5,
-            steps=PLMS_STEPS, mask=None, x0=None, inpainting_extra_input=None, grounding_extra_input=None):
+            steps=PLMS_STEPS, mask=None, x0=None, inpainting_extra_input=None, grounding_extra_input=None, sampler="plms", ddim_eta=0.0,
+            ddim_discretize="uniform"):
     """The denoising hot path proper, from conditioning tensors to the final latent
     (run_batch_images lines interface.py:505-539 without text/VAE stages).  ``mask`` [1|B, 1, h, w] (1 = keep) and ``x0``
     [1|B, 4, h, w] (the encoded input image): inpainting, plms.py:95-99.  The latent's shape [B, 4, h, w] is ``starting_noise``'s
     (plms.py:68-71); h != w needs both to be multiples of 2^(number of UNet downsamples) = 8.  ``inpainting_extra_input`` [1|B, 5, h, w]: the
     extra first-conv input of an inpaint_mode model (required there, ignored by every other model).  ``relations``: None for a model without
     the relation chain (ignored there); a model with it raises ValueError on None before any kernel runs.  ``grounding_extra_input``
-    [B, 3, H, W]: the map a spatial model's grounding downsampler reads (required there, ignored by every other model)."""
+    [B, 3, H, W]: the map a spatial model's grounding downsampler reads (required there, ignored by every other model).  ``sampler``: "plms"
+    or "ddim" (sampler.DDIMSampler, with ``ddim_eta`` >= 0 and ``ddim_discretize`` "uniform" | "quad"; check_sampler_args)."""
     model, autoencoder, text_encoder, diffusion, config = all_models
+    sampler, ddim_eta, ddim_discretize = check_sampler_args(sampler, ddim_eta, ddim_discretize)
     _check_noise(model, starting_noise)
-    sampler = PLMSSampler(diffusion, model, alpha_generator_func=partial(alpha_generator, type=alpha_type),
-                          set_alpha_scale=set_alpha_scale)
+    callbacks = dict(alpha_generator_func=partial(alpha_generator, type=alpha_type), set_alpha_scale=set_alpha_scale)
+    if sampler == "ddim":
+        sampler = DDIMSampler(diffusion, model, eta=ddim_eta, discretize=ddim_discretize, **callbacks)
+    else:
+        sampler = PLMSSampler(diffusion, model, **callbacks)
     grounding_input = model.grounding_tokenizer_input.prepare(grounding_batch, text_encoder)
     input = dict(x=starting_noise, timesteps=None, context=context, relations=relations, grounding_input=grounding_input,
                  inpainting_extra_input=inpainting_extra_input, grounding_extra_input=grounding_extra_input)
@@ -682,10 +704,13 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     _check_noise(model, starting_noise)
     fam = family_of(model.cfg)           # the batch builder follows the model, not the checkpoint's file name
     _refuse_foreign_meta(model, fam, meta, multiple, tuple(int(v) for v in starting_noise.shape[-2:]) if fam.extra_key else None)
+    # the sampler switch is read from ``args`` per call, like ``steps``: not sticky through the cached config
+    sampler_args = check_sampler_args(args.get("sampler", "plms"), args.get("ddim_eta", 0.0), args.get("ddim_discretize", "uniform"))
     config.update(args)                      # mutates the caller's dict, like interface.py:297/484
     cfg = _AttrDict(config)
     if cfg.get("no_plms", False):
-        raise NotImplementedError("the DDIM path is broken in the reference with this UNet (SURVEY App-B#8); PLMS only")
+        raise NotImplementedError("no_plms = True is the reference's DDIM switch, which is broken there with this UNet (SURVEY App-B#8) and "
+                                  "stays refused; DDIM runs under args[\"sampler\"] = \"ddim\" (with args[\"ddim_eta\"], args[\"ddim_discretize\"])")
     bs = cfg.batch_size
     max_rel = cfg.get("max_relations", 10)
     # (a keypoint model: no phrases, no CLIP model, and -- always on the upstream block -- no relation phrases)
@@ -723,7 +748,8 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     samples = denoise(all_models, context, uc, relations, batch, starting_noise, meta.get("alpha_type"), cfg.guidance_scale,
                       steps=int(args.get("steps", PLMS_STEPS)), mask=mask, x0=z0,   # steps per call: not sticky through the cached config
                       inpainting_extra_input=extra,
-                      grounding_extra_input=batch[fam.extra_key] if fam.extra_key else None)      # *_grounding_downsampler_input.prepare: the map itself
+                      grounding_extra_input=batch[fam.extra_key] if fam.extra_key else None,      # *_grounding_downsampler_input.prepare: the map itself
+                      sampler=sampler_args[0], ddim_eta=sampler_args[1], ddim_discretize=sampler_args[2])
     return _postprocess(autoencoder.decode(samples))
 
 

@@ -586,6 +586,29 @@ def plms_update(x, e, olds, coefs, div, sqrt_at, s1m, sqrt_aprev, dir_coef, x_pr
     return x_prev
 
 
+def ddim_update(eps: torch.Tensor, x: torch.Tensor, x_out: torch.Tensor, *, sqrt_at: float, s1m: float, sqrt_aprev: float, dir_coef: float,
+                sigma: float = 0.0, noise: Optional[torch.Tensor] = None, guidance: float = 1.0, pred_x0: Optional[torch.Tensor] = None):
+    """One DDIM update in one launch (gl_ddim_update, ddim.py:115-135).  ``eps``: the UNet output, x's shape, or twice x's batch = the
+    [cond ; uncond] halves, combined with ``guidance`` inside the launch.  ``x_out`` may be ``x``; ``noise`` None = the reference's
+    ``0 * randn`` (the term is skipped); ``pred_x0`` optionally receives the x0 prediction.  Bit-identical to the torch fp32 expression."""
+    for t, n in ((eps, "eps"), (x, "x"), (x_out, "x_out"), (noise, "noise"), (pred_x0, "pred_x0")):
+        if t is None:
+            continue
+        _req(t, F32, n, 4)
+        if not t.is_contiguous():
+            raise ValueError(f"{n}: need a contiguous tensor")
+    n = x.numel()
+    if n == 0 or eps.numel() not in (n, 2 * n):
+        raise ValueError(f"eps {tuple(eps.shape)}: need x's {tuple(x.shape)} elements once, or twice ([cond ; uncond])")
+    for t, nm in ((x_out, "x_out"), (noise, "noise"), (pred_x0, "pred_x0")):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"{nm} {tuple(t.shape)}: need x's shape {tuple(x.shape)}")
+    check(_lib.lib().gl_ddim_update(eps.data_ptr(), x.data_ptr(), _ptr(noise), eps.numel() // n, float(guidance), float(sqrt_at), float(s1m),
+                                    float(sqrt_aprev), float(dir_coef), float(sigma), n, x_out.data_ptr(), _ptr(pred_x0), _stream()),
+          "gl_ddim_update")
+    return x_out
+
+
 def pack_latent(x: torch.Tensor, Cpad: int, reps: int, out: torch.Tensor, split: bool = False):
     """x fp32 [B, C, h, w] -> out fp16 [reps*B, h*w, Cpad]; ``split``: channels [hi | lo | hi] of x (first-conv weights [Whi | Whi | Wlo])."""
     _req(x, F32, "x")

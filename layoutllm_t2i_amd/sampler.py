@@ -1,23 +1,30 @@
-"""PLMS sampler with the reference's call surface (GLIGEN/ldm/models/diffusion/plms.py:10-163).
+"""The two samplers with the reference's call surface: PLMS (GLIGEN/ldm/models/diffusion/plms.py:10-163) and DDIM with eta
+(GLIGEN/ldm/models/diffusion/ddim.py:9-135).
 
     PLMSSampler(diffusion, model, alpha_generator_func=..., set_alpha_scale=...)
         .sample(S, shape, input, uc, guidance_scale, mask=None, x0=None) -> latent
+    DDIMSampler(diffusion, model, alpha_generator_func=..., set_alpha_scale=..., eta=0.0, discretize="uniform")
+        .sample(S, shape, input, uc, guidance_scale, mask=None, x0=None) -> latent
 
-Same loop, same side effects (per-step fuser scale via set_alpha_scale, permanent SD first-conv
-switch on every scale-0 step, step-0 double evaluation, Adams-Bashforth history of <= 3 eps), but:
+Same loops, same side effects (per-step fuser scale via set_alpha_scale, permanent SD first-conv switch on every scale-0 step; PLMS: step-0
+double evaluation, Adams-Bashforth history of <= 3 eps), but:
 
   * cond + uncond run as ONE 2B-sized UNet evaluation (result-identical per sample): the
     conditioning batch is [real grounding + prompt ; null grounding + ""], hoisted once per image;
-  * the CFG combine and the x_prev update are two tiny fused HIP kernels on fp32 latents, evaluated
-    in the reference's operation order (bit-identical to torch fp32 given the same eps);
-  * the schedule tables are computed once per S;
+  * PLMS: the CFG combine and the x_prev update are two tiny fused HIP kernels on fp32 latents; DDIM: ONE kernel (gl_ddim_update) reads the 2B
+    output and does the combine, pred_x0 and x_prev.  Both evaluate in the reference's operation order (bit-identical to torch fp32 given
+    the same eps);
+  * the schedule tables are computed once per S (DDIM: per (S, discretisation, eta));
   * an inpaint_mode model's ``input["inpainting_extra_input"]`` (the same tensor for the cond and the uncond pass, plms.py:118-121) is handed
     to the engine once per ``sample()``, not per step;
   * a map model (canny / hed / depth / normal, sem) takes ``input["grounding_extra_input"]`` (required there, ignored elsewhere): its tokenizer
     runs once per ``sample()``, the unconditional half takes the cached null tokens, both halves read the same extra (UNetModel.condition);
-  * inpainting (``mask`` / ``x0``, plms.py:95-99): each step first replaces the known region,
+  * inpainting (``mask`` / ``x0``, plms.py:95-99, ddim.py:101-105): each step first replaces the known region,
     x = q_sample(x0, t) * mask + (1 - mask) * x, as one fused in-place fp32 HIP kernel (gl_latent_blend, bit-identical to
     the torch expression), with the q_sample noise drawn by ``torch.randn_like(x0)`` before the step's own draws.
+
+What the two samplers share (the hoisted conditioning, the running latent, the per-step fuser scale and first-conv switch, the masked blend)
+lives in ``_Sampler``; each class adds its schedule and its loop.
 """
 from __future__ import annotations
 
@@ -29,7 +36,9 @@ import torch
 from . import host, ops
 
 
-class PLMSSampler(object):
+class _Sampler(object):
+    """The state and the per-step prologue both samplers share."""
+
     def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None):
         self.diffusion = diffusion
         self.model = model
@@ -38,36 +47,25 @@ class PLMSSampler(object):
         self.schedule = schedule
         self.alpha_generator_func = alpha_generator_func
         self.set_alpha_scale = set_alpha_scale
-        self.mirror_rng = True     # plms.py:138 draws randn_like(x) * 0 on every update
-        self._sched_S = None
 
-    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=False):
-        if ddim_eta != 0:
-            raise ValueError('ddim_eta must be 0 for PLMS')
-        if ddim_discretize != "uniform":
-            raise NotImplementedError(ddim_discretize)
-        if self._sched_S == ddim_num_steps:
-            return
+    def _acp(self) -> np.ndarray:
         acp = self.diffusion.alphas_cumprod.detach().cpu().numpy().astype(np.float32)
         assert acp.shape[0] == self.ddpm_num_timesteps, 'alphas have to be defined for each timestep'
-        s = host.make_schedule(ddim_num_steps, acp)
+        return acp
+
+    def _set_tables(self, s) -> None:
         self.ddim_timesteps = s["ddim_timesteps"]
         self.ddim_alphas = s["ddim_alphas"]
         self.ddim_alphas_prev = s["ddim_alphas_prev"]
         self.ddim_sqrt_one_minus_alphas = s["ddim_sqrt_one_minus_alphas"]
         self.ddim_sigmas = s["ddim_sigmas"]
         self._sched = s
-        self._sched_S = ddim_num_steps
 
-    @torch.no_grad()
-    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
-        self.make_schedule(ddim_num_steps=S)
-        return self.plms_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
-
-    @torch.no_grad()
-    def plms_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+    def _begin(self, tag, shape, input, uc, guidance_scale, mask, x0):
+        """Everything before the loop: the starting latent in the engine buffer ``<tag>.x``, the conditioning hoisted once, the fuser scales of
+        the steps and the masked blend of one step (None without a mask).  Returns (x_a, reps, time_range, alphas, blend)."""
         if mask is not None and x0 is None:
-            raise AssertionError("a mask needs x0, the latent of the image to keep (plms.py:96)")
+            raise AssertionError("a mask needs x0, the latent of the image to keep (plms.py:96)")       # before the model is touched
         model, eng = self.model, self.model.engine
         dev = self.device
         b = shape[0]
@@ -76,31 +74,18 @@ class PLMSSampler(object):
             img = torch.randn(shape, device=dev)
             input["x"] = img
         x = img.to(dev, torch.float32).contiguous().clone()
-        n = x.numel()
 
         time_range = np.flip(self.ddim_timesteps)
-        total_steps = self.ddim_timesteps.shape[0]
         alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
 
         # ---- conditioning, once per image: [cond ; uncond] when CFG is active (plms.py:115-124)
         # every missing input raises before any kernel runs; the grounding extra of a map family is handed over whatever conv is switched in
         reps = model.condition(input, uc if uc is not None and guidance_scale != 1 else None, always_extra=True)
 
-        ring = [eng.buf(f"plms.e{j}", tuple(x.shape), torch.float32) for j in range(4)]
-        x_a = eng.buf("plms.x", tuple(x.shape), torch.float32)    # running latent (the engine copies it per forward)
-        x_mid = eng.buf("plms.xmid", tuple(x.shape), torch.float32)
+        x_a = eng.buf(f"{tag}.x", tuple(x.shape), torch.float32)    # running latent (the engine copies it per forward)
         x_a.copy_(x)
-        old: List[torch.Tensor] = []      # newest last, <= 3 entries; tensors are slots of `ring`
-        free = list(ring)
 
-        def step_eval(x_eval, t_val, e_out, e_terms, coefs, div, index, x_out):
-            """one gl_plms_step: UNet (2B batch) -> CFG combine into e_out -> e' -> x_out = update of x_a"""
-            sq_at, s1m, sq_ap, dirc = host.step_coefs(self._sched, index)
-            if self.mirror_rng:
-                torch.randn_like(x_a)          # plms.py:138 draws noise * sigma (= 0) on every update: keep the RNG stream aligned
-            eng.plms_step(x_eval, x_a, x_out, e_out, e_terms, coefs, div, float(t_val), reps, float(guidance_scale),
-                          model.fuser_scale, model.use_sd_conv, sq_at, s1m, sq_ap, dirc)
-
+        blend = None
         if mask is not None:
             # q_sample coefficients of every step, read from the fp32 buffers (ldm.py:19-22); the x0 / mask operands, once
             sac = self.diffusion.sqrt_alphas_cumprod.detach().cpu().numpy()
@@ -112,15 +97,64 @@ class PLMSSampler(object):
                 raise ValueError(f"x0 must be [1|{b}, {tuple(x.shape[1:])}] and mask [1|{b}, 1, {tuple(x.shape[2:])}], got "
                                  f"{tuple(x0.shape)} and {tuple(mask.shape)}")
 
-        for i, step in enumerate(time_range):
-            if alphas is not None:
-                self.set_alpha_scale(model, alphas[i])
-                if alphas[i] == 0:
-                    model.restore_first_conv_from_SD()
-            if mask is not None:
+            def blend(step):
                 # plms.py:95-99: img = q_sample(x0, ts) * mask + (1 - mask) * img; the noise is randn_like(x0) on x0's device
                 noise = torch.randn_like(x0).to(dev, torch.float32).contiguous()
                 ops.latent_blend(x_a, x0_d, noise, mask_d, float(sac[int(step)]), float(s1ac[int(step)]))
+        return x_a, reps, time_range, alphas, blend
+
+    def _step_prologue(self, i, step, alphas, blend) -> None:
+        """what every step does before it evaluates the UNet: the fuser scale, the permanent first-conv switch, the masked blend"""
+        if alphas is not None:
+            self.set_alpha_scale(self.model, alphas[i])
+            if alphas[i] == 0:
+                self.model.restore_first_conv_from_SD()
+        if blend is not None:
+            blend(step)
+
+
+class PLMSSampler(_Sampler):
+    def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None):
+        super().__init__(diffusion, model, schedule, alpha_generator_func, set_alpha_scale)
+        self.mirror_rng = True     # plms.py:138 draws randn_like(x) * 0 on every update
+        self._sched_S = None
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=False):
+        if ddim_eta != 0:
+            raise ValueError('ddim_eta must be 0 for PLMS')
+        if ddim_discretize != "uniform":
+            raise NotImplementedError(ddim_discretize)
+        if self._sched_S == ddim_num_steps:
+            return
+        self._set_tables(host.make_schedule(ddim_num_steps, self._acp()))
+        self._sched_S = ddim_num_steps
+
+    @torch.no_grad()
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+        self.make_schedule(ddim_num_steps=S)
+        return self.plms_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def plms_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+        x_a, reps, time_range, alphas, blend = self._begin("plms", shape, input, uc, guidance_scale, mask, x0)
+        model, eng = self.model, self.model.engine
+        total_steps = self.ddim_timesteps.shape[0]
+
+        ring = [eng.buf(f"plms.e{j}", tuple(x_a.shape), torch.float32) for j in range(4)]
+        x_mid = eng.buf("plms.xmid", tuple(x_a.shape), torch.float32)
+        old: List[torch.Tensor] = []      # newest last, <= 3 entries; tensors are slots of `ring`
+        free = list(ring)
+
+        def step_eval(x_eval, t_val, e_out, e_terms, coefs, div, index, x_out):
+            """one gl_plms_step: UNet (2B batch) -> CFG combine into e_out -> e' -> x_out = update of x_a"""
+            sq_at, s1m, sq_ap, dirc = host.step_coefs(self._sched, index)
+            if self.mirror_rng:
+                torch.randn_like(x_a)          # plms.py:138 draws noise * sigma (= 0) on every update: keep the RNG stream aligned
+            eng.plms_step(x_eval, x_a, x_out, e_out, e_terms, coefs, div, float(t_val), reps, float(guidance_scale),
+                          model.fuser_scale, model.use_sd_conv, sq_at, s1m, sq_ap, dirc)
+
+        for i, step in enumerate(time_range):
+            self._step_prologue(i, step, alphas, blend)
             index = total_steps - i - 1
             t_next = time_range[min(i + 1, len(time_range) - 1)]
             e_t = free.pop()
@@ -136,5 +170,57 @@ class PLMSSampler(object):
             old.append(e_t)
             if len(old) >= 4:
                 free.append(old.pop(0))
+        input["x"] = x_a.clone()
+        return input["x"]
+
+
+class DDIMSampler(_Sampler):
+    """ddim.py:9-135 on the HIP engine.  One step = one 2B UNet evaluation + ONE kernel (``Engine.ddim_step``).
+
+    Two deliberate differences from the reference:
+
+      * ``sample()`` samples with the constructor's ``eta`` and ``discretize``.  The reference's ``sample()`` re-makes the schedule with its
+        defaults on every call (ddim.py:56), so eta > 0 and "quad" are only reachable there through ``make_schedule`` + ``ddim_sampling``
+        -- which work here the same way.
+      * classifier-free guidance runs on a model with the relation chain.  The reference builds its unconditional input without
+        ``"relations"`` (ddim.py:116) and fails in the relation UNet (``KeyError: 'relations'``, openaimodel.py:444); here the unconditional
+        half reads the same relations as the conditional one, as plms.py:121 has it.
+
+    RNG order per step, as in the reference: with a mask ``torch.randn_like(x0)`` (q_sample) first, then one ``torch.randn_like`` of the
+    latent's shape -- drawn when sigma is 0 too (ddim.py:132 multiplies it by 0) and then not handed to the kernel."""
+
+    def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None, eta=0.0, discretize="uniform"):
+        super().__init__(diffusion, model, schedule, alpha_generator_func, set_alpha_scale)
+        self.eta = host.check_ddim_eta(eta)
+        if discretize not in host.DDIM_DISCRETIZE:
+            raise ValueError(f"ddim_discretize = {discretize!r}: one of {host.DDIM_DISCRETIZE}")
+        self.discretize = discretize
+        self._sched_key = None
+
+    def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.):
+        key = (int(ddim_num_steps), ddim_discretize, float(ddim_eta))
+        if self._sched_key == key:
+            return
+        self._set_tables(host.make_ddim_schedule(ddim_num_steps, self._acp(), ddim_discretize, ddim_eta))
+        self._sched_key = key
+
+    @torch.no_grad()
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+        """Unlike the reference's, this does NOT reset eta to 0 (nor the discretisation to "uniform"): it uses the constructor's."""
+        self.make_schedule(ddim_num_steps=S, ddim_discretize=self.discretize, ddim_eta=self.eta)
+        return self.ddim_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def ddim_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+        x_a, reps, time_range, alphas, blend = self._begin("ddim", shape, input, uc, guidance_scale, mask, x0)
+        model, eng = self.model, self.model.engine
+        total_steps = self.ddim_timesteps.shape[0]
+        for i, step in enumerate(time_range):
+            self._step_prologue(i, step, alphas, blend)
+            sq_at, s1m, sq_ap, dirc, sigma = host.ddim_step_coefs(self._sched, total_steps - i - 1)
+            noise = torch.randn_like(x_a)      # ddim.py:132 draws on every step, sigma 0 included: keep the RNG stream aligned
+            eng.ddim_step(x_a, x_a, t=float(int(step)), reps=reps, guidance=float(guidance_scale), fuser_scale=model.fuser_scale,
+                          sd_conv=model.use_sd_conv, sqrt_at=sq_at, s1m=s1m, sqrt_aprev=sq_ap, dir_coef=dirc, sigma=sigma,
+                          noise=noise.to(self.device, torch.float32).contiguous() if sigma != 0 else None)
         input["x"] = x_a.clone()
         return input["x"]
