@@ -360,6 +360,16 @@ int gl_plms_update(const float* x, const float* e, const float* e1, const float*
  * is read before the same element is written.  n % 4 == 0 and 16-byte pointers take the float4 path, everything else the scalar one. */
 int gl_ddim_update(const float* eps, const float* x, const float* noise, int32_t reps, float guidance, float sqrt_at, float s1m,
                    float sqrt_aprev, float dir_coef, float sigma, int64_t n, float* x_out, float* pred_x0, void* stream);
+/* gl_dpmpp_update: everything of one DPM-Solver++(2M) step (Lu et al., arXiv 2211.01095, Algorithm 2, data prediction) behind the UNet in
+ * ONE launch, additive to ABI 15.  eps fp32 [reps * n] as for gl_ddim_update (reps == 2: e = e_u + guidance * (e_c - e_u)).  Then
+ * x0 = (x - s1m * e) / sqrt_at; D = w1 * x0 + w0 * x0_old; x_out = c_x * x + c_d * D, left to right with FP contraction off: given the same
+ * eps, bit-identical to the torch fp32 expression.  x0_old fp32 [n], or NULL = a first-order step: the w0 term is skipped, D = w1 * x0, and
+ * w0 must be 0 (w1 is 1 there; host.dpm_step_coefs).  x0_out fp32 [n] is required: it is the history of the next step.  No no-alias
+ * promise: x_out may be x and x0_out may be x0_old (one history buffer is enough) -- every thread loads all of its operands before it
+ * stores.  n % 4 == 0 and 16-byte pointers take the float4 path, everything else the scalar one; the grid is gl_ddim_update's.
+ * GL_ERR_BAD_ARG: reps other than 1 or 2, n <= 0, NULL eps / x / x_out / x0_out, x0_old == NULL with w0 != 0. */
+int gl_dpmpp_update(const float* eps, const float* x, const float* x0_old, int32_t reps, float guidance, float sqrt_at, float s1m,
+                    float c_x, float c_d, float w1, float w0, int64_t n, float* x_out, float* x0_out, void* stream);
 int gl_pack_latent(const float* x, int32_t B, int32_t C, int32_t hw, int32_t Cpad, int32_t reps, int32_t split, void* out,
                    void* stream);
 /* gl_pack_latent_extra: gl_pack_latent over the channel concatenation of TWO sources (the first-conv input of an inpaint_mode UNet,
@@ -568,6 +578,19 @@ typedef struct gl_ddim_step_args {
 } gl_ddim_step_args;
 int gl_ddim_step(gl_engine* e, const gl_ddim_step_args* a, void* stream);
 int gl_sizeof_ddim_step_args(void);
+/* gl_dpmpp_step: one denoiser evaluation + one gl_dpmpp_update launch, additive to ABI 15: eps = UNet(x, t) into the handle's own output
+ * buffer (graph-cached like gl_unet_forward), then x_out / x0_out from (eps, x, x0_old) as gl_dpmpp_update describes.  x fp32
+ * [Bn / reps, C, h, w]; x_out may be x, x0_out may be x0_old; x0_old NULL = a first-order step.  Refuses what gl_ddim_step refuses, and a
+ * NULL x0_out or a NULL x0_old with w0 != 0 (GL_ERR_BAD_ARG) before the forward runs. */
+typedef struct gl_dpmpp_step_args {
+    const float* x;  float* x_out;                                   /* fp32 [B, C, h, w] */
+    const float* x0_old;  float* x0_out;                             /* fp32 [B, C, h, w]; x0_old or NULL */
+    float t;  int32_t reps;  float guidance;  float fuser_scale;  int32_t sd_conv;
+    float sqrt_at, s1m, c_x, c_d, w1, w0;
+    int32_t use_graph;
+} gl_dpmpp_step_args;
+int gl_dpmpp_step(gl_engine* e, const gl_dpmpp_step_args* a, void* stream);
+int gl_sizeof_dpmpp_step_args(void);
 /* introspection for tests / tools */
 int64_t gl_pool_bytes(const gl_engine* e);
 int gl_num_launches(const gl_engine* e);       /* kernel launches of the last eagerly executed / captured forward */

@@ -143,6 +143,17 @@ class DdimStepArgs(C.Structure):
     ]
 
 
+class DpmppStepArgs(C.Structure):
+    """gl_dpmpp_step_args"""
+    _fields_ = [
+        ("x", vp), ("x_out", vp),
+        ("x0_old", vp), ("x0_out", vp),
+        ("t", f32), ("reps", i32), ("guidance", f32), ("fuser_scale", f32), ("sd_conv", i32),
+        ("sqrt_at", f32), ("s1m", f32), ("c_x", f32), ("c_d", f32), ("w1", f32), ("w0", f32),
+        ("use_graph", i32),
+    ]
+
+
 class RewardArgs(C.Structure):
     """gl_reward_args"""
     _fields_ = [("txt", vp), ("img_pred", vp), ("img_gt", vp), ("B", i32), ("D", i32),
@@ -209,6 +220,7 @@ PROTOTYPES = {
     "gl_cfg_combine": (i32, [fp, f32, i64, fp, vp]),
     "gl_plms_update": (i32, [fp, fp, fp, fp, fp, f32, f32, f32, f32, f32, f32, f32, f32, f32, i64, fp, vp]),
     "gl_ddim_update": (i32, [fp, fp, fp, i32, f32, f32, f32, f32, f32, f32, i64, fp, fp, vp]),
+    "gl_dpmpp_update": (i32, [fp, fp, fp, i32, f32, f32, f32, f32, f32, f32, f32, i64, fp, fp, vp]),
     "gl_pack_latent": (i32, [fp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "gl_pack_latent_extra": (i32, [fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "gl_latent_affine_pack": (i32, [fp, fp, fp, f32, i32, i32, i32, i32, vp, vp]),
@@ -253,6 +265,8 @@ PROTOTYPES = {
     "gl_plms_step": (i32, [vp, C.POINTER(PlmsStepArgs), vp]),
     "gl_ddim_step": (i32, [vp, C.POINTER(DdimStepArgs), vp]),
     "gl_sizeof_ddim_step_args": (i32, []),
+    "gl_dpmpp_step": (i32, [vp, C.POINTER(DpmppStepArgs), vp]),
+    "gl_sizeof_dpmpp_step_args": (i32, []),
     "gl_pool_bytes": (i64, [vp]),
     "gl_num_launches": (i32, [vp]),
     "gl_sizeof_unet_config": (i32, []),
@@ -339,7 +353,8 @@ def lib() -> C.CDLL:
         raise HipLibraryError(f"ABI version mismatch: lib {l.gl_abi_version()} vs host {ABI_VERSION}")
     for cls, fn in ((GemmArgs, l.gl_sizeof_gemm_args), (ConvArgs, l.gl_sizeof_conv_args), (AttnArgs, l.gl_sizeof_attn_args),
                     (UNetConfigC, l.gl_sizeof_unet_config), (WeightInfo, l.gl_sizeof_weight_info),
-                    (PlmsStepArgs, l.gl_sizeof_plms_step_args), (DdimStepArgs, l.gl_sizeof_ddim_step_args), (RewardArgs, l.gl_sizeof_reward_args), (FFArgs, l.gl_sizeof_ff_args),
+                    (PlmsStepArgs, l.gl_sizeof_plms_step_args), (DdimStepArgs, l.gl_sizeof_ddim_step_args), (DpmppStepArgs, l.gl_sizeof_dpmpp_step_args),
+                    (RewardArgs, l.gl_sizeof_reward_args), (FFArgs, l.gl_sizeof_ff_args),
                     (VaeConfigC, l.gl_sizeof_vae_config), (GnArgs, l.gl_sizeof_gn_args),
                     (LayoutRewardArgs, l.gl_sizeof_layout_reward_args), (PolicyArgs, l.gl_sizeof_policy_args),
                     (PolicyGradArgs, l.gl_sizeof_policy_grad_args), (PolicyAdamArgs, l.gl_sizeof_policy_adam_args)):

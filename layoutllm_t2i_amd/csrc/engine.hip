@@ -1621,6 +1621,22 @@ extern "C" int gl_ddim_step(gl_engine* e, const gl_ddim_step_args* a, void* stre
                           (int64_t)(ne / a->reps), a->x_out, a->pred_x0, stream);
 }
 
+extern "C" int gl_dpmpp_step(gl_engine* e, const gl_dpmpp_step_args* a, void* stream) {
+    if (!e || !a || !a->x || !a->x_out || !a->x0_out) return GL_ERR_BAD_ARG;
+    gl_opts_scope opts_scope(e->ovr);       // this handle's option overrides are in effect for the call
+    if (a->reps != 1 && a->reps != 2) return GL_ERR_BAD_ARG;
+    if (!a->x0_old && a->w0 != 0.0f) return GL_ERR_BAD_ARG;       // refused before the forward runs, not behind it
+    const gl_unet_config& cfg = e->cfg;
+    if (cfg.in_channels != cfg.out_channels) return GL_ERR_UNSUPPORTED;
+    const size_t ne = (size_t)e->Bn * cfg.out_channels * e->lat_h * e->lat_w;
+    float* eps_i = e->f32("out.eps", ne);
+    CKP(eps_i);
+    CK(gl_unet_forward(e, a->x, nullptr, a->t, a->reps, a->fuser_scale, a->sd_conv, eps_i, a->use_graph, stream));
+    // the CFG combine, the x0 prediction, the multistep difference and x_prev in one launch, straight from the 2B output
+    return gl_dpmpp_update(eps_i, a->x, a->x0_old, a->reps, a->guidance, a->sqrt_at, a->s1m, a->c_x, a->c_d, a->w1, a->w0,
+                           (int64_t)(ne / a->reps), a->x_out, a->x0_out, stream);
+}
+
 extern "C" int gl_set_handle_option(gl_engine* e, int key, int value) {
     return e ? gl_handle_set_option(e->ovr, key, value) : GL_ERR_BAD_ARG;
 }
@@ -1650,3 +1666,4 @@ extern "C" int gl_sizeof_unet_config(void) { return (int)sizeof(gl_unet_config);
 extern "C" int gl_sizeof_weight_info(void) { return (int)sizeof(gl_weight_info); }
 extern "C" int gl_sizeof_plms_step_args(void) { return (int)sizeof(gl_plms_step_args); }
 extern "C" int gl_sizeof_ddim_step_args(void) { return (int)sizeof(gl_ddim_step_args); }
+extern "C" int gl_sizeof_dpmpp_step_args(void) { return (int)sizeof(gl_dpmpp_step_args); }

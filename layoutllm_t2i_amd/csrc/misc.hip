@@ -296,6 +296,55 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(const float* eps, cons
         }
     }
 }
+
+// One DPM-Solver++(2M) step behind the UNet (Lu et al., arXiv 2211.01095, Algorithm 2) as ONE launch: the CFG combine as above, then
+// x0 = (x - s1m * e) / sqrt_at; D = w1 * x0 + w0 * x0_old; x_prev = c_x * x + c_d * D, left to right.  x0_old == NULL (a first-order step):
+// D = w1 * x0.  No __restrict__ on x / x_out / x0_old / x0_out: x_out may be x and x0_out may be x0_old (ONE history buffer); every thread
+// reads all of its operands before it stores, and no thread reads an element another thread writes.  VEC as for ddim_update_kernel.
+template <int VEC>
+__global__ __launch_bounds__(256) void dpmpp_update_kernel(const float* eps, const float* x, const float* x0_old, int reps, float guidance,
+                                                           float sqrt_at, float s1m, float c_x, float c_d, float w1, float w0, size_t n,
+                                                           float* x_out, float* x0_out) {
+    const size_t nvec = n / VEC;
+    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = v * VEC;
+        float ec[VEC], eu[VEC], xv[VEC], hv[VEC];
+        if constexpr (VEC == 4) {
+            const float4 tc = *reinterpret_cast<const float4*>(eps + i), tx = *reinterpret_cast<const float4*>(x + i);
+            ec[0] = tc.x; ec[1] = tc.y; ec[2] = tc.z; ec[3] = tc.w;
+            xv[0] = tx.x; xv[1] = tx.y; xv[2] = tx.z; xv[3] = tx.w;
+            if (reps == 2) {
+                const float4 tu = *reinterpret_cast<const float4*>(eps + n + i);
+                eu[0] = tu.x; eu[1] = tu.y; eu[2] = tu.z; eu[3] = tu.w;
+            }
+            if (x0_old) {
+                const float4 th = *reinterpret_cast<const float4*>(x0_old + i);
+                hv[0] = th.x; hv[1] = th.y; hv[2] = th.z; hv[3] = th.w;
+            }
+        } else {
+            ec[0] = eps[i]; xv[0] = x[i];
+            if (reps == 2) eu[0] = eps[n + i];
+            if (x0_old) hv[0] = x0_old[i];
+        }
+        float o[VEC], p[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            const float e = reps == 2 ? eu[j] + guidance * (ec[j] - eu[j]) : ec[j];
+            p[j] = (xv[j] - s1m * e) / sqrt_at;
+            float d = w1 * p[j];
+            if (x0_old) d = d + w0 * hv[j];
+            const float cx = c_x * xv[j];
+            o[j] = cx + c_d * d;
+        }
+        if constexpr (VEC == 4) {
+            *reinterpret_cast<float4*>(x_out + i) = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<float4*>(x0_out + i) = make_float4(p[0], p[1], p[2], p[3]);
+        } else {
+            x_out[i] = o[0];
+            x0_out[i] = p[0];
+        }
+    }
+}
 #pragma clang fp contract(fast)
 
 // DiagonalGaussianDistribution(quant_conv(h)).sample() * scale_factor (autoencoder.py:34-38, distributions.py:24-36) per pixel:
@@ -574,6 +623,22 @@ extern "C" int gl_ddim_update(const float* eps, const float* x, const float* noi
     else
         ddim_update_kernel<1><<<dim3(ew_blocks((size_t)n)), dim3(256), 0, (hipStream_t)stream>>>(
             eps, x, noise, reps, guidance, sqrt_at, s1m, sqrt_aprev, dir_coef, sigma, (size_t)n, x_out, pred_x0);
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_dpmpp_update(const float* eps, const float* x, const float* x0_old, int32_t reps, float guidance, float sqrt_at, float s1m,
+                               float c_x, float c_d, float w1, float w0, int64_t n, float* x_out, float* x0_out, void* stream) {
+    if (!eps || !x || !x_out || !x0_out || n <= 0 || (reps != 1 && reps != 2)) return GL_ERR_BAD_ARG;
+    if (!x0_old && w0 != 0.0f) return GL_ERR_BAD_ARG;       // a first-order step has no history term
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x0_old) |
+                           reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(x0_out);
+    if ((n % 4) == 0 && (ptrs % 16) == 0)
+        dpmpp_update_kernel<4><<<dim3(ew_blocks((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream>>>(
+            eps, x, x0_old, reps, guidance, sqrt_at, s1m, c_x, c_d, w1, w0, (size_t)n, x_out, x0_out);
+    else
+        dpmpp_update_kernel<1><<<dim3(ew_blocks((size_t)n)), dim3(256), 0, (hipStream_t)stream>>>(
+            eps, x, x0_old, reps, guidance, sqrt_at, s1m, c_x, c_d, w1, w0, (size_t)n, x_out, x0_out);
     GL_CHECK_LAUNCH();
     return 0;
 }

@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import DdimStepArgs, PlmsStepArgs, check, init_device
+from ._lib import DdimStepArgs, DpmppStepArgs, PlmsStepArgs, check, init_device
 from .arch import UNetConfig
 from .weights import PackedWeights
 
@@ -347,4 +347,32 @@ class UNetEngine:
         a.use_graph = int(self.use_graphs)
         with torch.cuda.device(self.dev):
             self._check(self._lib.gl_ddim_step(self.handle, C.byref(a), self._stream()), "gl_ddim_step")
+        return x_out
+
+    @torch.no_grad()
+    def dpmpp_step(self, x: torch.Tensor, x_out: torch.Tensor, x0_out: torch.Tensor, *, t: float, reps: int, guidance: float, fuser_scale: float,
+                   sd_conv: bool, sqrt_at: float, s1m: float, c_x: float, c_d: float, w1: float = 1.0, w0: float = 0.0,
+                   x0_old: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One gl_dpmpp_step: UNet(x, t) into the engine's own eps buffer, then ONE launch for the CFG combine, x0 = (x - s1m * e) / sqrt_at,
+        D = w1 * x0 + w0 * x0_old and x_out = c_x * x + c_d * D (DPM-Solver++(2M), host.dpm_step_coefs).  ``x_out`` may be ``x``; ``x0_out``
+        receives x0 and may be ``x0_old``; ``x0_old`` None = a first-order step (``w0`` must be 0)."""
+        self._check_x(x, reps)
+        for tns, name in ((x_out, "x_out"), (x0_out, "x0_out"), (x0_old, "x0_old")):
+            if tns is None and name != "x0_old":
+                raise _lib.HipLibraryError(f"{name}: required")
+            if tns is not None and (not tns.is_cuda or tns.dtype != F32 or not tns.is_contiguous() or tns.shape != x.shape):
+                raise _lib.HipLibraryError(f"{name}: need a contiguous fp32 GPU tensor of the latent's shape")
+        if x0_old is None and w0 != 0:
+            raise ValueError(f"w0 = {w0} without x0_old: a first-order step has no history term")
+        if sd_conv and not self.P.has_sd_conv:
+            raise RuntimeError("SD first-conv weights were not packed")
+        a = DpmppStepArgs()
+        a.x, a.x_out = x.data_ptr(), x_out.data_ptr()
+        a.x0_old = None if x0_old is None else x0_old.data_ptr()
+        a.x0_out = x0_out.data_ptr()
+        a.t, a.reps, a.guidance, a.fuser_scale, a.sd_conv = float(t), int(reps), float(guidance), float(fuser_scale), int(bool(sd_conv))
+        a.sqrt_at, a.s1m, a.c_x, a.c_d, a.w1, a.w0 = float(sqrt_at), float(s1m), float(c_x), float(c_d), float(w1), float(w0)
+        a.use_graph = int(self.use_graphs)
+        with torch.cuda.device(self.dev):
+            self._check(self._lib.gl_dpmpp_step(self.handle, C.byref(a), self._stream()), "gl_dpmpp_step")
         return x_out

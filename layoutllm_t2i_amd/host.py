@@ -1,5 +1,5 @@
 """Host-side (CPU, once per image) pieces of the denoising path: integer box rectangles for the
-relation injection, the alpha (fuser-scale) schedule and the PLMS / DDIM schedule tables.
+relation injection, the alpha (fuser-scale) schedule and the PLMS / DDIM / DPM-Solver++ schedule tables.
 
 Everything here is tiny scalar/table work that the reference redoes inside its hot loop
 (attention.py:321-346 with 4 ``.tolist()`` device syncs per call x 16 layers x 102 forwards;
@@ -7,7 +7,7 @@ plms.py:60 per sample() call); it is hoisted out of the loop, result-identically
 """
 from __future__ import annotations
 
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -147,6 +147,76 @@ def ddim_step_coefs(sched: Dict[str, np.ndarray], index: int) -> Tuple[float, fl
     s1m = f(sched["ddim_sqrt_one_minus_alphas"][index])
     dir_coef = np.sqrt(f(f(f(1.0) - a_prev) - f(sigma * sigma)))
     return (float(np.sqrt(a_t)), float(s1m), float(np.sqrt(a_prev)), float(dir_coef), float(sigma))
+
+
+DPM_DISCRETIZE = ("logsnr", "quad", "uniform")
+DPM_ORDERS = (2, 1)
+DPM_LOWER_ORDER_FINAL = 15        # fewer evaluations than this: the last step is first order (the usual lower_order_final rule)
+
+
+def _log_snr(a):
+    """lambda = 1/2 log(a / (1 - a)) in float64: half the log signal-to-noise ratio at alphas_cumprod ``a``"""
+    a = np.asarray(a, dtype=np.float64)
+    return 0.5 * np.log(a / (1.0 - a))
+
+
+def make_dpm_schedule(S: int, acp: np.ndarray, discretize: str = "logsnr") -> Dict[str, np.ndarray]:
+    """Timesteps and nodes of the DPM-Solver++(2M) sampler (Lu et al., arXiv 2211.01095).  ``acp``: the float32 alphas_cumprod buffer.
+
+    'logsnr': S targets ``linspace(lambda(1), lambda(T - 1), S)`` (float64); per target the t in [1, T - 1] with the nearest lambda; sorted
+    ascending, repeats dropped (S = 10: [1, 6, 24, ..., 882, 999]; S = 1: [T - 1]).  'uniform' / 'quad': make_ddim_schedule's timesteps, repeats dropped (a
+    step of width h = 0 would divide by zero in r).  Hence n = len(ddim_timesteps) may differ from S: <= S on 'logsnr' and 'quad', range()'s
+    count on 'uniform' (S = 6 gives 7).
+
+    The nodes as in DDIM: ddim_alphas float32 = acp[t], ddim_alphas_prev float64 = [acp[0], acp[t[:-1]]]; plus ``lambdas`` /
+    ``lambdas_prev`` float64 = the half log-SNR of either, ``ddim_sqrt_one_minus_alphas`` float32, and ``ddim_sigmas`` = 0 (deterministic)."""
+    acp = np.asarray(acp, dtype=np.float32)
+    T = acp.shape[0]
+    S = int(S)
+    if S < 1:
+        raise ValueError(f"steps = {S}: must be >= 1")
+    if discretize == "logsnr":
+        lam = _log_snr(acp[1:])                       # lam[k] = lambda(k + 1), decreasing in t
+        targets = np.linspace(lam[0], lam[-1], S) if S > 1 else lam[-1:]      # one step: from t = T - 1, where the latent is noise
+        ts = np.abs(lam[None, :] - targets[:, None]).argmin(axis=1) + 1
+    elif discretize in ("uniform", "quad"):
+        ts = make_ddim_schedule(S, acp, discretize)["ddim_timesteps"]
+    else:
+        raise ValueError(f"dpm_discretize = {discretize!r}: one of {DPM_DISCRETIZE}")
+    ts = np.unique(np.asarray(ts, dtype=np.int64))    # ascending, repeats dropped
+    a = acp[ts]
+    a_prev = np.asarray([acp[0]] + acp[ts[:-1]].tolist(), dtype=np.float64)
+    return dict(ddim_timesteps=ts, ddim_alphas=a, ddim_alphas_prev=a_prev,
+                ddim_sqrt_one_minus_alphas=np.sqrt(1.0 - a.astype(np.float64)).astype(np.float32), ddim_sigmas=np.zeros(len(ts), np.float64),
+                lambdas=_log_snr(a), lambdas_prev=_log_snr(a_prev))
+
+
+def dpm_step_coefs(sched: Dict[str, np.ndarray], index: int, prev_index: Optional[int] = None,
+                   order: int = 2) -> Tuple[float, float, float, float, float, float]:
+    """The scalars of one DPM-Solver++(2M) step from node ``index`` (a_t) to its a_prev, in float64, each rounded ONCE to float32:
+    (sqrt(a_t), sqrt(1 - a_t), c_x, c_d, w1, w0) of
+
+        x0 = (x - s1m * e) / sqrt_at;  D = w1 * x0 + w0 * x0_old;  x_prev = c_x * x + c_d * D
+
+    with h = lambda(a_prev) - lambda(a_t) > 0, c_x = sqrt(1 - a_prev) / sqrt(1 - a_t), c_d = -sqrt(a_prev) * expm1(-h).  ``prev_index``:
+    the node of the step before (whose x0 is ``x0_old``), None on the first step.  Second order: r = h_of_that_step / h,
+    (w1, w0) = (1 + 1 / (2 r), -1 / (2 r)).  First order, (w1, w0) = (1, 0) -- DDIM with eta 0 in exponential-integrator form: the first step,
+    ``order`` 1, and the last step (index 0) of a schedule with fewer than DPM_LOWER_ORDER_FINAL nodes."""
+    if order not in DPM_ORDERS:
+        raise ValueError(f"dpm_order = {order!r}: one of {DPM_ORDERS}")
+    f = np.float32
+    n = len(sched["ddim_timesteps"])
+    a_t, a_prev = np.float64(sched["ddim_alphas"][index]), np.float64(sched["ddim_alphas_prev"][index])
+    h = np.float64(sched["lambdas_prev"][index]) - np.float64(sched["lambdas"][index])
+    c_x = np.sqrt(1.0 - a_prev) / np.sqrt(1.0 - a_t)
+    c_d = -np.sqrt(a_prev) * np.expm1(-h)
+    first_order = prev_index is None or order == 1 or (index == 0 and n < DPM_LOWER_ORDER_FINAL)
+    if first_order:
+        w1, w0 = 1.0, 0.0
+    else:
+        r = (np.float64(sched["lambdas_prev"][prev_index]) - np.float64(sched["lambdas"][prev_index])) / h
+        w1, w0 = 1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r)
+    return (float(f(np.sqrt(a_t))), float(f(np.sqrt(1.0 - a_t))), float(f(c_x)), float(f(c_d)), float(f(w1)), float(f(w0)))
 
 
 def draw_masks_from_boxes(boxes, size):

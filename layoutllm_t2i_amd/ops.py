@@ -609,6 +609,34 @@ def ddim_update(eps: torch.Tensor, x: torch.Tensor, x_out: torch.Tensor, *, sqrt
     return x_out
 
 
+def dpmpp_update(eps: torch.Tensor, x: torch.Tensor, x_out: torch.Tensor, x0_out: torch.Tensor, *, sqrt_at: float, s1m: float, c_x: float,
+                 c_d: float, w1: float = 1.0, w0: float = 0.0, x0_old: Optional[torch.Tensor] = None, guidance: float = 1.0):
+    """One DPM-Solver++(2M) update in one launch (gl_dpmpp_update): x0 = (x - s1m * e) / sqrt_at, D = w1 * x0 + w0 * x0_old,
+    x_out = c_x * x + c_d * D (host.dpm_step_coefs).  ``eps``: the UNet output, x's shape, or twice x's batch = the [cond ; uncond] halves,
+    combined with ``guidance`` inside the launch.  ``x0_old`` None = a first-order step (``w0`` must be 0).  ``x0_out`` receives x0, the
+    history of the next step; ``x_out`` may be ``x`` and ``x0_out`` may be ``x0_old``.  Bit-identical to the torch fp32 expression."""
+    for t, n in ((eps, "eps"), (x, "x"), (x_out, "x_out"), (x0_out, "x0_out"), (x0_old, "x0_old")):
+        if t is None:
+            if n != "x0_old":
+                raise ValueError(f"{n}: required")
+            continue
+        _req(t, F32, n, 4)
+        if not t.is_contiguous():
+            raise ValueError(f"{n}: need a contiguous tensor")
+    n = x.numel()
+    if n == 0 or eps.numel() not in (n, 2 * n):
+        raise ValueError(f"eps {tuple(eps.shape)}: need x's {tuple(x.shape)} elements once, or twice ([cond ; uncond])")
+    for t, nm in ((x_out, "x_out"), (x0_out, "x0_out"), (x0_old, "x0_old")):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"{nm} {tuple(t.shape)}: need x's shape {tuple(x.shape)}")
+    if x0_old is None and w0 != 0:
+        raise ValueError(f"w0 = {w0} without x0_old: a first-order step has no history term")
+    check(_lib.lib().gl_dpmpp_update(eps.data_ptr(), x.data_ptr(), _ptr(x0_old), eps.numel() // n, float(guidance), float(sqrt_at), float(s1m),
+                                     float(c_x), float(c_d), float(w1), float(w0), n, x_out.data_ptr(), x0_out.data_ptr(), _stream()),
+          "gl_dpmpp_update")
+    return x_out
+
+
 def pack_latent(x: torch.Tensor, Cpad: int, reps: int, out: torch.Tensor, split: bool = False):
     """x fp32 [B, C, h, w] -> out fp16 [reps*B, h*w, Cpad]; ``split``: channels [hi | lo | hi] of x (first-conv weights [Whi | Whi | Wlo])."""
     _req(x, F32, "x")

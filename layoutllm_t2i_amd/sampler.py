@@ -1,9 +1,11 @@
 """The two samplers with the reference's call surface: PLMS (GLIGEN/ldm/models/diffusion/plms.py:10-163) and DDIM with eta
-(GLIGEN/ldm/models/diffusion/ddim.py:9-135).
+(GLIGEN/ldm/models/diffusion/ddim.py:9-135); and one the reference does not have, DPM-Solver++(2M) (``DPMSolverSampler``, below).
 
     PLMSSampler(diffusion, model, alpha_generator_func=..., set_alpha_scale=...)
         .sample(S, shape, input, uc, guidance_scale, mask=None, x0=None) -> latent
     DDIMSampler(diffusion, model, alpha_generator_func=..., set_alpha_scale=..., eta=0.0, discretize="uniform")
+        .sample(S, shape, input, uc, guidance_scale, mask=None, x0=None) -> latent
+    DPMSolverSampler(diffusion, model, alpha_generator_func=..., set_alpha_scale=..., order=2, discretize="logsnr")
         .sample(S, shape, input, uc, guidance_scale, mask=None, x0=None) -> latent
 
 Same loops, same side effects (per-step fuser scale via set_alpha_scale, permanent SD first-conv switch on every scale-0 step; PLMS: step-0
@@ -14,7 +16,9 @@ double evaluation, Adams-Bashforth history of <= 3 eps), but:
   * PLMS: the CFG combine and the x_prev update are two tiny fused HIP kernels on fp32 latents; DDIM: ONE kernel (gl_ddim_update) reads the 2B
     output and does the combine, pred_x0 and x_prev.  Both evaluate in the reference's operation order (bit-identical to torch fp32 given
     the same eps);
-  * the schedule tables are computed once per S (DDIM: per (S, discretisation, eta));
+  * DPM-Solver++(2M): ONE kernel too (gl_dpmpp_update: the combine, the x0 prediction, the multistep difference with the x0 of the step
+    before, x_prev), bit-identical to the torch fp32 expression; its history is one buffer;
+  * the schedule tables are computed once per S (DDIM: per (S, discretisation, eta); DPM-Solver++: per (S, discretisation));
   * an inpaint_mode model's ``input["inpainting_extra_input"]`` (the same tensor for the cond and the uncond pass, plms.py:118-121) is handed
     to the engine once per ``sample()``, not per step;
   * a map model (canny / hed / depth / normal, sem) takes ``input["grounding_extra_input"]`` (required there, ignored elsewhere): its tokenizer
@@ -23,7 +27,7 @@ double evaluation, Adams-Bashforth history of <= 3 eps), but:
     x = q_sample(x0, t) * mask + (1 - mask) * x, as one fused in-place fp32 HIP kernel (gl_latent_blend, bit-identical to
     the torch expression), with the q_sample noise drawn by ``torch.randn_like(x0)`` before the step's own draws.
 
-What the two samplers share (the hoisted conditioning, the running latent, the per-step fuser scale and first-conv switch, the masked blend)
+What the samplers share (the hoisted conditioning, the running latent, the per-step fuser scale and first-conv switch, the masked blend)
 lives in ``_Sampler``; each class adds its schedule and its loop.
 """
 from __future__ import annotations
@@ -37,7 +41,7 @@ from . import host, ops
 
 
 class _Sampler(object):
-    """The state and the per-step prologue both samplers share."""
+    """The state and the per-step prologue the samplers share."""
 
     def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None):
         self.diffusion = diffusion
@@ -222,5 +226,59 @@ class DDIMSampler(_Sampler):
             eng.ddim_step(x_a, x_a, t=float(int(step)), reps=reps, guidance=float(guidance_scale), fuser_scale=model.fuser_scale,
                           sd_conv=model.use_sd_conv, sqrt_at=sq_at, s1m=s1m, sqrt_aprev=sq_ap, dir_coef=dirc, sigma=sigma,
                           noise=noise.to(self.device, torch.float32).contiguous() if sigma != 0 else None)
+        input["x"] = x_a.clone()
+        return input["x"]
+
+
+class DPMSolverSampler(_Sampler):
+    """DPM-Solver++(2M) (Lu et al., arXiv 2211.01095, Algorithm 2: the data-prediction multistep solver) on the HIP engine -- not in the
+    reference.  One step = one 2B UNet evaluation + ONE kernel (``Engine.dpmpp_step``):
+
+        x0 = (x - s1m * e) / sqrt_at;  D = w1 * x0 + w0 * x0_old;  x_prev = c_x * x + c_d * D       (host.dpm_step_coefs)
+
+    The steps sit on the half log-SNR grid by default (``discretize`` "logsnr"; "uniform" / "quad" are DDIM's timesteps without repeats), so
+    ``S`` steps are n <= S evaluations; ``alpha_generator_func`` gets n.  ``order`` 2: the first step, and the last one of fewer than 15, are
+    first order; ``order`` 1 is DDIM with eta 0 in exponential-integrator form.  The history is ONE engine buffer, ``dpmpp.x0`` (the kernel
+    reads the old x0 and writes the new one in place).  The sampler draws no noise: without a mask the result does not depend on the torch
+    seed; with one, the only draw of a step is the blend's ``torch.randn_like(x0)``.  Everything in ``_Sampler`` is inherited unchanged."""
+
+    def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None, order=2, discretize="logsnr"):
+        super().__init__(diffusion, model, schedule, alpha_generator_func, set_alpha_scale)
+        if isinstance(order, bool) or order not in host.DPM_ORDERS:
+            raise ValueError(f"dpm_order = {order!r}: one of {host.DPM_ORDERS}")
+        if discretize not in host.DPM_DISCRETIZE:
+            raise ValueError(f"dpm_discretize = {discretize!r}: one of {host.DPM_DISCRETIZE}")
+        self.order = int(order)
+        self.discretize = discretize
+        self._sched_key = None
+
+    def make_schedule(self, num_steps, discretize=None):
+        discretize = self.discretize if discretize is None else discretize
+        key = (int(num_steps), discretize)
+        if self._sched_key == key:
+            return
+        self._set_tables(host.make_dpm_schedule(num_steps, self._acp(), discretize))
+        self._sched_key = key
+
+    @torch.no_grad()
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+        self.make_schedule(S)
+        return self.dpm_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def dpm_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+        x_a, reps, time_range, alphas, blend = self._begin("dpmpp", shape, input, uc, guidance_scale, mask, x0)
+        model, eng = self.model, self.model.engine
+        total_steps = self.ddim_timesteps.shape[0]
+        hist = eng.buf("dpmpp.x0", tuple(x_a.shape), torch.float32)      # the x0 prediction of the step before; rewritten in place
+        prev = None
+        for i, step in enumerate(time_range):
+            self._step_prologue(i, step, alphas, blend)
+            index = total_steps - i - 1
+            sq_at, s1m, c_x, c_d, w1, w0 = host.dpm_step_coefs(self._sched, index, prev, self.order)
+            eng.dpmpp_step(x_a, x_a, hist, t=float(int(step)), reps=reps, guidance=float(guidance_scale), fuser_scale=model.fuser_scale,
+                           sd_conv=model.use_sd_conv, sqrt_at=sq_at, s1m=s1m, c_x=c_x, c_d=c_d, w1=w1, w0=w0,
+                           x0_old=hist if w0 != 0 else None)
+            prev = index
         input["x"] = x_a.clone()
         return input["x"]

@@ -25,12 +25,28 @@ from .policy_train import PolicyTrainer
 from .prompting import build_prompt, center2lefttop, extract_prediction
 
 
-def generate_with(all_models, clip_model=None, clip_processor=None, device=None) -> Callable:
-    """``generate`` for ``train_batch``: ``interface.generate_batch_images`` on ``all_models`` (train_rl.py:90-91)"""
+def generate_with(all_models, clip_model=None, clip_processor=None, device=None, sampler=None, steps=None, dpm_order=None,
+                  dpm_discretize=None) -> Callable:
+    """``generate`` for ``train_batch``: ``interface.generate_batch_images`` on ``all_models`` (train_rl.py:90-91).  ``sampler`` / ``steps`` /
+    ``dpm_order`` / ``dpm_discretize``: when any is given, the same call through ``interface.run_batch_images`` with those as ``args`` keys
+    (the rollout images only feed the reward: ``sampler="dpmpp_2m", steps=20`` is 20 UNet evaluations per image in place of 51); checked
+    here, before the rollout.  None given: ``generate_batch_images`` exactly."""
     from . import interface
+    more = {k: v for k, v in dict(sampler=sampler, steps=steps, dpm_order=dpm_order, dpm_discretize=dpm_discretize).items() if v is not None}
+    if more:
+        interface.check_dpm_args(interface.check_sampler_args(more.get("sampler", "plms"))[0], more.get("dpm_order", 2),
+                                 more.get("dpm_discretize", "logsnr"))
 
     def generate(captions, categories, bboxes):
-        return interface.generate_batch_images(all_models, captions, categories, bboxes, clip_model, clip_processor, device)
+        if not more:
+            return interface.generate_batch_images(all_models, captions, categories, bboxes, clip_model, clip_processor, device)
+        # generate_batch_images' own call (its 512 x 512 images, its starting-noise draw), with the per-call keys added
+        h, w = interface.latent_hw(None, None, all_models[1])
+        bs = len(captions)
+        args = dict(batch_size=bs, no_plms=False, guidance_scale=7.5, **more)
+        meta = dict(prompts=captions, phrases=categories, locations=bboxes, alpha_type=[0.3, 0.0, 0.7])
+        starting_noise = torch.randn(bs, 4, h, w).to(device)
+        return interface.run_batch_images(all_models, args, meta, starting_noise, clip_model, clip_processor, device=device)
     return generate
 
 
