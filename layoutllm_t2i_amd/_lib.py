@@ -120,15 +120,20 @@ class VaeConfigC(C.Structure):
                 ("embed_dim", i32), ("scale_factor", f32)]
 
 
+# what the three step structs share: the evaluation's fields sit between a struct's operands and its scalars, use_graph closes it
+_STEP_EVAL = [("t", f32), ("reps", i32), ("guidance", f32), ("fuser_scale", f32), ("sd_conv", i32)]
+_STEP_TAIL = [("use_graph", i32)]
+
+
 class PlmsStepArgs(C.Structure):
     """gl_plms_step_args"""
     _fields_ = [
         ("x_eval", vp), ("x_base", vp), ("x_out", vp),
         ("e_out", vp),
         ("e_terms", vp * 4), ("coef", f32 * 4), ("n_terms", i32), ("div", f32),
-        ("t", f32), ("reps", i32), ("guidance", f32), ("fuser_scale", f32), ("sd_conv", i32),
+        *_STEP_EVAL,
         ("sqrt_at", f32), ("s1m", f32), ("sqrt_aprev", f32), ("dir_coef", f32),
-        ("use_graph", i32),
+        *_STEP_TAIL,
     ]
 
 
@@ -137,9 +142,9 @@ class DdimStepArgs(C.Structure):
     _fields_ = [
         ("x", vp), ("x_out", vp),
         ("noise", vp), ("pred_x0", vp),
-        ("t", f32), ("reps", i32), ("guidance", f32), ("fuser_scale", f32), ("sd_conv", i32),
+        *_STEP_EVAL,
         ("sqrt_at", f32), ("s1m", f32), ("sqrt_aprev", f32), ("dir_coef", f32), ("sigma", f32),
-        ("use_graph", i32),
+        *_STEP_TAIL,
     ]
 
 
@@ -148,9 +153,9 @@ class DpmppStepArgs(C.Structure):
     _fields_ = [
         ("x", vp), ("x_out", vp),
         ("x0_old", vp), ("x0_out", vp),
-        ("t", f32), ("reps", i32), ("guidance", f32), ("fuser_scale", f32), ("sd_conv", i32),
+        *_STEP_EVAL,
         ("sqrt_at", f32), ("s1m", f32), ("c_x", f32), ("c_d", f32), ("w1", f32), ("w0", f32),
-        ("use_graph", i32),
+        *_STEP_TAIL,
     ]
 
 

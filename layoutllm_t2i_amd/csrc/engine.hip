@@ -1580,19 +1580,29 @@ extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev,
     return 0;
 }
 
-extern "C" int gl_plms_step(gl_engine* e, const gl_plms_step_args* a, void* stream) {
-    if (!e || !a || !a->x_eval || !a->x_base || !a->x_out || !a->e_out || a->n_terms < 1 || a->n_terms > 4) return GL_ERR_BAD_ARG;
+// What every sampler step does first, behind the entry's own pointer checks: the handle's option overrides, the reps check, the refusal of a
+// model whose output is no latent, then eps = UNet(x, t) into the handle's own ``out.eps``.  Hands back that buffer and n = its elements / reps,
+// the size of the latent.  ``a``: any of the three step structs (they share the fields read here).  The option scope ends with the forward:
+// the update launches behind it read no option.
+template <typename Args>
+static int step_eval(gl_engine* e, const Args* a, const float* x, void* stream, float** eps_i, size_t* n) {
     gl_opts_scope opts_scope(e->ovr);       // this handle's option overrides are in effect for the call
     if (a->reps != 1 && a->reps != 2) return GL_ERR_BAD_ARG;
     const gl_unet_config& cfg = e->cfg;
     if (cfg.in_channels != cfg.out_channels) return GL_ERR_UNSUPPORTED;
+    const size_t ne = (size_t)e->Bn * cfg.out_channels * e->lat_h * e->lat_w;
+    *eps_i = e->f32("out.eps", ne);
+    CKP(*eps_i);
+    *n = ne / a->reps;
+    return gl_unet_forward(e, x, nullptr, a->t, a->reps, a->fuser_scale, a->sd_conv, *eps_i, a->use_graph, stream);
+}
+
+extern "C" int gl_plms_step(gl_engine* e, const gl_plms_step_args* a, void* stream) {
+    if (!e || !a || !a->x_eval || !a->x_base || !a->x_out || !a->e_out || a->n_terms < 1 || a->n_terms > 4) return GL_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const int Bn = e->Bn;
-    const size_t ne = (size_t)Bn * cfg.out_channels * e->lat_h * e->lat_w;
-    const size_t n = ne / a->reps;
-    float* eps_i = e->f32("out.eps", ne);
-    CKP(eps_i);
-    CK(gl_unet_forward(e, a->x_eval, nullptr, a->t, a->reps, a->fuser_scale, a->sd_conv, eps_i, a->use_graph, stream));
+    float* eps_i;
+    size_t n;
+    CK(step_eval(e, a, a->x_eval, stream, &eps_i, &n));
     if (a->reps == 2) {
         CK(gl_cfg_combine(eps_i, a->guidance, (int64_t)n, a->e_out, st));
     } else if (hipMemcpyAsync(a->e_out, eps_i, n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
@@ -1608,33 +1618,23 @@ extern "C" int gl_plms_step(gl_engine* e, const gl_plms_step_args* a, void* stre
 
 extern "C" int gl_ddim_step(gl_engine* e, const gl_ddim_step_args* a, void* stream) {
     if (!e || !a || !a->x || !a->x_out) return GL_ERR_BAD_ARG;
-    gl_opts_scope opts_scope(e->ovr);       // this handle's option overrides are in effect for the call
-    if (a->reps != 1 && a->reps != 2) return GL_ERR_BAD_ARG;
-    const gl_unet_config& cfg = e->cfg;
-    if (cfg.in_channels != cfg.out_channels) return GL_ERR_UNSUPPORTED;
-    const size_t ne = (size_t)e->Bn * cfg.out_channels * e->lat_h * e->lat_w;
-    float* eps_i = e->f32("out.eps", ne);
-    CKP(eps_i);
-    CK(gl_unet_forward(e, a->x, nullptr, a->t, a->reps, a->fuser_scale, a->sd_conv, eps_i, a->use_graph, stream));
+    float* eps_i;
+    size_t n;
+    CK(step_eval(e, a, a->x, stream, &eps_i, &n));
     // the CFG combine, pred_x0 and x_prev in one launch, straight from the 2B output
     return gl_ddim_update(eps_i, a->x, a->noise, a->reps, a->guidance, a->sqrt_at, a->s1m, a->sqrt_aprev, a->dir_coef, a->sigma,
-                          (int64_t)(ne / a->reps), a->x_out, a->pred_x0, stream);
+                          (int64_t)n, a->x_out, a->pred_x0, stream);
 }
 
 extern "C" int gl_dpmpp_step(gl_engine* e, const gl_dpmpp_step_args* a, void* stream) {
     if (!e || !a || !a->x || !a->x_out || !a->x0_out) return GL_ERR_BAD_ARG;
-    gl_opts_scope opts_scope(e->ovr);       // this handle's option overrides are in effect for the call
-    if (a->reps != 1 && a->reps != 2) return GL_ERR_BAD_ARG;
-    if (!a->x0_old && a->w0 != 0.0f) return GL_ERR_BAD_ARG;       // refused before the forward runs, not behind it
-    const gl_unet_config& cfg = e->cfg;
-    if (cfg.in_channels != cfg.out_channels) return GL_ERR_UNSUPPORTED;
-    const size_t ne = (size_t)e->Bn * cfg.out_channels * e->lat_h * e->lat_w;
-    float* eps_i = e->f32("out.eps", ne);
-    CKP(eps_i);
-    CK(gl_unet_forward(e, a->x, nullptr, a->t, a->reps, a->fuser_scale, a->sd_conv, eps_i, a->use_graph, stream));
+    if (!a->x0_old && a->w0 != 0.0f) return GL_ERR_BAD_ARG;       // refused before the forward runs and ahead of the channel refusal
+    float* eps_i;
+    size_t n;
+    CK(step_eval(e, a, a->x, stream, &eps_i, &n));
     // the CFG combine, the x0 prediction, the multistep difference and x_prev in one launch, straight from the 2B output
     return gl_dpmpp_update(eps_i, a->x, a->x0_old, a->reps, a->guidance, a->sqrt_at, a->s1m, a->c_x, a->c_d, a->w1, a->w0,
-                           (int64_t)(ne / a->reps), a->x_out, a->x0_out, stream);
+                           (int64_t)n, a->x_out, a->x0_out, stream);
 }
 
 extern "C" int gl_set_handle_option(gl_engine* e, int key, int value) {

@@ -4,6 +4,8 @@
 #include "gligen_hip.h"
 #include "opts.h"
 
+#include <initializer_list>
+
 namespace {
 
 // text_grounding_net.py:30-41 + util.py:12-26.  One block per (b, i) row; out row = [in_dim | 8*num_freqs].
@@ -182,9 +184,34 @@ __global__ void silu_kernel(const half_t* __restrict__ x, half_t* __restrict__ y
     }
 }
 
+// The operand scaffolding of the elementwise sampler kernels (latent_blend, ddim_update, dpmpp_update): VEC consecutive floats of one operand per
+// thread, as one float4 (VEC = 4: 16-byte pointers) or one scalar.  Arrays by reference: they stay in registers.  No arithmetic here.
+template <int VEC>
+__device__ __forceinline__ void ew_load(const float* p, float (&v)[VEC]) {
+    if constexpr (VEC == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        v[0] = p[0];
+    }
+}
+
+template <int VEC>
+__device__ __forceinline__ void ew_store(float* p, const float (&v)[VEC]) {
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else p[0] = v[0];
+}
+
 // The sampler arithmetic follows the reference's operation order with contraction disabled so that,
-// given identical eps, x_prev is bit-identical to torch fp32 (plms.py:123,126-161).
+// given identical eps, x_prev is bit-identical to torch fp32 (plms.py:123,126-161).  Every helper that holds a multiply-add is defined inside
+// this region: above it, it would be contracted to FMA.
 #pragma clang fp contract(off)
+// classifier-free guidance on the [cond ; uncond] halves (reps == 2): e = e_u + g * (e_c - e_u); one half (reps == 1): e_c as it is, and eu
+// (by reference: not loaded then) is not read
+__device__ __forceinline__ float guided_eps(float ec, const float& eu, int reps, float guidance) {
+    return reps == 2 ? eu + guidance * (ec - eu) : ec;
+}
+
 __global__ void cfg_combine_kernel(const float* __restrict__ eps2b, float guidance, size_t n, float* __restrict__ e) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float ec = eps2b[i];
@@ -227,24 +254,17 @@ __global__ __launch_bounds__(256) void latent_blend_kernel(float* x, const float
         const size_t i0 = ((size_t)(nb0 == 1 ? 0 : b) * C + c) * hw + p;
         const size_t im = (size_t)(nbm == 1 ? 0 : b) * hw + p;
         float xv[VEC], x0v[VEC], nv[VEC], mv[VEC];
-        if constexpr (VEC == 4) {
-            const float4 t = *reinterpret_cast<const float4*>(x + i), t0 = *reinterpret_cast<const float4*>(x0 + i0),
-                         tn = *reinterpret_cast<const float4*>(noise + i0), tm = *reinterpret_cast<const float4*>(m + im);
-            xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
-            x0v[0] = t0.x; x0v[1] = t0.y; x0v[2] = t0.z; x0v[3] = t0.w;
-            nv[0] = tn.x; nv[1] = tn.y; nv[2] = tn.z; nv[3] = tn.w;
-            mv[0] = tm.x; mv[1] = tm.y; mv[2] = tm.z; mv[3] = tm.w;
-        } else {
-            xv[0] = x[i]; x0v[0] = x0[i0]; nv[0] = noise[i0]; mv[0] = m[im];
-        }
+        ew_load<VEC>(x + i, xv);
+        ew_load<VEC>(x0 + i0, x0v);
+        ew_load<VEC>(noise + i0, nv);
+        ew_load<VEC>(m + im, mv);
         float o[VEC];
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
             const float q = a * x0v[j] + s * nv[j];
             o[j] = q * mv[j] + (1.0f - mv[j]) * xv[j];
         }
-        if constexpr (VEC == 4) *reinterpret_cast<float4*>(x + i) = make_float4(o[0], o[1], o[2], o[3]);
-        else x[i] = o[0];
+        ew_store<VEC>(x + i, o);
     }
 }
 
@@ -261,39 +281,21 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(const float* eps, cons
     for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
         const size_t i = v * VEC;
         float ec[VEC], eu[VEC], xv[VEC], nv[VEC];
-        if constexpr (VEC == 4) {
-            const float4 tc = *reinterpret_cast<const float4*>(eps + i), tx = *reinterpret_cast<const float4*>(x + i);
-            ec[0] = tc.x; ec[1] = tc.y; ec[2] = tc.z; ec[3] = tc.w;
-            xv[0] = tx.x; xv[1] = tx.y; xv[2] = tx.z; xv[3] = tx.w;
-            if (reps == 2) {
-                const float4 tu = *reinterpret_cast<const float4*>(eps + n + i);
-                eu[0] = tu.x; eu[1] = tu.y; eu[2] = tu.z; eu[3] = tu.w;
-            }
-            if (noise) {
-                const float4 tn = *reinterpret_cast<const float4*>(noise + i);
-                nv[0] = tn.x; nv[1] = tn.y; nv[2] = tn.z; nv[3] = tn.w;
-            }
-        } else {
-            ec[0] = eps[i]; xv[0] = x[i];
-            if (reps == 2) eu[0] = eps[n + i];
-            if (noise) nv[0] = noise[i];
-        }
+        ew_load<VEC>(eps + i, ec);
+        ew_load<VEC>(x + i, xv);
+        if (reps == 2) ew_load<VEC>(eps + n + i, eu);
+        if (noise) ew_load<VEC>(noise + i, nv);
         float o[VEC], p[VEC];
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const float e = reps == 2 ? eu[j] + guidance * (ec[j] - eu[j]) : ec[j];
+            const float e = guided_eps(ec[j], eu[j], reps, guidance);
             p[j] = (xv[j] - s1m * e) / sqrt_at;
             const float dir_xt = dir_coef * e;
             o[j] = sqrt_aprev * p[j] + dir_xt;
             if (noise) o[j] = o[j] + sigma * nv[j];
         }
-        if constexpr (VEC == 4) {
-            *reinterpret_cast<float4*>(x_out + i) = make_float4(o[0], o[1], o[2], o[3]);
-            if (pred_out) *reinterpret_cast<float4*>(pred_out + i) = make_float4(p[0], p[1], p[2], p[3]);
-        } else {
-            x_out[i] = o[0];
-            if (pred_out) pred_out[i] = p[0];
-        }
+        ew_store<VEC>(x_out + i, o);
+        if (pred_out) ew_store<VEC>(pred_out + i, p);
     }
 }
 
@@ -309,40 +311,22 @@ __global__ __launch_bounds__(256) void dpmpp_update_kernel(const float* eps, con
     for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
         const size_t i = v * VEC;
         float ec[VEC], eu[VEC], xv[VEC], hv[VEC];
-        if constexpr (VEC == 4) {
-            const float4 tc = *reinterpret_cast<const float4*>(eps + i), tx = *reinterpret_cast<const float4*>(x + i);
-            ec[0] = tc.x; ec[1] = tc.y; ec[2] = tc.z; ec[3] = tc.w;
-            xv[0] = tx.x; xv[1] = tx.y; xv[2] = tx.z; xv[3] = tx.w;
-            if (reps == 2) {
-                const float4 tu = *reinterpret_cast<const float4*>(eps + n + i);
-                eu[0] = tu.x; eu[1] = tu.y; eu[2] = tu.z; eu[3] = tu.w;
-            }
-            if (x0_old) {
-                const float4 th = *reinterpret_cast<const float4*>(x0_old + i);
-                hv[0] = th.x; hv[1] = th.y; hv[2] = th.z; hv[3] = th.w;
-            }
-        } else {
-            ec[0] = eps[i]; xv[0] = x[i];
-            if (reps == 2) eu[0] = eps[n + i];
-            if (x0_old) hv[0] = x0_old[i];
-        }
+        ew_load<VEC>(eps + i, ec);
+        ew_load<VEC>(x + i, xv);
+        if (reps == 2) ew_load<VEC>(eps + n + i, eu);
+        if (x0_old) ew_load<VEC>(x0_old + i, hv);
         float o[VEC], p[VEC];
 #pragma unroll
         for (int j = 0; j < VEC; ++j) {
-            const float e = reps == 2 ? eu[j] + guidance * (ec[j] - eu[j]) : ec[j];
+            const float e = guided_eps(ec[j], eu[j], reps, guidance);
             p[j] = (xv[j] - s1m * e) / sqrt_at;
             float d = w1 * p[j];
             if (x0_old) d = d + w0 * hv[j];
             const float cx = c_x * xv[j];
             o[j] = cx + c_d * d;
         }
-        if constexpr (VEC == 4) {
-            *reinterpret_cast<float4*>(x_out + i) = make_float4(o[0], o[1], o[2], o[3]);
-            *reinterpret_cast<float4*>(x0_out + i) = make_float4(p[0], p[1], p[2], p[3]);
-        } else {
-            x_out[i] = o[0];
-            x0_out[i] = p[0];
-        }
+        ew_store<VEC>(x_out + i, o);
+        ew_store<VEC>(x0_out + i, p);
     }
 }
 #pragma clang fp contract(fast)
@@ -487,6 +471,14 @@ int ew_blocks(size_t n) {
     return (int)(b > 2048 ? 2048 : (b == 0 ? 1 : b));
 }
 
+// The float4 form (<4>) of an elementwise sampler kernel, else the scalar one (<1>): ``n`` -- the element count, or the row length a vector
+// must not cross -- is a multiple of 4 and every non-null operand is 16-byte aligned.
+bool ew_vec4(size_t n, std::initializer_list<const void*> operands) {
+    uintptr_t bits = 0;
+    for (const void* p : operands) bits |= reinterpret_cast<uintptr_t>(p);
+    return (n % 4) == 0 && (bits % 16) == 0;
+}
+
 }  // namespace
 
 extern "C" int gl_posnet_input(const float* boxes, const float* masks, const float* emb, const float* null_pos,
@@ -615,9 +607,7 @@ extern "C" int gl_plms_update(const float* x, const float* e, const float* e1, c
 extern "C" int gl_ddim_update(const float* eps, const float* x, const float* noise, int32_t reps, float guidance, float sqrt_at, float s1m,
                               float sqrt_aprev, float dir_coef, float sigma, int64_t n, float* x_out, float* pred_x0, void* stream) {
     if (!eps || !x || !x_out || n <= 0 || (reps != 1 && reps != 2)) return GL_ERR_BAD_ARG;
-    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(noise) |
-                           reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(pred_x0);
-    if ((n % 4) == 0 && (ptrs % 16) == 0)
+    if (ew_vec4((size_t)n, {eps, x, noise, x_out, pred_x0}))
         ddim_update_kernel<4><<<dim3(ew_blocks((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream>>>(
             eps, x, noise, reps, guidance, sqrt_at, s1m, sqrt_aprev, dir_coef, sigma, (size_t)n, x_out, pred_x0);
     else
@@ -631,9 +621,7 @@ extern "C" int gl_dpmpp_update(const float* eps, const float* x, const float* x0
                                float c_x, float c_d, float w1, float w0, int64_t n, float* x_out, float* x0_out, void* stream) {
     if (!eps || !x || !x_out || !x0_out || n <= 0 || (reps != 1 && reps != 2)) return GL_ERR_BAD_ARG;
     if (!x0_old && w0 != 0.0f) return GL_ERR_BAD_ARG;       // a first-order step has no history term
-    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(eps) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x0_old) |
-                           reinterpret_cast<uintptr_t>(x_out) | reinterpret_cast<uintptr_t>(x0_out);
-    if ((n % 4) == 0 && (ptrs % 16) == 0)
+    if (ew_vec4((size_t)n, {eps, x, x0_old, x_out, x0_out}))
         dpmpp_update_kernel<4><<<dim3(ew_blocks((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream>>>(
             eps, x, x0_old, reps, guidance, sqrt_at, s1m, c_x, c_d, w1, w0, (size_t)n, x_out, x0_out);
     else
@@ -667,9 +655,7 @@ extern "C" int gl_latent_blend(float* x, const float* x0, const float* noise, co
     if (!x || !x0 || !noise || !mask || B <= 0 || C <= 0 || hw <= 0) return GL_ERR_BAD_ARG;
     if ((x0_batch != 1 && x0_batch != B) || (mask_batch != 1 && mask_batch != B)) return GL_ERR_BAD_ARG;
     const size_t n = (size_t)B * C * hw;
-    const bool vec = (hw % 4) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(noise) |
-                                        reinterpret_cast<uintptr_t>(mask)) % 16) == 0;
-    if (vec)
+    if (ew_vec4((size_t)hw, {x, x0, noise, mask}))       // a float4 stays inside one (b, c) row
         latent_blend_kernel<4><<<dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream>>>(x, x0, noise, mask, a, s, B, C, hw, x0_batch, mask_batch);
     else
         latent_blend_kernel<1><<<dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream>>>(x, x0, noise, mask, a, s, B, C, hw, x0_batch, mask_batch);

@@ -298,31 +298,43 @@ class UNetEngine:
                                                   eps_out.data_ptr(), int(self.use_graphs), self._stream()), "gl_unet_forward")
         return eps_out
 
+    def _check_step(self, x: torch.Tensor, reps: int, operands, required=()) -> None:
+        """What the three steps check first: the evaluated latent against the conditioning, then every (name, tensor) of ``operands`` -- a
+        contiguous fp32 GPU tensor of the latent's shape; None passes unless the name is in ``required``."""
+        self._check_x(x, reps)
+        for name, tns in operands:
+            if tns is None and name in required:
+                raise _lib.HipLibraryError(f"{name}: required")
+            if tns is not None and (not tns.is_cuda or tns.dtype != F32 or not tns.is_contiguous() or tns.shape != x.shape):
+                raise _lib.HipLibraryError(f"{name}: need a contiguous fp32 GPU tensor of the latent's shape")
+
+    def _run_step(self, entry: str, a, t, reps, guidance, fuser_scale, sd_conv) -> None:
+        """What the three steps end with, behind their own checks: the SD first-conv refusal, the fields every step struct carries
+        (_lib._STEP_EVAL, use_graph), the entry under the device guard."""
+        if sd_conv and not self.P.has_sd_conv:
+            raise RuntimeError("SD first-conv weights were not packed")
+        a.t, a.reps, a.guidance, a.fuser_scale, a.sd_conv = float(t), int(reps), float(guidance), float(fuser_scale), int(bool(sd_conv))
+        a.use_graph = int(self.use_graphs)
+        with torch.cuda.device(self.dev):
+            self._check(getattr(self._lib, entry)(self.handle, C.byref(a), self._stream()), entry)
+
     @torch.no_grad()
     def plms_step(self, x_eval: torch.Tensor, x_base: torch.Tensor, x_out: torch.Tensor, e_out: torch.Tensor, e_terms: List[torch.Tensor],
                   coefs, div: float, t: float, reps: int, guidance: float, fuser_scale: float, sd_conv: bool, sqrt_at: float, s1m: float,
                   sqrt_aprev: float, dir_coef: float) -> torch.Tensor:
         """One gl_plms_step: UNet(x_eval, t) -> CFG combine into ``e_out`` -> e' = sum coefs[j] * e_terms[j] / div ->
         x_out = PLMS / DDIM(sigma 0) update of x_base (plms.py:110-163)."""
-        self._check_x(x_eval, reps)
-        a = PlmsStepArgs()
-        for tns, name in ((x_eval, "x_eval"), (x_base, "x_base"), (x_out, "x_out"), (e_out, "e_out"), *[(e, "e_term") for e in e_terms]):
-            if not tns.is_cuda or tns.dtype != F32 or not tns.is_contiguous() or tns.shape != x_eval.shape:
-                raise _lib.HipLibraryError(f"{name}: need a contiguous fp32 GPU tensor of the latent's shape")
-        a.x_eval, a.x_base, a.x_out, a.e_out = x_eval.data_ptr(), x_base.data_ptr(), x_out.data_ptr(), e_out.data_ptr()
+        self._check_step(x_eval, reps, [("x_eval", x_eval), ("x_base", x_base), ("x_out", x_out), ("e_out", e_out), *[("e_term", e) for e in e_terms]])
         if not 1 <= len(e_terms) <= 4 or len(coefs) != len(e_terms):
             raise ValueError("1..4 eps terms with one coefficient each")
+        a = PlmsStepArgs()
+        a.x_eval, a.x_base, a.x_out, a.e_out = x_eval.data_ptr(), x_base.data_ptr(), x_out.data_ptr(), e_out.data_ptr()
         for j, (e, c) in enumerate(zip(e_terms, coefs)):
             a.e_terms[j] = e.data_ptr()
             a.coef[j] = float(c)
         a.n_terms, a.div = len(e_terms), float(div)
-        a.t, a.reps, a.guidance, a.fuser_scale, a.sd_conv = float(t), int(reps), float(guidance), float(fuser_scale), int(bool(sd_conv))
         a.sqrt_at, a.s1m, a.sqrt_aprev, a.dir_coef = float(sqrt_at), float(s1m), float(sqrt_aprev), float(dir_coef)
-        a.use_graph = int(self.use_graphs)
-        if sd_conv and not self.P.has_sd_conv:
-            raise RuntimeError("SD first-conv weights were not packed")
-        with torch.cuda.device(self.dev):
-            self._check(self._lib.gl_plms_step(self.handle, C.byref(a), self._stream()), "gl_plms_step")
+        self._run_step("gl_plms_step", a, t, reps, guidance, fuser_scale, sd_conv)
         return x_out
 
     @torch.no_grad()
@@ -332,21 +344,13 @@ class UNetEngine:
         """One gl_ddim_step: UNet(x, t) into the engine's own eps buffer, then ONE launch for the CFG combine, pred_x0 and
         x_out = sqrt_aprev * pred_x0 + dir_coef * e + sigma * noise (ddim.py:111-135).  ``x_out`` may be ``x``; ``noise`` None = the
         reference's ``0 * randn`` (skipped); ``pred_x0`` optionally receives the x0 prediction."""
-        self._check_x(x, reps)
-        for tns, name in ((x_out, "x_out"), (noise, "noise"), (pred_x0, "pred_x0")):
-            if tns is not None and (not tns.is_cuda or tns.dtype != F32 or not tns.is_contiguous() or tns.shape != x.shape):
-                raise _lib.HipLibraryError(f"{name}: need a contiguous fp32 GPU tensor of the latent's shape")
-        if sd_conv and not self.P.has_sd_conv:
-            raise RuntimeError("SD first-conv weights were not packed")
+        self._check_step(x, reps, [("x_out", x_out), ("noise", noise), ("pred_x0", pred_x0)])
         a = DdimStepArgs()
         a.x, a.x_out = x.data_ptr(), x_out.data_ptr()
         a.noise = None if noise is None else noise.data_ptr()
         a.pred_x0 = None if pred_x0 is None else pred_x0.data_ptr()
-        a.t, a.reps, a.guidance, a.fuser_scale, a.sd_conv = float(t), int(reps), float(guidance), float(fuser_scale), int(bool(sd_conv))
         a.sqrt_at, a.s1m, a.sqrt_aprev, a.dir_coef, a.sigma = float(sqrt_at), float(s1m), float(sqrt_aprev), float(dir_coef), float(sigma)
-        a.use_graph = int(self.use_graphs)
-        with torch.cuda.device(self.dev):
-            self._check(self._lib.gl_ddim_step(self.handle, C.byref(a), self._stream()), "gl_ddim_step")
+        self._run_step("gl_ddim_step", a, t, reps, guidance, fuser_scale, sd_conv)
         return x_out
 
     @torch.no_grad()
@@ -356,23 +360,12 @@ class UNetEngine:
         """One gl_dpmpp_step: UNet(x, t) into the engine's own eps buffer, then ONE launch for the CFG combine, x0 = (x - s1m * e) / sqrt_at,
         D = w1 * x0 + w0 * x0_old and x_out = c_x * x + c_d * D (DPM-Solver++(2M), host.dpm_step_coefs).  ``x_out`` may be ``x``; ``x0_out``
         receives x0 and may be ``x0_old``; ``x0_old`` None = a first-order step (``w0`` must be 0)."""
-        self._check_x(x, reps)
-        for tns, name in ((x_out, "x_out"), (x0_out, "x0_out"), (x0_old, "x0_old")):
-            if tns is None and name != "x0_old":
-                raise _lib.HipLibraryError(f"{name}: required")
-            if tns is not None and (not tns.is_cuda or tns.dtype != F32 or not tns.is_contiguous() or tns.shape != x.shape):
-                raise _lib.HipLibraryError(f"{name}: need a contiguous fp32 GPU tensor of the latent's shape")
+        self._check_step(x, reps, [("x_out", x_out), ("x0_out", x0_out), ("x0_old", x0_old)], required=("x_out", "x0_out"))
         if x0_old is None and w0 != 0:
             raise ValueError(f"w0 = {w0} without x0_old: a first-order step has no history term")
-        if sd_conv and not self.P.has_sd_conv:
-            raise RuntimeError("SD first-conv weights were not packed")
         a = DpmppStepArgs()
-        a.x, a.x_out = x.data_ptr(), x_out.data_ptr()
+        a.x, a.x_out, a.x0_out = x.data_ptr(), x_out.data_ptr(), x0_out.data_ptr()
         a.x0_old = None if x0_old is None else x0_old.data_ptr()
-        a.x0_out = x0_out.data_ptr()
-        a.t, a.reps, a.guidance, a.fuser_scale, a.sd_conv = float(t), int(reps), float(guidance), float(fuser_scale), int(bool(sd_conv))
         a.sqrt_at, a.s1m, a.c_x, a.c_d, a.w1, a.w0 = float(sqrt_at), float(s1m), float(c_x), float(c_d), float(w1), float(w0)
-        a.use_graph = int(self.use_graphs)
-        with torch.cuda.device(self.dev):
-            self._check(self._lib.gl_dpmpp_step(self.handle, C.byref(a), self._stream()), "gl_dpmpp_step")
+        self._run_step("gl_dpmpp_step", a, t, reps, guidance, fuser_scale, sd_conv)
         return x_out

@@ -13,8 +13,8 @@ a passed ``starting_noise`` [bs, 4, h, w] decides the shape itself (image = 8h x
 ``meta``: ``ckpt`` (path), ``prompt``, ``phrases``, ``locations`` (ltrb, normalised), optional
 ``alpha_type``, ``save_folder_name``, ``images`` (one reference image or None per box, for a ``*_box_text_image`` checkpoint; with
 ``text_mask`` / ``image_mask`` / ``projection_matrix`` as in interface.prepare_batch); ``config``: object/dict with ``batch_size``, ``guidance_scale``,
-``no_plms`` (must be False), optional ``sampler`` ("plms", the default, "ddim" with ``ddim_eta`` / ``ddim_discretize``, interface.check_sampler_args, or "dpmpp_2m" with
-``dpm_order`` / ``dpm_discretize``, interface.check_dpm_args),
+``no_plms`` (must be False), optional ``sampler`` ("plms", the default, "ddim" with ``ddim_eta`` / ``ddim_discretize``, or "dpmpp_2m" with
+``dpm_order`` / ``dpm_discretize``: sampler.SAMPLER_KEYS, checked by sampler.resolve_sampler),
 optional ``negative_prompt`` (a string encoded for the unconditional pass, gligen_inference.py:379-380; default
 None = the empty prompt), optional ``folder``.  Images are saved like the reference does
 (gligen_inference.py:437-446) when ``config.folder`` is given.
@@ -47,6 +47,7 @@ import torch
 
 from . import interface
 from .family import family_of
+from .sampler import SAMPLER_KEYS
 
 _MODELS = {}
 
@@ -92,8 +93,8 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
         version = "openai/clip-vit-large-patch14"
         clip_model = CLIPModel.from_pretrained(version).to(device)
         clip_processor = CLIPProcessor.from_pretrained(version)
-    # per-call keys, handed on only when the config carries them: the step count and the sampler switch (interface.check_sampler_args)
-    for k in ("steps", "sampler", "ddim_eta", "ddim_discretize", "dpm_order", "dpm_discretize"):
+    # per-call keys, handed on only when the config carries them: the step count and the sampler switch (sampler.resolve_sampler)
+    for k in ("steps",) + SAMPLER_KEYS:
         if k in (config if isinstance(config, dict) else vars(config)):
             args[k] = _get(config, k)
     images = interface.run_one_image(all_models, args, m, starting_noise, clip_model, clip_processor, device=device)

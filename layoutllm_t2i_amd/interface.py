@@ -37,11 +37,11 @@ from .arch import VAEConfig
 from .family import family_of
 from .model import LatentDiffusion, UNetModel, grounding_input_for, load_sd_first_conv
 from .vae import VAEDecoder
-from .sampler import DDIMSampler, DPMSolverSampler, PLMSSampler
+from .sampler import SAMPLERS, DDIMSampler, DPMSolverSampler, PLMSSampler, resolve_sampler  # noqa: F401  (the classes: part of the surface)
 
 MAX_OBJS = 30
 PLMS_STEPS = 50
-SAMPLERS = ("plms", "ddim", "dpmpp_2m")      # args["sampler"]; "plms" is the default
+# SAMPLERS (above): ("plms", "ddim", "dpmpp_2m"), the values of args["sampler"] out of sampler.SAMPLER_TABLE; "plms" is the default
 
 
 def set_alpha_scale(model, alpha_scale):
@@ -617,16 +617,10 @@ def build_inpainting_extra(z0, mask):
 def check_sampler_args(sampler="plms", ddim_eta=0.0, ddim_discretize="uniform"):
     """The sampler switch (``args["sampler"]`` / ``args["ddim_eta"]`` / ``args["ddim_discretize"]``), checked before any encoder or kernel
     runs: an unknown sampler, a negative or non-finite eta, an unknown discretisation, or eta / "quad" together with PLMS (which has neither)
-    raise ValueError.  Returns (sampler, eta, discretize)."""
-    if sampler not in SAMPLERS:
-        raise ValueError(f"sampler = {sampler!r}: one of {SAMPLERS}")
-    eta = host.check_ddim_eta(ddim_eta)
-    if ddim_discretize not in host.DDIM_DISCRETIZE:
-        raise ValueError(f"ddim_discretize = {ddim_discretize!r}: one of {host.DDIM_DISCRETIZE}")
-    if sampler == "plms" and (eta != 0 or ddim_discretize != "uniform"):
-        raise ValueError(f"ddim_eta = {eta} / ddim_discretize = {ddim_discretize!r} with sampler = 'plms': PLMS is deterministic on uniform "
-                         "steps; eta and 'quad' need sampler = 'ddim'")
-    return sampler, eta, ddim_discretize
+    raise ValueError.  Returns (sampler, eta, discretize).  sampler.resolve_sampler up to the "ddim" stage: the keys of the samplers behind
+    it, and what those refuse, are check_dpm_args' part."""
+    _, v = resolve_sampler(dict(sampler=sampler, ddim_eta=ddim_eta, ddim_discretize=ddim_discretize), upto="ddim")
+    return v["sampler"], v["ddim_eta"], v["ddim_discretize"]
 
 
 def check_dpm_args(sampler="plms", dpm_order=2, dpm_discretize="logsnr", ddim_eta=0.0, ddim_discretize="uniform"):
@@ -634,22 +628,9 @@ def check_dpm_args(sampler="plms", dpm_order=2, dpm_discretize="logsnr", ddim_et
     checked next to check_sampler_args (which has judged ``sampler`` and the ddim keys on their own), before any encoder or kernel runs.
     ValueError naming the key: a bad order or discretisation; either at a non-default value with "plms" / "ddim" (which have neither);
     ``ddim_eta`` != 0 or ``ddim_discretize`` != "uniform" with "dpmpp_2m" (a deterministic solver with its own grids).
-    Returns (order, discretize)."""
-    if isinstance(dpm_order, bool) or not isinstance(dpm_order, (int, np.integer)) or dpm_order not in host.DPM_ORDERS:
-        raise ValueError(f"dpm_order = {dpm_order!r}: one of {host.DPM_ORDERS}")
-    if dpm_discretize not in host.DPM_DISCRETIZE:
-        raise ValueError(f"dpm_discretize = {dpm_discretize!r}: one of {host.DPM_DISCRETIZE}")
-    if sampler == "dpmpp_2m":
-        if ddim_eta != 0:
-            raise ValueError(f"ddim_eta = {ddim_eta} with sampler = 'dpmpp_2m': the solver is deterministic; eta needs sampler = 'ddim'")
-        if ddim_discretize != "uniform":
-            raise ValueError(f"ddim_discretize = {ddim_discretize!r} with sampler = 'dpmpp_2m': its grid is args[\"dpm_discretize\"]")
-    else:
-        if dpm_order != 2:
-            raise ValueError(f"dpm_order = {dpm_order} with sampler = {sampler!r}: it needs sampler = 'dpmpp_2m'")
-        if dpm_discretize != "logsnr":
-            raise ValueError(f"dpm_discretize = {dpm_discretize!r} with sampler = {sampler!r}: it needs sampler = 'dpmpp_2m'")
-    return int(dpm_order), dpm_discretize
+    Returns (order, discretize).  sampler.resolve_sampler on all five keys: what check_sampler_args would refuse is refused here as well."""
+    _, v = resolve_sampler(dict(sampler=sampler, dpm_order=dpm_order, dpm_discretize=dpm_discretize, ddim_eta=ddim_eta, ddim_discretize=ddim_discretize))
+    return v["dpm_order"], v["dpm_discretize"]
 
 
 @torch.no_grad()
@@ -663,20 +644,15 @@ def denoise(all_models, context, uc, relations, grounding_batch, starting_noise,
     extra first-conv input of an inpaint_mode model (required there, ignored by every other model).  ``relations``: None for a model without
     the relation chain (ignored there); a model with it raises ValueError on None before any kernel runs.  ``grounding_extra_input``
     [B, 3, H, W]: the map a spatial model's grounding downsampler reads (required there, ignored by every other model).  ``sampler``: "plms"
-    or "ddim" (sampler.DDIMSampler, with ``ddim_eta`` >= 0 and ``ddim_discretize`` "uniform" | "quad"; check_sampler_args), or "dpmpp_2m"
-    (sampler.DPMSolverSampler, with ``dpm_order`` 2 | 1 and ``dpm_discretize`` "logsnr" | "quad" | "uniform"; check_dpm_args): there
-    ``steps`` bounds the number of UNet evaluations, 20 is the usual choice."""
+    or "ddim" (sampler.DDIMSampler, with ``ddim_eta`` >= 0 and ``ddim_discretize`` "uniform" | "quad"), or "dpmpp_2m"
+    (sampler.DPMSolverSampler, with ``dpm_order`` 2 | 1 and ``dpm_discretize`` "logsnr" | "quad" | "uniform"; there ``steps`` bounds the
+    number of UNet evaluations, 20 is the usual choice); all five go through sampler.resolve_sampler first."""
     model, autoencoder, text_encoder, diffusion, config = all_models
-    sampler, ddim_eta, ddim_discretize = check_sampler_args(sampler, ddim_eta, ddim_discretize)
-    dpm_order, dpm_discretize = check_dpm_args(sampler, dpm_order, dpm_discretize, ddim_eta, ddim_discretize)
+    spec, values = resolve_sampler(dict(sampler=sampler, ddim_eta=ddim_eta, ddim_discretize=ddim_discretize, dpm_order=dpm_order,
+                                        dpm_discretize=dpm_discretize))
     _check_noise(model, starting_noise)
     callbacks = dict(alpha_generator_func=partial(alpha_generator, type=alpha_type), set_alpha_scale=set_alpha_scale)
-    if sampler == "ddim":
-        sampler = DDIMSampler(diffusion, model, eta=ddim_eta, discretize=ddim_discretize, **callbacks)
-    elif sampler == "dpmpp_2m":
-        sampler = DPMSolverSampler(diffusion, model, order=dpm_order, discretize=dpm_discretize, **callbacks)
-    else:
-        sampler = PLMSSampler(diffusion, model, **callbacks)
+    sampler = spec.cls(diffusion, model, **spec.kwargs(values), **callbacks)
     grounding_input = model.grounding_tokenizer_input.prepare(grounding_batch, text_encoder)
     input = dict(x=starting_noise, timesteps=None, context=context, relations=relations, grounding_input=grounding_input,
                  inpainting_extra_input=inpainting_extra_input, grounding_extra_input=grounding_extra_input)
@@ -733,8 +709,7 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     fam = family_of(model.cfg)           # the batch builder follows the model, not the checkpoint's file name
     _refuse_foreign_meta(model, fam, meta, multiple, tuple(int(v) for v in starting_noise.shape[-2:]) if fam.extra_key else None)
     # the sampler switch is read from ``args`` per call, like ``steps``: not sticky through the cached config
-    sampler_args = check_sampler_args(args.get("sampler", "plms"), args.get("ddim_eta", 0.0), args.get("ddim_discretize", "uniform"))
-    dpm_args = check_dpm_args(sampler_args[0], args.get("dpm_order", 2), args.get("dpm_discretize", "logsnr"), *sampler_args[1:])
+    _, sampler_values = resolve_sampler(args)
     config.update(args)                      # mutates the caller's dict, like interface.py:297/484
     cfg = _AttrDict(config)
     if cfg.get("no_plms", False):
@@ -778,8 +753,7 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
                       steps=int(args.get("steps", PLMS_STEPS)), mask=mask, x0=z0,   # steps per call: not sticky through the cached config
                       inpainting_extra_input=extra,
                       grounding_extra_input=batch[fam.extra_key] if fam.extra_key else None,      # *_grounding_downsampler_input.prepare: the map itself
-                      sampler=sampler_args[0], ddim_eta=sampler_args[1], ddim_discretize=sampler_args[2],
-                      dpm_order=dpm_args[0], dpm_discretize=dpm_args[1])
+                      **sampler_values)
     return _postprocess(autoencoder.decode(samples))
 
 

@@ -586,23 +586,33 @@ def plms_update(x, e, olds, coefs, div, sqrt_at, s1m, sqrt_aprev, dir_coef, x_pr
     return x_prev
 
 
+def _update_operands(eps, x, more, required=()) -> int:
+    """The operands of a fused sampler update (ddim_update, dpmpp_update): ``eps``, ``x`` and the (name, tensor) pairs of ``more`` are
+    contiguous fp32 GPU tensors, 4-byte aligned; None passes unless the name is in ``required``; eps holds x's elements once or twice, every
+    other operand once.  Returns x's element count."""
+    for nm, t in [("eps", eps), ("x", x), *more]:
+        if t is None:
+            if nm in required:
+                raise ValueError(f"{nm}: required")
+            continue
+        _req(t, F32, nm, 4)
+        if not t.is_contiguous():
+            raise ValueError(f"{nm}: need a contiguous tensor")
+    n = x.numel()
+    if n == 0 or eps.numel() not in (n, 2 * n):
+        raise ValueError(f"eps {tuple(eps.shape)}: need x's {tuple(x.shape)} elements once, or twice ([cond ; uncond])")
+    for nm, t in more:
+        if t is not None and t.numel() != n:
+            raise ValueError(f"{nm} {tuple(t.shape)}: need x's shape {tuple(x.shape)}")
+    return n
+
+
 def ddim_update(eps: torch.Tensor, x: torch.Tensor, x_out: torch.Tensor, *, sqrt_at: float, s1m: float, sqrt_aprev: float, dir_coef: float,
                 sigma: float = 0.0, noise: Optional[torch.Tensor] = None, guidance: float = 1.0, pred_x0: Optional[torch.Tensor] = None):
     """One DDIM update in one launch (gl_ddim_update, ddim.py:115-135).  ``eps``: the UNet output, x's shape, or twice x's batch = the
     [cond ; uncond] halves, combined with ``guidance`` inside the launch.  ``x_out`` may be ``x``; ``noise`` None = the reference's
     ``0 * randn`` (the term is skipped); ``pred_x0`` optionally receives the x0 prediction.  Bit-identical to the torch fp32 expression."""
-    for t, n in ((eps, "eps"), (x, "x"), (x_out, "x_out"), (noise, "noise"), (pred_x0, "pred_x0")):
-        if t is None:
-            continue
-        _req(t, F32, n, 4)
-        if not t.is_contiguous():
-            raise ValueError(f"{n}: need a contiguous tensor")
-    n = x.numel()
-    if n == 0 or eps.numel() not in (n, 2 * n):
-        raise ValueError(f"eps {tuple(eps.shape)}: need x's {tuple(x.shape)} elements once, or twice ([cond ; uncond])")
-    for t, nm in ((x_out, "x_out"), (noise, "noise"), (pred_x0, "pred_x0")):
-        if t is not None and t.numel() != n:
-            raise ValueError(f"{nm} {tuple(t.shape)}: need x's shape {tuple(x.shape)}")
+    n = _update_operands(eps, x, [("x_out", x_out), ("noise", noise), ("pred_x0", pred_x0)])
     check(_lib.lib().gl_ddim_update(eps.data_ptr(), x.data_ptr(), _ptr(noise), eps.numel() // n, float(guidance), float(sqrt_at), float(s1m),
                                     float(sqrt_aprev), float(dir_coef), float(sigma), n, x_out.data_ptr(), _ptr(pred_x0), _stream()),
           "gl_ddim_update")
@@ -615,20 +625,7 @@ def dpmpp_update(eps: torch.Tensor, x: torch.Tensor, x_out: torch.Tensor, x0_out
     x_out = c_x * x + c_d * D (host.dpm_step_coefs).  ``eps``: the UNet output, x's shape, or twice x's batch = the [cond ; uncond] halves,
     combined with ``guidance`` inside the launch.  ``x0_old`` None = a first-order step (``w0`` must be 0).  ``x0_out`` receives x0, the
     history of the next step; ``x_out`` may be ``x`` and ``x0_out`` may be ``x0_old``.  Bit-identical to the torch fp32 expression."""
-    for t, n in ((eps, "eps"), (x, "x"), (x_out, "x_out"), (x0_out, "x0_out"), (x0_old, "x0_old")):
-        if t is None:
-            if n != "x0_old":
-                raise ValueError(f"{n}: required")
-            continue
-        _req(t, F32, n, 4)
-        if not t.is_contiguous():
-            raise ValueError(f"{n}: need a contiguous tensor")
-    n = x.numel()
-    if n == 0 or eps.numel() not in (n, 2 * n):
-        raise ValueError(f"eps {tuple(eps.shape)}: need x's {tuple(x.shape)} elements once, or twice ([cond ; uncond])")
-    for t, nm in ((x_out, "x_out"), (x0_out, "x0_out"), (x0_old, "x0_old")):
-        if t is not None and t.numel() != n:
-            raise ValueError(f"{nm} {tuple(t.shape)}: need x's shape {tuple(x.shape)}")
+    n = _update_operands(eps, x, [("x_out", x_out), ("x0_out", x0_out), ("x0_old", x0_old)], required=("eps", "x", "x_out", "x0_out"))
     if x0_old is None and w0 != 0:
         raise ValueError(f"w0 = {w0} without x0_old: a first-order step has no history term")
     check(_lib.lib().gl_dpmpp_update(eps.data_ptr(), x.data_ptr(), _ptr(x0_old), eps.numel() // n, float(guidance), float(sqrt_at), float(s1m),

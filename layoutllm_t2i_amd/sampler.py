@@ -27,12 +27,16 @@ double evaluation, Adams-Bashforth history of <= 3 eps), but:
     x = q_sample(x0, t) * mask + (1 - mask) * x, as one fused in-place fp32 HIP kernel (gl_latent_blend, bit-identical to
     the torch expression), with the q_sample noise drawn by ``torch.randn_like(x0)`` before the step's own draws.
 
-What the samplers share (the hoisted conditioning, the running latent, the per-step fuser scale and first-conv switch, the masked blend)
-lives in ``_Sampler``; each class adds its schedule and its loop.
+One path: ``_Sampler`` owns ``sample()``, the loop, the schedule cache and what every step does first (the hoisted conditioning, the running
+latent, the per-step fuser scale and first-conv switch, the masked blend); a class adds its schedule tables, what it allocates before the loop
+and one step.  The switch is stated once as well: one ``SamplerSpec`` record per sampler (its ``args`` keys with defaults, validators and the
+constructor keyword each feeds, and what it refuses of the others' keys) in ``SAMPLER_TABLE``, read by ``resolve_sampler`` -- the only place
+that turns the per-call keys into a class and its keywords; interface.py, gligen_inference.py, txt2img.py and train_rl.py go through it.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from dataclasses import dataclass
+from typing import Callable, Tuple
 
 import numpy as np
 import torch
@@ -41,7 +45,11 @@ from . import host, ops
 
 
 class _Sampler(object):
-    """The state and the per-step prologue the samplers share."""
+    """``sample()``, the loop and the schedule cache of every sampler.  A subclass supplies ``tag`` (the prefix of its engine buffers),
+    ``make_schedule`` with its own signature and refusals (it hands ``_schedule`` a key and the tables' maker), ``_sample_schedule`` (what
+    ``sample()`` passes to ``make_schedule`` behind S), ``_alloc`` (what it allocates before the loop) and ``_step`` (one step)."""
+    tag = None
+    _sample_schedule = ()
 
     def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None):
         self.diffusion = diffusion
@@ -51,6 +59,39 @@ class _Sampler(object):
         self.schedule = schedule
         self.alpha_generator_func = alpha_generator_func
         self.set_alpha_scale = set_alpha_scale
+        self._sched_key = None
+
+    def _schedule(self, key, make) -> None:
+        """the one schedule cache: ``make()`` gives the tables of ``key`` unless they are the ones in place"""
+        if self._sched_key != key:
+            self._set_tables(make())
+            self._sched_key = key
+
+    @torch.no_grad()
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+        self.make_schedule(S, *self._sample_schedule)
+        return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    @torch.no_grad()
+    def _sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+        """The loop over the schedule in place (``plms_sampling`` / ``ddim_sampling`` / ``dpm_sampling`` by the classes' own names)."""
+        x_a, reps, time_range, alphas, blend = self._begin(self.tag, shape, input, uc, guidance_scale, mask, x0)
+        model = self.model
+        total_steps = self.ddim_timesteps.shape[0]
+        state = self._alloc(x_a)
+
+        def at(t):
+            """the evaluation's arguments of an engine step at timestep ``t``, read when the step is issued"""
+            return dict(t=float(int(t)), reps=reps, guidance=float(guidance_scale), fuser_scale=model.fuser_scale, sd_conv=model.use_sd_conv)
+
+        for i, step in enumerate(time_range):
+            self._step_prologue(i, step, alphas, blend)
+            self._step(state, x_a, at, i, time_range, total_steps - i - 1)
+        input["x"] = x_a.clone()
+        return input["x"]
+
+    def _alloc(self, x_a):
+        return None
 
     def _acp(self) -> np.ndarray:
         acp = self.diffusion.alphas_cumprod.detach().cpu().numpy().astype(np.float32)
@@ -118,64 +159,51 @@ class _Sampler(object):
 
 
 class PLMSSampler(_Sampler):
+    tag = "plms"
+    plms_sampling = _Sampler._sampling
+
     def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None):
         super().__init__(diffusion, model, schedule, alpha_generator_func, set_alpha_scale)
         self.mirror_rng = True     # plms.py:138 draws randn_like(x) * 0 on every update
-        self._sched_S = None
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=False):
         if ddim_eta != 0:
             raise ValueError('ddim_eta must be 0 for PLMS')
         if ddim_discretize != "uniform":
             raise NotImplementedError(ddim_discretize)
-        if self._sched_S == ddim_num_steps:
-            return
-        self._set_tables(host.make_schedule(ddim_num_steps, self._acp()))
-        self._sched_S = ddim_num_steps
+        self._schedule((ddim_num_steps,), lambda: host.make_schedule(ddim_num_steps, self._acp()))
 
-    @torch.no_grad()
-    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
-        self.make_schedule(ddim_num_steps=S)
-        return self.plms_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
-
-    @torch.no_grad()
-    def plms_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
-        x_a, reps, time_range, alphas, blend = self._begin("plms", shape, input, uc, guidance_scale, mask, x0)
-        model, eng = self.model, self.model.engine
-        total_steps = self.ddim_timesteps.shape[0]
-
+    def _alloc(self, x_a):
+        eng = self.model.engine
         ring = [eng.buf(f"plms.e{j}", tuple(x_a.shape), torch.float32) for j in range(4)]
-        x_mid = eng.buf("plms.xmid", tuple(x_a.shape), torch.float32)
-        old: List[torch.Tensor] = []      # newest last, <= 3 entries; tensors are slots of `ring`
-        free = list(ring)
+        # old: the eps history, newest last, <= 3 entries; its tensors and the free ones are slots of `ring`
+        return dict(x_mid=eng.buf("plms.xmid", tuple(x_a.shape), torch.float32), old=[], free=list(ring))
 
-        def step_eval(x_eval, t_val, e_out, e_terms, coefs, div, index, x_out):
+    def _step(self, st, x_a, at, i, time_range, index):
+        old, free = st["old"], st["free"]
+
+        def step_eval(x_eval, t_val, e_out, e_terms, coefs, div, x_out):
             """one gl_plms_step: UNet (2B batch) -> CFG combine into e_out -> e' -> x_out = update of x_a"""
             sq_at, s1m, sq_ap, dirc = host.step_coefs(self._sched, index)
             if self.mirror_rng:
                 torch.randn_like(x_a)          # plms.py:138 draws noise * sigma (= 0) on every update: keep the RNG stream aligned
-            eng.plms_step(x_eval, x_a, x_out, e_out, e_terms, coefs, div, float(t_val), reps, float(guidance_scale),
-                          model.fuser_scale, model.use_sd_conv, sq_at, s1m, sq_ap, dirc)
+            a = at(t_val)              # plms_step takes its arguments by position: callers wrap it with that signature
+            self.model.engine.plms_step(x_eval, x_a, x_out, e_out, e_terms, coefs, div, a["t"], a["reps"], a["guidance"], a["fuser_scale"],
+                                        a["sd_conv"], sq_at, s1m, sq_ap, dirc)
 
-        for i, step in enumerate(time_range):
-            self._step_prologue(i, step, alphas, blend)
-            index = total_steps - i - 1
-            t_next = time_range[min(i + 1, len(time_range) - 1)]
-            e_t = free.pop()
-            if len(old) == 0:
-                # step 0 evaluates twice (plms.py:144-150): x_mid from e_t alone, then e' = (e_t + e(x_mid, t_next)) / 2
-                step_eval(x_a, int(step), e_t, [e_t], (1.0,), 1.0, index, x_mid)
-                e_next = free[-1]                                   # scratch slot, not kept
-                coefs, div = host.PLMS_COEFS[0]
-                step_eval(x_mid, int(t_next), e_next, [e_t, e_next], coefs, div, index, x_a)
-            else:
-                coefs, div = host.PLMS_COEFS[min(len(old), 3)]
-                step_eval(x_a, int(step), e_t, [e_t] + old[::-1][:len(coefs) - 1], coefs, div, index, x_a)
-            old.append(e_t)
-            if len(old) >= 4:
-                free.append(old.pop(0))
-        input["x"] = x_a.clone()
-        return input["x"]
+        e_t = free.pop()
+        if len(old) == 0:
+            # step 0 evaluates twice (plms.py:144-150): x_mid from e_t alone, then e' = (e_t + e(x_mid, t_next)) / 2
+            step_eval(x_a, time_range[i], e_t, [e_t], (1.0,), 1.0, st["x_mid"])
+            e_next = free[-1]                                   # scratch slot, not kept
+            coefs, div = host.PLMS_COEFS[0]
+            step_eval(st["x_mid"], time_range[min(i + 1, len(time_range) - 1)], e_next, [e_t, e_next], coefs, div, x_a)
+        else:
+            coefs, div = host.PLMS_COEFS[min(len(old), 3)]
+            step_eval(x_a, time_range[i], e_t, [e_t] + old[::-1][:len(coefs) - 1], coefs, div, x_a)
+        old.append(e_t)
+        if len(old) >= 4:
+            free.append(old.pop(0))
 
 
 class DDIMSampler(_Sampler):
@@ -192,6 +220,8 @@ class DDIMSampler(_Sampler):
 
     RNG order per step, as in the reference: with a mask ``torch.randn_like(x0)`` (q_sample) first, then one ``torch.randn_like`` of the
     latent's shape -- drawn when sigma is 0 too (ddim.py:132 multiplies it by 0) and then not handed to the kernel."""
+    tag = "ddim"
+    ddim_sampling = _Sampler._sampling
 
     def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None, eta=0.0, discretize="uniform"):
         super().__init__(diffusion, model, schedule, alpha_generator_func, set_alpha_scale)
@@ -199,35 +229,18 @@ class DDIMSampler(_Sampler):
         if discretize not in host.DDIM_DISCRETIZE:
             raise ValueError(f"ddim_discretize = {discretize!r}: one of {host.DDIM_DISCRETIZE}")
         self.discretize = discretize
-        self._sched_key = None
+        # unlike the reference's, sample() does NOT reset eta to 0 (nor the discretisation to "uniform"): it uses the constructor's
+        self._sample_schedule = (self.discretize, self.eta)
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.):
-        key = (int(ddim_num_steps), ddim_discretize, float(ddim_eta))
-        if self._sched_key == key:
-            return
-        self._set_tables(host.make_ddim_schedule(ddim_num_steps, self._acp(), ddim_discretize, ddim_eta))
-        self._sched_key = key
+        self._schedule((int(ddim_num_steps), ddim_discretize, float(ddim_eta)),
+                       lambda: host.make_ddim_schedule(ddim_num_steps, self._acp(), ddim_discretize, ddim_eta))
 
-    @torch.no_grad()
-    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
-        """Unlike the reference's, this does NOT reset eta to 0 (nor the discretisation to "uniform"): it uses the constructor's."""
-        self.make_schedule(ddim_num_steps=S, ddim_discretize=self.discretize, ddim_eta=self.eta)
-        return self.ddim_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
-
-    @torch.no_grad()
-    def ddim_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
-        x_a, reps, time_range, alphas, blend = self._begin("ddim", shape, input, uc, guidance_scale, mask, x0)
-        model, eng = self.model, self.model.engine
-        total_steps = self.ddim_timesteps.shape[0]
-        for i, step in enumerate(time_range):
-            self._step_prologue(i, step, alphas, blend)
-            sq_at, s1m, sq_ap, dirc, sigma = host.ddim_step_coefs(self._sched, total_steps - i - 1)
-            noise = torch.randn_like(x_a)      # ddim.py:132 draws on every step, sigma 0 included: keep the RNG stream aligned
-            eng.ddim_step(x_a, x_a, t=float(int(step)), reps=reps, guidance=float(guidance_scale), fuser_scale=model.fuser_scale,
-                          sd_conv=model.use_sd_conv, sqrt_at=sq_at, s1m=s1m, sqrt_aprev=sq_ap, dir_coef=dirc, sigma=sigma,
-                          noise=noise.to(self.device, torch.float32).contiguous() if sigma != 0 else None)
-        input["x"] = x_a.clone()
-        return input["x"]
+    def _step(self, st, x_a, at, i, time_range, index):
+        sq_at, s1m, sq_ap, dirc, sigma = host.ddim_step_coefs(self._sched, index)
+        noise = torch.randn_like(x_a)      # ddim.py:132 draws on every step, sigma 0 included: keep the RNG stream aligned
+        self.model.engine.ddim_step(x_a, x_a, **at(time_range[i]), sqrt_at=sq_at, s1m=s1m, sqrt_aprev=sq_ap, dir_coef=dirc, sigma=sigma,
+                                    noise=noise.to(self.device, torch.float32).contiguous() if sigma != 0 else None)
 
 
 class DPMSolverSampler(_Sampler):
@@ -241,6 +254,8 @@ class DPMSolverSampler(_Sampler):
     first order; ``order`` 1 is DDIM with eta 0 in exponential-integrator form.  The history is ONE engine buffer, ``dpmpp.x0`` (the kernel
     reads the old x0 and writes the new one in place).  The sampler draws no noise: without a mask the result does not depend on the torch
     seed; with one, the only draw of a step is the blend's ``torch.randn_like(x0)``.  Everything in ``_Sampler`` is inherited unchanged."""
+    tag = "dpmpp"
+    dpm_sampling = _Sampler._sampling
 
     def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None, order=2, discretize="logsnr"):
         super().__init__(diffusion, model, schedule, alpha_generator_func, set_alpha_scale)
@@ -250,35 +265,97 @@ class DPMSolverSampler(_Sampler):
             raise ValueError(f"dpm_discretize = {discretize!r}: one of {host.DPM_DISCRETIZE}")
         self.order = int(order)
         self.discretize = discretize
-        self._sched_key = None
 
     def make_schedule(self, num_steps, discretize=None):
         discretize = self.discretize if discretize is None else discretize
-        key = (int(num_steps), discretize)
-        if self._sched_key == key:
-            return
-        self._set_tables(host.make_dpm_schedule(num_steps, self._acp(), discretize))
-        self._sched_key = key
+        self._schedule((int(num_steps), discretize), lambda: host.make_dpm_schedule(num_steps, self._acp(), discretize))
 
-    @torch.no_grad()
-    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
-        self.make_schedule(S)
-        return self.dpm_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+    def _alloc(self, x_a):
+        # hist: the x0 prediction of the step before, rewritten in place; prev: that step's node
+        return dict(hist=self.model.engine.buf("dpmpp.x0", tuple(x_a.shape), torch.float32), prev=None)
 
-    @torch.no_grad()
-    def dpm_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
-        x_a, reps, time_range, alphas, blend = self._begin("dpmpp", shape, input, uc, guidance_scale, mask, x0)
-        model, eng = self.model, self.model.engine
-        total_steps = self.ddim_timesteps.shape[0]
-        hist = eng.buf("dpmpp.x0", tuple(x_a.shape), torch.float32)      # the x0 prediction of the step before; rewritten in place
-        prev = None
-        for i, step in enumerate(time_range):
-            self._step_prologue(i, step, alphas, blend)
-            index = total_steps - i - 1
-            sq_at, s1m, c_x, c_d, w1, w0 = host.dpm_step_coefs(self._sched, index, prev, self.order)
-            eng.dpmpp_step(x_a, x_a, hist, t=float(int(step)), reps=reps, guidance=float(guidance_scale), fuser_scale=model.fuser_scale,
-                           sd_conv=model.use_sd_conv, sqrt_at=sq_at, s1m=s1m, c_x=c_x, c_d=c_d, w1=w1, w0=w0,
-                           x0_old=hist if w0 != 0 else None)
-            prev = index
-        input["x"] = x_a.clone()
-        return input["x"]
+    def _step(self, st, x_a, at, i, time_range, index):
+        sq_at, s1m, c_x, c_d, w1, w0 = host.dpm_step_coefs(self._sched, index, st["prev"], self.order)
+        self.model.engine.dpmpp_step(x_a, x_a, st["hist"], **at(time_range[i]), sqrt_at=sq_at, s1m=s1m, c_x=c_x, c_d=c_d, w1=w1, w0=w0,
+                                     x0_old=st["hist"] if w0 != 0 else None)
+        st["prev"] = index
+
+
+# ------------------------------------------------------------------------------------------- the switch: one record per sampler
+@dataclass(frozen=True)
+class Key:
+    name: str                                    # the per-call ``args`` key
+    default: object
+    kwarg: str                                   # the constructor keyword it feeds
+    check: Callable                              # value -> the validated value, or ValueError naming the key
+
+
+@dataclass(frozen=True)
+class SamplerSpec:
+    name: str                                    # args["sampler"]
+    cls: type
+    keys: Tuple[Key, ...] = ()                   # the args keys it owns
+    refuses: Tuple[Tuple[Tuple[str, ...], str], ...] = ()     # (keys of another sampler, the message when one of them is off its default)
+
+    def kwargs(self, values) -> dict:
+        """the constructor keywords out of resolve_sampler's values"""
+        return {k.kwarg: values[k.name] for k in self.keys}
+
+
+def _one_of(key, choices):
+    def check(v):
+        if v not in choices:
+            raise ValueError(f"{key} = {v!r}: one of {choices}")
+        return v
+    return check
+
+
+def _dpm_order(v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in host.DPM_ORDERS:
+        raise ValueError(f"dpm_order = {v!r}: one of {host.DPM_ORDERS}")
+    return int(v)
+
+
+# the wording of the cross-sampler refusals is irregular and kept as text
+_NEEDS_DPM = ((("dpm_order",), "dpm_order = {dpm_order} with sampler = {sampler!r}: it needs sampler = 'dpmpp_2m'"),
+              (("dpm_discretize",), "dpm_discretize = {dpm_discretize!r} with sampler = {sampler!r}: it needs sampler = 'dpmpp_2m'"))
+DEFAULT_SAMPLER = "plms"
+SAMPLER_TABLE = {s.name: s for s in (         # in the order the samplers arrived, which is the order of the refusals
+    SamplerSpec("plms", PLMSSampler, refuses=(
+        (("ddim_eta", "ddim_discretize"), "ddim_eta = {ddim_eta} / ddim_discretize = {ddim_discretize!r} with sampler = 'plms': PLMS is "
+                                          "deterministic on uniform steps; eta and 'quad' need sampler = 'ddim'"),) + _NEEDS_DPM),
+    SamplerSpec("ddim", DDIMSampler, keys=(Key("ddim_eta", 0.0, "eta", host.check_ddim_eta),
+                                           Key("ddim_discretize", "uniform", "discretize", _one_of("ddim_discretize", host.DDIM_DISCRETIZE))),
+                refuses=_NEEDS_DPM),
+    SamplerSpec("dpmpp_2m", DPMSolverSampler, keys=(Key("dpm_order", 2, "order", _dpm_order),
+                                                   Key("dpm_discretize", "logsnr", "discretize", _one_of("dpm_discretize", host.DPM_DISCRETIZE))),
+                refuses=((("ddim_eta",), "ddim_eta = {ddim_eta} with sampler = 'dpmpp_2m': the solver is deterministic; eta needs sampler = 'ddim'"),
+                         (("ddim_discretize",), "ddim_discretize = {ddim_discretize!r} with sampler = 'dpmpp_2m': its grid is args[\"dpm_discretize\"]"))),
+)}
+SAMPLERS = tuple(SAMPLER_TABLE)                                                        # ("plms", "ddim", "dpmpp_2m")
+SAMPLER_KEYS = ("sampler",) + tuple(k.name for s in SAMPLER_TABLE.values() for k in s.keys)      # every per-call key of the switch
+
+
+def resolve_sampler(keys, upto=None) -> Tuple[SamplerSpec, dict]:
+    """The sampler switch, checked in one place before any encoder or kernel runs.  ``keys``: a mapping that may hold any of SAMPLER_KEYS (a
+    whole ``args`` dict will do; what is absent is at its default).  Returns the sampler's record and every key's validated value by name
+    (``spec.kwargs(values)``: the constructor's keywords).  ValueError, in this order: an unknown sampler; then per sampler of the table its
+    own keys' values (eta negative or not finite, an unknown discretisation, an order that is no int of DPM_ORDERS), followed by the refusals
+    between that sampler and the ones before it -- a key off its default under a sampler that does not own it.  ``upto``: stop behind that
+    sampler's stage, leaving the later samplers' keys unjudged and out of the values (interface.check_sampler_args, which stops at "ddim")."""
+    name = keys.get("sampler", DEFAULT_SAMPLER)
+    if name not in SAMPLERS:
+        raise ValueError(f"sampler = {name!r}: one of {SAMPLERS}")
+    spec = SAMPLER_TABLE[name]
+    values, defaults, pending, chosen = {"sampler": name}, {}, list(spec.refuses), False
+    for owner in SAMPLER_TABLE.values():
+        for k in owner.keys:
+            values[k.name], defaults[k.name] = k.check(keys.get(k.name, k.default)), k.default
+        chosen = chosen or owner is spec
+        for refusal in [r for r in pending if chosen and all(k in values for k in r[0])]:
+            pending.remove(refusal)
+            if any(values[k] != defaults[k] for k in refusal[0]):
+                raise ValueError(refusal[1].format(**values))
+        if owner.name == upto:
+            break
+    return spec, values

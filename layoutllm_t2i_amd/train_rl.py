@@ -34,8 +34,7 @@ def generate_with(all_models, clip_model=None, clip_processor=None, device=None,
     from . import interface
     more = {k: v for k, v in dict(sampler=sampler, steps=steps, dpm_order=dpm_order, dpm_discretize=dpm_discretize).items() if v is not None}
     if more:
-        interface.check_dpm_args(interface.check_sampler_args(more.get("sampler", "plms"))[0], more.get("dpm_order", 2),
-                                 more.get("dpm_discretize", "logsnr"))
+        interface.resolve_sampler(more)         # every key of the switch that was given, judged the way the rollout's call will judge it
 
     def generate(captions, categories, bboxes):
         if not more:

@@ -25,6 +25,7 @@ from . import interface
 from .family import FAMILIES, family_of
 from .policy import CandidatePool, PolicyNetwork, embed_texts
 from .prompting import build_prompt, convert_xcycwh_to_ltrb, convert_xywh_to_ltrb, extract_prediction
+from .sampler import DEFAULT_SAMPLER
 
 BOX_FAMILIES = tuple(f.name for f in FAMILIES.values() if f.boxes)
 
@@ -58,7 +59,7 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
     CPU generator per batch, as ``generate_one_image`` draws it.  ``folder``: save ``{prompt}_{i}.jpg`` there (``draw_boxes``: with the
     layout drawn on the saved copies).  ``instruction``: the wording of the LLM prompt (prompting.build_prompt).  ``sampler`` / ``ddim_eta``:
     handed through as ``args["sampler"]`` / ``args["ddim_eta"]`` ("ddim" with eta >= 0; checked before the policy or the LLM runs);
-    ``dpm_order`` / ``dpm_discretize``: ``args["dpm_order"]`` / ``args["dpm_discretize"]`` of ``sampler="dpmpp_2m"`` (interface.check_dpm_args;
+    ``dpm_order`` / ``dpm_discretize``: ``args["dpm_order"]`` / ``args["dpm_discretize"]`` of ``sampler="dpmpp_2m"`` (sampler.resolve_sampler;
     with ``steps=20`` an image costs 20 UNet evaluations in place of PLMS's 51).
     Returns dict(images, categories, bboxes_ltrb, cids, prompt_text, llm_output)."""
     model = all_models[0]
@@ -69,8 +70,10 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
         raise ValueError(f"num_per_prompt = {num_per_prompt}, batch_size = {batch_size}: both must be >= 1")
     if starting_noise is not None and (starting_noise.dim() != 4 or starting_noise.shape[0] != num_per_prompt):
         raise ValueError(f"starting_noise {tuple(starting_noise.shape)}: expected [num_per_prompt = {num_per_prompt}, 4, h, w]")
-    sampler, ddim_eta, _ = interface.check_sampler_args(sampler, ddim_eta)
-    dpm_order, dpm_discretize = interface.check_dpm_args(sampler, dpm_order, dpm_discretize, ddim_eta)
+    given = dict(sampler=sampler, ddim_eta=ddim_eta, dpm_order=dpm_order, dpm_discretize=dpm_discretize)
+    spec, values = interface.resolve_sampler(given)
+    # handed on: nothing for the default sampler, else the sampler and those of its own keys this entry takes
+    sampler_args = {} if spec.name == DEFAULT_SAMPLER else {k: values[k] for k in ("sampler", *(key.name for key in spec.keys)) if k in given}
     towers = pool.towers if pool.towers is not None else clip_model
     if towers is None:
         raise ValueError("no text tower for the prompt: build the pool with CandidatePool.from_captions, or pass clip_model")
@@ -95,10 +98,7 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
     while len(images) < num_per_prompt:
         n = min(batch_size, num_per_prompt - len(images))
         args = dict(batch_size=n, no_plms=False, guidance_scale=guidance_scale)
-        if sampler == "dpmpp_2m":
-            args.update(sampler=sampler, dpm_order=dpm_order, dpm_discretize=dpm_discretize)
-        elif sampler != "plms":
-            args.update(sampler=sampler, ddim_eta=ddim_eta)
+        args.update(sampler_args)
         if steps is not None:
             args["steps"] = int(steps)
         noise = torch.randn(n, 4, h, w) if starting_noise is None else starting_noise[len(images):len(images) + n]

@@ -266,3 +266,25 @@ def test_sampler_constructor_and_make_schedule_arguments():
         p.make_schedule(10, ddim_eta=0.5)
     with pytest.raises(NotImplementedError):
         p.make_schedule(10, ddim_discretize="quad")
+
+
+def test_plms_sampler_calls_plms_step_by_position():
+    """``UNetEngine.plms_step`` takes every argument by position, and callers that time it wrap it with exactly that signature (the
+    benchmark does): the sampler must not hand any of them over by keyword."""
+    calls = []
+
+    class _E(_StubEngine):
+        def plms_step(self, x_eval, x_base, x_out, e_out, e_terms, coefs, div, t, reps, guidance, fuser_scale, sd_conv, *sched):
+            calls.append((t, reps, guidance, fuser_scale, sd_conv, sched))
+            return x_out
+
+    m = _StubModel()
+    m.engine = _E()
+    x = torch.zeros(2, 4, 16, 16)
+    PLMSSampler(LatentDiffusion(), m).sample(S=4, shape=tuple(x.shape), input=dict(x=x), uc=torch.zeros(2, 77, 768), guidance_scale=7.5)
+    sched = host.make_schedule(4, host.alphas_cumprod())
+    ts = [float(t) for t in sched["ddim_timesteps"][::-1]]
+    assert len(calls) == 5                                                        # step 0 evaluates twice
+    assert [c[0] for c in calls] == [ts[0], ts[1]] + ts[1:]
+    assert all(c[1:5] == (2, 7.5, 1.0, False) for c in calls)
+    assert [c[5] for c in calls] == [tuple(host.step_coefs(sched, i)) for i in (3, 3, 2, 1, 0)]

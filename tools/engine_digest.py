@@ -29,8 +29,8 @@ STRICT = {50: 1, 51: 1}
 STRICT_NO_W3 = {50: 1, 51: 0}
 
 
-def case(name, cfg="text", B=2, hw=16, reps=1, t=481.0, fs=1.0, sd=False, graph=True, opts=None, plms=False, extra_bs=0):
-    return dict(name=name, cfg=cfg, B=B, hw=hw, reps=reps, t=t, fs=fs, sd=sd, graph=graph, opts=opts or {}, plms=plms, extra_bs=extra_bs)
+def case(name, cfg="text", B=2, hw=16, reps=1, t=481.0, fs=1.0, sd=False, graph=True, opts=None, plms=False, extra_bs=0, step=None):
+    return dict(name=name, cfg=cfg, B=B, hw=hw, reps=reps, t=t, fs=fs, sd=sd, graph=graph, opts=opts or {}, plms=plms, extra_bs=extra_bs, step=step)
 
 
 # B = samples of the latent; the conditioning batch is B * reps ([cond ; uncond] with reps = 2)
@@ -44,6 +44,13 @@ CASES = [
     case("text_2b_shared_prefix", reps=2),
     case("text_2b_per_sample_t", reps=2, t=[981.0, 481.0, 21.0, 1.0]),
     case("text_plms_step", reps=2, plms=True),
+    # step: (entry, with its optional operand -- DDIM: noise and pred_x0; DPM: the history of a second-order step)
+    case("text_ddim_step", reps=2, step=("ddim", False)),
+    case("text_ddim_step_noise_pred_x0", reps=2, step=("ddim", True)),
+    case("text_ddim_step_eager_1b", graph=False, step=("ddim", True)),
+    case("text_dpmpp_step_first_order", reps=2, step=("dpmpp", False)),
+    case("text_dpmpp_step_second_order", reps=2, step=("dpmpp", True)),
+    case("text_dpmpp_step_8x8_1b", B=1, hw=8, step=("dpmpp", True)),
     case("text_8x8", B=1, hw=8),
     case("text_rect_16x24", hw=(16, 24)),
     case("text_32x32_third_pass", B=1, hw=32, reps=2),                 # 2B * 32 * 32 = 2048 rows at the first level: option 45's third pass
@@ -102,6 +109,22 @@ for c in CASES:
         e_out, x_out = torch.empty_like(x), torch.empty_like(x)
         eng.plms_step(x, x, x_out, e_out, [e_out] + old, coefs, div, t, reps, 7.5, c["fs"], c["sd"], *host.step_coefs(host.make_schedule(50, host.alphas_cumprod()), 30))
         out = torch.cat([e_out, x_out], 0)
+    elif c["step"]:
+        kind, full = c["step"]
+        g = torch.Generator().manual_seed(13)
+        other = torch.randn(x.shape, generator=g).to(dev)                # DDIM's noise / DPM's x0 of the step before
+        x_out, aux = torch.empty_like(x), torch.zeros_like(x)
+        ev = dict(t=t, reps=reps, guidance=7.5, fuser_scale=c["fs"], sd_conv=c["sd"])
+        if kind == "ddim":
+            sq_at, s1m, sq_ap, dirc, sigma = host.ddim_step_coefs(host.make_ddim_schedule(50, host.alphas_cumprod(), "uniform", 1.0), 30)
+            eng.ddim_step(x, x_out, **ev, sqrt_at=sq_at, s1m=s1m, sqrt_aprev=sq_ap, dir_coef=dirc, sigma=sigma if full else 0.0,
+                          noise=other if full else None, pred_x0=aux if full else None)
+        else:
+            sched = host.make_dpm_schedule(20, host.alphas_cumprod())
+            sq_at, s1m, c_x, c_d, w1, w0 = host.dpm_step_coefs(sched, 10, 11 if full else None)
+            aux.copy_(other)                                             # the history buffer: read (second order) and rewritten in place
+            eng.dpmpp_step(x, x_out, aux, **ev, sqrt_at=sq_at, s1m=s1m, c_x=c_x, c_d=c_d, w1=w1, w0=w0, x0_old=aux if full else None)
+        out = torch.cat([x_out, aux], 0)
     else:
         out = eng.forward(x, t, c["fs"], c["sd"], reps)
         if c["graph"]:
