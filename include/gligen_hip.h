@@ -370,6 +370,15 @@ int gl_ddim_update(const float* eps, const float* x, const float* noise, int32_t
  * GL_ERR_BAD_ARG: reps other than 1 or 2, n <= 0, NULL eps / x / x_out / x0_out, x0_old == NULL with w0 != 0. */
 int gl_dpmpp_update(const float* eps, const float* x, const float* x0_old, int32_t reps, float guidance, float sqrt_at, float s1m,
                     float c_x, float c_d, float w1, float w0, int64_t n, float* x_out, float* x0_out, void* stream);
+/* gl_cfg3_combine: classifier-free guidance with separate text and layout scales (the two-condition form of InstructPix2Pix, Brooks et al.,
+ * arXiv 2211.09800, eq. 3), additive to ABI 15.  eps3b = the UNet output fp32 [3n] of the conditioning batch [cond ; text-only ; uncond]:
+ * e_c saw the prompt and the grounding, e_t the prompt and the null grounding, e_u neither.
+ *     e_out = (e_u + s_text * (e_t - e_u)) + s_layout * (e_c - e_t)
+ * left to right with FP contraction off: given the same eps, bit-identical to the torch fp32 expression.  s_layout == s_text is
+ * gl_cfg_combine's e_u + s * (e_c - e_u) up to rounding (e_t cancels); s_layout == 0 weights e_c by zero.  e_out fp32 [n] aliases nothing.
+ * n % 4 == 0 and 16-byte pointers take the float4 path, everything else the scalar one; the grid is gl_ddim_update's.
+ * GL_ERR_BAD_ARG, before any device call: n <= 0, NULL eps3b / e_out. */
+int gl_cfg3_combine(const float* eps3b, float s_text, float s_layout, int64_t n, float* e_out, void* stream);
 int gl_pack_latent(const float* x, int32_t B, int32_t C, int32_t hw, int32_t Cpad, int32_t reps, int32_t split, void* out,
                    void* stream);
 /* gl_pack_latent_extra: gl_pack_latent over the channel concatenation of TWO sources (the first-conv input of an inpaint_mode UNet,
@@ -591,6 +600,23 @@ typedef struct gl_dpmpp_step_args {
 } gl_dpmpp_step_args;
 int gl_dpmpp_step(gl_engine* e, const gl_dpmpp_step_args* a, void* stream);
 int gl_sizeof_dpmpp_step_args(void);
+/* gl_cfg3_eval: one three-branch denoiser evaluation + one gl_cfg3_combine launch, additive to ABI 15: eps = UNet(x, t) with reps = 3 over
+ * the conditioning batch [cond ; text-only ; uncond] into the handle's own output buffer (graph-cached like gl_unet_forward), then
+ * e_out = (e_u + s_text * (e_t - e_u)) + s_layout * (e_c - e_t).  It updates no latent: the caller hands e_out fp32 [Bn / 3, C, h, w] to
+ * gl_plms_update, or to gl_ddim_update / gl_dpmpp_update with reps = 1.  The evaluation's fields are those of the step structs; reps must
+ * be 3 (gl_plms_step / gl_ddim_step / gl_dpmpp_step keep refusing every reps but 1 and 2) and guidance is not read -- the scales are s_text
+ * and s_layout.  The shared cond / uncond prefix (option 44) is a reps == 2 form and does not apply.  Refuses what those entries refuse:
+ * NULL x / e_out, a reps other than its own (GL_ERR_BAD_ARG), in_channels != out_channels (GL_ERR_UNSUPPORTED), everything
+ * gl_unet_forward refuses; and a conditioning batch that is no multiple of 3 (GL_ERR_BAD_ARG with a gl_last_error message), before
+ * anything is launched. */
+typedef struct gl_cfg3_eval_args {
+    const float* x;  float* e_out;                                   /* fp32 [Bn / 3, C, h, w] */
+    float t;  int32_t reps;  float guidance;  float fuser_scale;  int32_t sd_conv;
+    float s_text, s_layout;
+    int32_t use_graph;
+} gl_cfg3_eval_args;
+int gl_cfg3_eval(gl_engine* e, const gl_cfg3_eval_args* a, void* stream);
+int gl_sizeof_cfg3_eval_args(void);
 /* introspection for tests / tools */
 int64_t gl_pool_bytes(const gl_engine* e);
 int gl_num_launches(const gl_engine* e);       /* kernel launches of the last eagerly executed / captured forward */

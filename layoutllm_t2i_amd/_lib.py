@@ -120,7 +120,7 @@ class VaeConfigC(C.Structure):
                 ("embed_dim", i32), ("scale_factor", f32)]
 
 
-# what the three step structs share: the evaluation's fields sit between a struct's operands and its scalars, use_graph closes it
+# what the step structs share: the evaluation's fields sit between a struct's operands and its scalars, use_graph closes it
 _STEP_EVAL = [("t", f32), ("reps", i32), ("guidance", f32), ("fuser_scale", f32), ("sd_conv", i32)]
 _STEP_TAIL = [("use_graph", i32)]
 
@@ -155,6 +155,16 @@ class DpmppStepArgs(C.Structure):
         ("x0_old", vp), ("x0_out", vp),
         *_STEP_EVAL,
         ("sqrt_at", f32), ("s1m", f32), ("c_x", f32), ("c_d", f32), ("w1", f32), ("w0", f32),
+        *_STEP_TAIL,
+    ]
+
+
+class Cfg3EvalArgs(C.Structure):
+    """gl_cfg3_eval_args"""
+    _fields_ = [
+        ("x", vp), ("e_out", vp),
+        *_STEP_EVAL,
+        ("s_text", f32), ("s_layout", f32),
         *_STEP_TAIL,
     ]
 
@@ -223,6 +233,7 @@ PROTOTYPES = {
     "gl_timestep_embedding": (i32, [fp, i32, i32, vp, vp]),
     "gl_silu_f16": (i32, [vp, vp, i64, vp]),
     "gl_cfg_combine": (i32, [fp, f32, i64, fp, vp]),
+    "gl_cfg3_combine": (i32, [fp, f32, f32, i64, fp, vp]),
     "gl_plms_update": (i32, [fp, fp, fp, fp, fp, f32, f32, f32, f32, f32, f32, f32, f32, f32, i64, fp, vp]),
     "gl_ddim_update": (i32, [fp, fp, fp, i32, f32, f32, f32, f32, f32, f32, i64, fp, fp, vp]),
     "gl_dpmpp_update": (i32, [fp, fp, fp, i32, f32, f32, f32, f32, f32, f32, f32, i64, fp, fp, vp]),
@@ -272,6 +283,8 @@ PROTOTYPES = {
     "gl_sizeof_ddim_step_args": (i32, []),
     "gl_dpmpp_step": (i32, [vp, C.POINTER(DpmppStepArgs), vp]),
     "gl_sizeof_dpmpp_step_args": (i32, []),
+    "gl_cfg3_eval": (i32, [vp, C.POINTER(Cfg3EvalArgs), vp]),
+    "gl_sizeof_cfg3_eval_args": (i32, []),
     "gl_pool_bytes": (i64, [vp]),
     "gl_num_launches": (i32, [vp]),
     "gl_sizeof_unet_config": (i32, []),
@@ -359,6 +372,7 @@ def lib() -> C.CDLL:
     for cls, fn in ((GemmArgs, l.gl_sizeof_gemm_args), (ConvArgs, l.gl_sizeof_conv_args), (AttnArgs, l.gl_sizeof_attn_args),
                     (UNetConfigC, l.gl_sizeof_unet_config), (WeightInfo, l.gl_sizeof_weight_info),
                     (PlmsStepArgs, l.gl_sizeof_plms_step_args), (DdimStepArgs, l.gl_sizeof_ddim_step_args), (DpmppStepArgs, l.gl_sizeof_dpmpp_step_args),
+                    (Cfg3EvalArgs, l.gl_sizeof_cfg3_eval_args),
                     (RewardArgs, l.gl_sizeof_reward_args), (FFArgs, l.gl_sizeof_ff_args),
                     (VaeConfigC, l.gl_sizeof_vae_config), (GnArgs, l.gl_sizeof_gn_args),
                     (LayoutRewardArgs, l.gl_sizeof_layout_reward_args), (PolicyArgs, l.gl_sizeof_policy_args),

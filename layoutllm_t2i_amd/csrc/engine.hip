@@ -1582,12 +1582,13 @@ extern "C" int gl_unet_forward(gl_engine* e, const float* x, const float* t_dev,
 
 // What every sampler step does first, behind the entry's own pointer checks: the handle's option overrides, the reps check, the refusal of a
 // model whose output is no latent, then eps = UNet(x, t) into the handle's own ``out.eps``.  Hands back that buffer and n = its elements / reps,
-// the size of the latent.  ``a``: any of the three step structs (they share the fields read here).  The option scope ends with the forward:
-// the update launches behind it read no option.
+// the size of the latent.  ``a``: any of the step structs (they share the fields read here).  ``min_reps`` .. ``max_reps``: the batch multiples
+// the entry takes -- 1 and 2 for the three sampler steps, 3 alone for gl_cfg3_eval.  The option scope ends with the forward: the update
+// launches behind it read no option.
 template <typename Args>
-static int step_eval(gl_engine* e, const Args* a, const float* x, void* stream, float** eps_i, size_t* n) {
+static int step_eval(gl_engine* e, const Args* a, const float* x, void* stream, float** eps_i, size_t* n, int min_reps = 1, int max_reps = 2) {
     gl_opts_scope opts_scope(e->ovr);       // this handle's option overrides are in effect for the call
-    if (a->reps != 1 && a->reps != 2) return GL_ERR_BAD_ARG;
+    if (a->reps < min_reps || a->reps > max_reps) return GL_ERR_BAD_ARG;
     const gl_unet_config& cfg = e->cfg;
     if (cfg.in_channels != cfg.out_channels) return GL_ERR_UNSUPPORTED;
     const size_t ne = (size_t)e->Bn * cfg.out_channels * e->lat_h * e->lat_w;
@@ -1637,6 +1638,19 @@ extern "C" int gl_dpmpp_step(gl_engine* e, const gl_dpmpp_step_args* a, void* st
                            (int64_t)n, a->x_out, a->x0_out, stream);
 }
 
+extern "C" int gl_cfg3_eval(gl_engine* e, const gl_cfg3_eval_args* a, void* stream) {
+    if (!e || !a || !a->x || !a->e_out) return GL_ERR_BAD_ARG;
+    if (e->cond_set && (e->Bn % 3) != 0) {
+        e->err = "gl_cfg3_eval: the conditioning batch has " + std::to_string(e->Bn) + " samples, no multiple of 3 ([cond ; text-only ; uncond])";
+        return GL_ERR_BAD_ARG;
+    }
+    float* eps_i;
+    size_t n;
+    CK(step_eval(e, a, a->x, stream, &eps_i, &n, 3, 3));
+    // the thirds of the handle's own output -> the guided eps the caller's update reads
+    return gl_cfg3_combine(eps_i, a->s_text, a->s_layout, (int64_t)n, a->e_out, stream);
+}
+
 extern "C" int gl_set_handle_option(gl_engine* e, int key, int value) {
     return e ? gl_handle_set_option(e->ovr, key, value) : GL_ERR_BAD_ARG;
 }
@@ -1667,3 +1681,4 @@ extern "C" int gl_sizeof_weight_info(void) { return (int)sizeof(gl_weight_info);
 extern "C" int gl_sizeof_plms_step_args(void) { return (int)sizeof(gl_plms_step_args); }
 extern "C" int gl_sizeof_ddim_step_args(void) { return (int)sizeof(gl_ddim_step_args); }
 extern "C" int gl_sizeof_dpmpp_step_args(void) { return (int)sizeof(gl_dpmpp_step_args); }
+extern "C" int gl_sizeof_cfg3_eval_args(void) { return (int)sizeof(gl_cfg3_eval_args); }

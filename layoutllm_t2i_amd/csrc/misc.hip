@@ -212,6 +212,31 @@ __device__ __forceinline__ float guided_eps(float ec, const float& eu, int reps,
     return reps == 2 ? eu + guidance * (ec - eu) : ec;
 }
 
+// three-branch guidance on the [cond ; text-only ; uncond] thirds: e = (e_u + s_t * (e_t - e_u)) + s_l * (e_c - e_t), left to right.  With
+// s_l == s_t it is guided_eps up to rounding; with s_l == 0 the conditional third is weighted by zero
+__device__ __forceinline__ float guided_eps3(float ec, float et, float eu, float s_text, float s_layout) {
+    const float text = eu + s_text * (et - eu);
+    return text + s_layout * (ec - et);
+}
+
+// The combine of a three-branch evaluation as one launch: eps3b fp32 [3n] -> e fp32 [n].  e aliases nothing.  VEC = 4: n % 4 == 0 and
+// 16-byte pointers (then the thirds at eps3b + n and eps3b + 2n are 16-byte aligned too), one float4 per third per thread.
+template <int VEC>
+__global__ __launch_bounds__(256) void cfg3_combine_kernel(const float* __restrict__ eps3b, float s_text, float s_layout, size_t n,
+                                                           float* __restrict__ e) {
+    const size_t nvec = n / VEC;
+    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = v * VEC;
+        float ec[VEC], et[VEC], eu[VEC], o[VEC];
+        ew_load<VEC>(eps3b + i, ec);
+        ew_load<VEC>(eps3b + n + i, et);
+        ew_load<VEC>(eps3b + 2 * n + i, eu);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) o[j] = guided_eps3(ec[j], et[j], eu[j], s_text, s_layout);
+        ew_store<VEC>(e + i, o);
+    }
+}
+
 __global__ void cfg_combine_kernel(const float* __restrict__ eps2b, float guidance, size_t n, float* __restrict__ e) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float ec = eps2b[i];
@@ -590,6 +615,16 @@ extern "C" int gl_silu_f16(const void* x, void* y, int64_t n, void* stream) {
 extern "C" int gl_cfg_combine(const float* eps2b, float guidance, int64_t n, float* e_out, void* stream) {
     if (!eps2b || !e_out || n <= 0) return GL_ERR_BAD_ARG;
     cfg_combine_kernel<<<dim3(ew_blocks((size_t)n)), dim3(256), 0, (hipStream_t)stream>>>(eps2b, guidance, (size_t)n, e_out);
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_cfg3_combine(const float* eps3b, float s_text, float s_layout, int64_t n, float* e_out, void* stream) {
+    if (!eps3b || !e_out || n <= 0) return GL_ERR_BAD_ARG;
+    if (ew_vec4((size_t)n, {eps3b, e_out}))
+        cfg3_combine_kernel<4><<<dim3(ew_blocks((size_t)n / 4)), dim3(256), 0, (hipStream_t)stream>>>(eps3b, s_text, s_layout, (size_t)n, e_out);
+    else
+        cfg3_combine_kernel<1><<<dim3(ew_blocks((size_t)n)), dim3(256), 0, (hipStream_t)stream>>>(eps3b, s_text, s_layout, (size_t)n, e_out);
     GL_CHECK_LAUNCH();
     return 0;
 }

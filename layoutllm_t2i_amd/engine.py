@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import DdimStepArgs, DpmppStepArgs, PlmsStepArgs, check, init_device
+from ._lib import Cfg3EvalArgs, DdimStepArgs, DpmppStepArgs, PlmsStepArgs, check, init_device
 from .arch import UNetConfig
 from .weights import PackedWeights
 
@@ -369,3 +369,16 @@ class UNetEngine:
         a.sqrt_at, a.s1m, a.c_x, a.c_d, a.w1, a.w0 = float(sqrt_at), float(s1m), float(c_x), float(c_d), float(w1), float(w0)
         self._run_step("gl_dpmpp_step", a, t, reps, guidance, fuser_scale, sd_conv)
         return x_out
+
+    @torch.no_grad()
+    def cfg3_eval(self, x: torch.Tensor, e_out: torch.Tensor, *, t: float, fuser_scale: float, sd_conv: bool, s_text: float,
+                  s_layout: float) -> torch.Tensor:
+        """One gl_cfg3_eval: UNet(x, t) over the [cond ; text-only ; uncond] conditioning batch (reps = 3) into the engine's own eps buffer,
+        then ONE launch for e_out = (e_u + s_text * (e_t - e_u)) + s_layout * (e_c - e_t).  No latent is updated: ``e_out`` goes to
+        ``ops.plms_update``, or to ``ops.ddim_update`` / ``ops.dpmpp_update`` as a B-sized eps."""
+        self._check_step(x, 3, [("e_out", e_out)], required=("e_out",))
+        a = Cfg3EvalArgs()
+        a.x, a.e_out = x.data_ptr(), e_out.data_ptr()
+        a.s_text, a.s_layout = float(s_text), float(s_layout)
+        self._run_step("gl_cfg3_eval", a, t, 3, s_text, fuser_scale, sd_conv)      # (guidance: not read by the entry)
+        return e_out

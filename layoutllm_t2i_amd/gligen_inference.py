@@ -93,8 +93,9 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
         version = "openai/clip-vit-large-patch14"
         clip_model = CLIPModel.from_pretrained(version).to(device)
         clip_processor = CLIPProcessor.from_pretrained(version)
-    # per-call keys, handed on only when the config carries them: the step count and the sampler switch (sampler.resolve_sampler)
-    for k in ("steps",) + SAMPLER_KEYS:
+    # per-call keys, handed on only when the config carries them: the step count, the sampler switch (sampler.resolve_sampler) and the
+    # layout's guidance scale (interface.check_layout_guidance)
+    for k in ("steps",) + SAMPLER_KEYS + (interface.LAYOUT_GUIDANCE_KEY,):
         if k in (config if isinstance(config, dict) else vars(config)):
             args[k] = _get(config, k)
     images = interface.run_one_image(all_models, args, m, starting_noise, clip_model, clip_processor, device=device)

@@ -23,6 +23,7 @@ clamp -> *0.5+0.5 -> *255 -> astype(uint8) truncation.
 """
 from __future__ import annotations
 
+import math
 import os
 import warnings
 from functools import partial
@@ -633,10 +634,29 @@ def check_dpm_args(sampler="plms", dpm_order=2, dpm_discretize="logsnr", ddim_et
     return v["dpm_order"], v["dpm_discretize"]
 
 
+LAYOUT_GUIDANCE_KEY = "layout_guidance_scale"
+
+
+def check_layout_guidance(value, family=None):
+    """``args["layout_guidance_scale"]``, the layout's own guidance scale s_l next to ``guidance_scale`` = s_t (three-branch guidance,
+    sampler._Sampler), checked before any encoder or kernel runs.  None (the key absent: one scale for both) or a finite real >= 0 that is
+    no bool; anything else raises ValueError naming the key.  ``family`` (family.Family): a map family (canny / hed / depth / normal, sem)
+    refuses a number -- its map also enters through the first conv, which every branch shares, so a text-only branch is not defined there.
+    Returns None or the float."""
+    if value is None:
+        return None
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) or not math.isfinite(value) or value < 0:
+        raise ValueError(f"{LAYOUT_GUIDANCE_KEY} = {value!r}: None or a finite number >= 0")
+    if family is not None and family.extra_key is not None:
+        raise ValueError(f"{LAYOUT_GUIDANCE_KEY} given to a {family.label} checkpoint: its map also feeds the first conv, which the text-only "
+                         "branch would share; separate text and layout scales need a text, text_image or keypoint checkpoint")
+    return float(value)
+
+
 @torch.no_grad()
 def denoise(all_models, context, uc, relations, grounding_batch, starting_noise, alpha_type=None, guidance_scale=7.5,
             steps=PLMS_STEPS, mask=None, x0=None, inpainting_extra_input=None, grounding_extra_input=None, sampler="plms", ddim_eta=0.0,
-            ddim_discretize="uniform", dpm_order=2, dpm_discretize="logsnr"):
+            ddim_discretize="uniform", dpm_order=2, dpm_discretize="logsnr", layout_guidance_scale=None):
     """The denoising hot path proper, from conditioning tensors to the final latent
     (run_batch_images lines interface.py:505-539 without text/VAE stages).  ``mask`` [1|B, 1, h, w] (1 = keep) and ``x0``
     [1|B, 4, h, w] (the encoded input image): inpainting, plms.py:95-99.  The latent's shape [B, 4, h, w] is ``starting_noise``'s
@@ -646,10 +666,13 @@ def denoise(all_models, context, uc, relations, grounding_batch, starting_noise,
     [B, 3, H, W]: the map a spatial model's grounding downsampler reads (required there, ignored by every other model).  ``sampler``: "plms"
     or "ddim" (sampler.DDIMSampler, with ``ddim_eta`` >= 0 and ``ddim_discretize`` "uniform" | "quad"), or "dpmpp_2m"
     (sampler.DPMSolverSampler, with ``dpm_order`` 2 | 1 and ``dpm_discretize`` "logsnr" | "quad" | "uniform"; there ``steps`` bounds the
-    number of UNet evaluations, 20 is the usual choice); all five go through sampler.resolve_sampler first."""
+    number of UNet evaluations, 20 is the usual choice); all five go through sampler.resolve_sampler first.  ``layout_guidance_scale``:
+    None, or the layout's own scale s_l >= 0 -- e = (e_u + s_t (e_t - e_u)) + s_l (e_c - e_t) with s_t = ``guidance_scale`` and e_t the
+    branch that reads the prompt and the null grounding (check_layout_guidance; any sampler; refused on a map family)."""
     model, autoencoder, text_encoder, diffusion, config = all_models
     spec, values = resolve_sampler(dict(sampler=sampler, ddim_eta=ddim_eta, ddim_discretize=ddim_discretize, dpm_order=dpm_order,
                                         dpm_discretize=dpm_discretize))
+    layout = check_layout_guidance(layout_guidance_scale, family_of(getattr(model, "cfg", None)))
     _check_noise(model, starting_noise)
     callbacks = dict(alpha_generator_func=partial(alpha_generator, type=alpha_type), set_alpha_scale=set_alpha_scale)
     sampler = spec.cls(diffusion, model, **spec.kwargs(values), **callbacks)
@@ -657,6 +680,9 @@ def denoise(all_models, context, uc, relations, grounding_batch, starting_noise,
     input = dict(x=starting_noise, timesteps=None, context=context, relations=relations, grounding_input=grounding_input,
                  inpainting_extra_input=inpainting_extra_input, grounding_extra_input=grounding_extra_input)
     shape = tuple(starting_noise.shape)
+    if layout is not None:
+        return sampler.sample_layout(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, layout_guidance_scale=layout,
+                                     mask=mask, x0=x0)
     return sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=mask, x0=x0)
 
 
@@ -707,9 +733,13 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     model, autoencoder, text_encoder, diffusion, config = all_models
     _check_noise(model, starting_noise)
     fam = family_of(model.cfg)           # the batch builder follows the model, not the checkpoint's file name
+    # the layout's guidance scale is read from ``args`` per call, like ``steps``; absent (or None), denoise is called as it always was
+    layout = check_layout_guidance(args.get(LAYOUT_GUIDANCE_KEY), fam)
     _refuse_foreign_meta(model, fam, meta, multiple, tuple(int(v) for v in starting_noise.shape[-2:]) if fam.extra_key else None)
     # the sampler switch is read from ``args`` per call, like ``steps``: not sticky through the cached config
     _, sampler_values = resolve_sampler(args)
+    if layout is not None:
+        sampler_values = dict(sampler_values, layout_guidance_scale=layout)
     config.update(args)                      # mutates the caller's dict, like interface.py:297/484
     cfg = _AttrDict(config)
     if cfg.get("no_plms", False):

@@ -283,14 +283,18 @@ class UNetModel:
         family_of(self.cfg).condition(self.engine, context, relations, self.tokens_of(grounding), hw)
         self._cond_key = key
 
-    def condition(self, input: dict, uc=None, always_extra: bool = False) -> int:
+    def condition(self, input: dict, uc=None, always_extra: bool = False, text_branch: bool = False) -> int:
         """Everything the engine holds per image, from the reference's ``input`` dict: the family's conditioning entry, then the downsampled
         ``grounding_extra_input`` of a map family and the ``inpainting_extra_input`` of an inpaint_mode model.  Every missing input raises
         before the engine is touched.  ``uc``: the unconditional context of classifier-free guidance -- the conditioning batch becomes
         [cond ; uncond] over whatever keys the family has, the unconditional half on the null grounding (a map family: the tokenizer's cached
         null tokens) and, where there are relations, on the same ones (plms.py:115-124).  ``always_extra``: hand the grounding extra over
-        even while the SD first conv, which does not read it, is switched in (a sampler switches convs between steps).  Returns the batch
-        multiple, 2 with ``uc`` and 1 without."""
+        even while the SD first conv, which does not read it, is switched in (a sampler switches convs between steps).  ``text_branch``
+        (needs ``uc``): the batch of three-branch guidance, [cond ; text-only ; uncond] -- the added third carries the conditional context
+        with the unconditional third's grounding and relations; the inpainting extra is shared by all thirds.  Returns the batch multiple,
+        3 with ``text_branch``, else 2 with ``uc`` and 1 without."""
+        if text_branch and uc is None:
+            raise ValueError("text_branch=True needs uc: the text-only third sits between the conditional and the unconditional one")
         H, W = (int(v) for v in input["x"].shape[-2:])
         extra = self.inpaint_extra_of(input)
         gextra = self.grounding_extra_of(input, (H, W)) if always_extra or not self.use_sd_conv else None
@@ -305,16 +309,22 @@ class UNetModel:
             else:
                 null = self.grounding_tokenizer_input.get_null_input()
             f32 = lambda t: t.to(self.device, torch.float32)
-            ctx = torch.cat([f32(ctx), f32(uc)], 0)
-            rel = torch.cat([f32(rel)] * 2, 0) if rel is not None else None
-            g = {k: torch.cat([f32(g[k]), f32(null[k])], 0) for k in null}
+            if text_branch:
+                # [cond ; text-only ; uncond]: the middle third reads the prompt, the null grounding and the same relations
+                ctx = torch.cat([f32(ctx), f32(ctx), f32(uc)], 0)
+                rel = torch.cat([f32(rel)] * 3, 0) if rel is not None else None
+                g = {k: torch.cat([f32(g[k]), f32(null[k]), f32(null[k])], 0) for k in null}
+            else:
+                ctx = torch.cat([f32(ctx), f32(uc)], 0)
+                rel = torch.cat([f32(rel)] * 2, 0) if rel is not None else None
+                g = {k: torch.cat([f32(g[k]), f32(null[k])], 0) for k in null}
         family_of(self.cfg).condition(self.engine, ctx, rel, g, H if H == W else (H, W))      # (H, W): the rectangular entry and its shape check
         self._cond_key = None
         if gextra is not None:
             self.engine.set_grounding_extra(self.downsampler(gextra))
         if extra is not None:
             self.engine.set_inpaint_extra(extra)
-        return 1 if uc is None else 2
+        return 1 if uc is None else 3 if text_branch else 2
 
     def relations_of(self, input: dict):
         """``input["relations"]``: required on a model with the rela_fuse chain (ValueError before any kernel runs); a model loaded from a

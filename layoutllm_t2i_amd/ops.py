@@ -569,6 +569,21 @@ def cfg_combine(eps2b: torch.Tensor, guidance: float, e_out: torch.Tensor):
     return e_out
 
 
+def cfg3_combine(eps3b: torch.Tensor, s_text: float, s_layout: float, e_out: torch.Tensor):
+    """Guidance with separate text and layout scales (gl_cfg3_combine): ``eps3b`` = the UNet output of the [cond ; text-only ; uncond] batch,
+    three times ``e_out``'s elements; e_out = (e_u + s_text * (e_t - e_u)) + s_layout * (e_c - e_t), bit-identical to that torch fp32
+    expression.  ``e_out`` must not overlap ``eps3b``."""
+    for t, nm in ((eps3b, "eps3b"), (e_out, "e_out")):
+        _req(t, F32, nm, 4)
+        if not t.is_contiguous():
+            raise ValueError(f"{nm}: need a contiguous tensor")
+    n = e_out.numel()
+    if n == 0 or eps3b.numel() != 3 * n:
+        raise ValueError(f"eps3b {tuple(eps3b.shape)}: need three times e_out's {tuple(e_out.shape)} elements ([cond ; text-only ; uncond])")
+    check(_lib.lib().gl_cfg3_combine(eps3b.data_ptr(), float(s_text), float(s_layout), n, e_out.data_ptr(), _stream()), "gl_cfg3_combine")
+    return e_out
+
+
 def plms_update(x, e, olds, coefs, div, sqrt_at, s1m, sqrt_aprev, dir_coef, x_prev):
     """x_prev from e' = (coefs[0]*e + sum coefs[1+j]*olds[j]) / div (plms.py:144-161)."""
     _req(x, F32, "x")

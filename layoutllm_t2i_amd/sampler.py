@@ -27,6 +27,13 @@ double evaluation, Adams-Bashforth history of <= 3 eps), but:
     x = q_sample(x0, t) * mask + (1 - mask) * x, as one fused in-place fp32 HIP kernel (gl_latent_blend, bit-identical to
     the torch expression), with the q_sample noise drawn by ``torch.randn_like(x0)`` before the step's own draws.
 
+Separate text and layout scales (every class: ``.sample_layout(S, shape, input, uc, guidance_scale, layout_guidance_scale, mask=None, x0=None)``,
+not in the reference; ``sample()`` keeps the reference's parameter list): the conditioning batch becomes [cond ; text-only ; uncond],
+one step = ``Engine.cfg3_eval`` (the 3B evaluation + gl_cfg3_combine: e = (e_u + s_t (e_t - e_u)) + s_l (e_c - e_t)) into a guided-eps buffer,
+then the sampler's op-level update (``ops.plms_update``, ``ops.ddim_update`` / ``ops.dpmpp_update`` on a B-sized eps) -- same coefficients,
+history and RNG draws as the two-branch step.  Where a step cannot see the grounding (fuser scale 0 on a model without the relation chain)
+e_c == e_t, and the sampler issues the existing two-branch step on [cond ; uncond] instead (``_Sampler._needs_text_branch``).
+
 One path: ``_Sampler`` owns ``sample()``, the loop, the schedule cache and what every step does first (the hoisted conditioning, the running
 latent, the per-step fuser scale and first-conv switch, the masked blend); a class adds its schedule tables, what it allocates before the loop
 and one step.  The switch is stated once as well: one ``SamplerSpec`` record per sampler (its ``args`` keys with defaults, validators and the
@@ -50,6 +57,7 @@ class _Sampler(object):
     ``sample()`` passes to ``make_schedule`` behind S), ``_alloc`` (what it allocates before the loop) and ``_step`` (one step)."""
     tag = None
     _sample_schedule = ()
+    _guided_eps = None          # set per step by _sampling under three-branch guidance
 
     def __init__(self, diffusion, model, schedule="linear", alpha_generator_func=None, set_alpha_scale=None):
         self.diffusion = diffusion
@@ -73,9 +81,22 @@ class _Sampler(object):
         return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
 
     @torch.no_grad()
-    def _sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
-        """The loop over the schedule in place (``plms_sampling`` / ``ddim_sampling`` / ``dpm_sampling`` by the classes' own names)."""
-        x_a, reps, time_range, alphas, blend = self._begin(self.tag, shape, input, uc, guidance_scale, mask, x0)
+    def sample_layout(self, S, shape, input, uc, guidance_scale, layout_guidance_scale, mask=None, x0=None):
+        """``sample()`` with the layout's own guidance scale (``_sampling``'s ``layout_guidance_scale``; None: ``sample()`` exactly).  A
+        method of its own: ``sample()`` keeps the reference's parameter list."""
+        self.make_schedule(S, *self._sample_schedule)
+        return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0, layout_guidance_scale=layout_guidance_scale)
+
+    @torch.no_grad()
+    def _sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, layout_guidance_scale=None):
+        """The loop over the schedule in place (``plms_sampling`` / ``ddim_sampling`` / ``dpm_sampling`` by the classes' own names).
+        ``layout_guidance_scale``: None = one scale for text and layout, the [cond ; uncond] batch; a number = the layout's own scale s_l
+        next to s_t = ``guidance_scale`` (three-branch guidance, see ``_needs_text_branch``)."""
+        layout = layout_guidance_scale
+        if layout is not None and uc is None:
+            raise ValueError("layout_guidance_scale needs uc, the unconditional context: the text-only and the unconditional branch are "
+                             "evaluated whatever guidance_scale is")
+        x_a, reps, time_range, alphas, blend = self._begin(self.tag, shape, input, uc, guidance_scale, mask, x0, layout is not None)
         model = self.model
         total_steps = self.ddim_timesteps.shape[0]
         state = self._alloc(x_a)
@@ -84,11 +105,33 @@ class _Sampler(object):
             """the evaluation's arguments of an engine step at timestep ``t``, read when the step is issued"""
             return dict(t=float(int(t)), reps=reps, guidance=float(guidance_scale), fuser_scale=model.fuser_scale, sd_conv=model.use_sd_conv)
 
-        for i, step in enumerate(time_range):
-            self._step_prologue(i, step, alphas, blend)
-            self._step(state, x_a, at, i, time_range, total_steps - i - 1)
+        def guided_eps(x_eval, t, e_out=None):
+            """one three-branch evaluation at timestep ``t``: the guided eps into ``e_out`` (default: the buffer ``<tag>.e3``)"""
+            if e_out is None:
+                e_out = model.engine.buf(f"{self.tag}.e3", tuple(x_a.shape), torch.float32)
+            return model.engine.cfg3_eval(x_eval, e_out, t=float(int(t)), fuser_scale=model.fuser_scale, sd_conv=model.use_sd_conv,
+                                          s_text=float(guidance_scale), s_layout=float(layout))
+
+        self._guided_eps = None         # what a step reads: None = the fused two-branch step, else the evaluation its op-level update follows
+        try:
+            for i, step in enumerate(time_range):
+                self._step_prologue(i, step, alphas, blend)
+                if layout is not None:
+                    want = 3 if self._needs_text_branch(model.fuser_scale) else 2
+                    if want != reps:            # the conditioning form in place is the other one: once per image with [0.3, 0, 0.7]
+                        reps = model.condition(input, uc, always_extra=True, text_branch=want == 3)
+                    self._guided_eps = guided_eps if reps == 3 else None
+                self._step(state, x_a, at, i, time_range, total_steps - i - 1)
+        finally:
+            self._guided_eps = None
         input["x"] = x_a.clone()
         return input["x"]
+
+    def _needs_text_branch(self, fuser_scale) -> bool:
+        """Whether a step at this fuser scale needs the text-only branch.  Without the relation chain a scale-0 step skips the fuser, the only
+        reader of the grounding: e_c == e_t there, the layout term vanishes and [cond ; uncond] with ``guidance_scale`` is the whole
+        formula.  The relation chain reads the boxes at every scale, so a relation model always runs three branches."""
+        return bool(self.model.cfg.relation) or fuser_scale != 0
 
     def _alloc(self, x_a):
         return None
@@ -106,9 +149,10 @@ class _Sampler(object):
         self.ddim_sigmas = s["ddim_sigmas"]
         self._sched = s
 
-    def _begin(self, tag, shape, input, uc, guidance_scale, mask, x0):
+    def _begin(self, tag, shape, input, uc, guidance_scale, mask, x0, layout=False):
         """Everything before the loop: the starting latent in the engine buffer ``<tag>.x``, the conditioning hoisted once, the fuser scales of
-        the steps and the masked blend of one step (None without a mask).  Returns (x_a, reps, time_range, alphas, blend)."""
+        the steps and the masked blend of one step (None without a mask).  ``layout``: three-branch guidance -- the conditioning takes the form
+        the first step needs.  Returns (x_a, reps, time_range, alphas, blend)."""
         if mask is not None and x0 is None:
             raise AssertionError("a mask needs x0, the latent of the image to keep (plms.py:96)")       # before the model is touched
         model, eng = self.model, self.model.engine
@@ -125,7 +169,11 @@ class _Sampler(object):
 
         # ---- conditioning, once per image: [cond ; uncond] when CFG is active (plms.py:115-124)
         # every missing input raises before any kernel runs; the grounding extra of a map family is handed over whatever conv is switched in
-        reps = model.condition(input, uc if uc is not None and guidance_scale != 1 else None, always_extra=True)
+        if layout:
+            first = alphas[0] if alphas is not None and len(alphas) else model.fuser_scale
+            reps = model.condition(input, uc, always_extra=True, text_branch=self._needs_text_branch(first))
+        else:
+            reps = model.condition(input, uc if uc is not None and guidance_scale != 1 else None, always_extra=True)
 
         x_a = eng.buf(f"{tag}.x", tuple(x.shape), torch.float32)    # running latent (the engine copies it per forward)
         x_a.copy_(x)
@@ -187,6 +235,11 @@ class PLMSSampler(_Sampler):
             sq_at, s1m, sq_ap, dirc = host.step_coefs(self._sched, index)
             if self.mirror_rng:
                 torch.randn_like(x_a)          # plms.py:138 draws noise * sigma (= 0) on every update: keep the RNG stream aligned
+            if self._guided_eps is not None:
+                # three branches: the guided eps into the same slot, then the op-level update over the same terms
+                self._guided_eps(x_eval, t_val, e_out)
+                ops.plms_update(x_a, e_terms[0], e_terms[1:], coefs, div, sq_at, s1m, sq_ap, dirc, x_out)
+                return
             a = at(t_val)              # plms_step takes its arguments by position: callers wrap it with that signature
             self.model.engine.plms_step(x_eval, x_a, x_out, e_out, e_terms, coefs, div, a["t"], a["reps"], a["guidance"], a["fuser_scale"],
                                         a["sd_conv"], sq_at, s1m, sq_ap, dirc)
@@ -239,6 +292,10 @@ class DDIMSampler(_Sampler):
     def _step(self, st, x_a, at, i, time_range, index):
         sq_at, s1m, sq_ap, dirc, sigma = host.ddim_step_coefs(self._sched, index)
         noise = torch.randn_like(x_a)      # ddim.py:132 draws on every step, sigma 0 included: keep the RNG stream aligned
+        if self._guided_eps is not None:
+            ops.ddim_update(self._guided_eps(x_a, time_range[i]), x_a, x_a, sqrt_at=sq_at, s1m=s1m, sqrt_aprev=sq_ap, dir_coef=dirc, sigma=sigma,
+                            noise=noise.to(self.device, torch.float32).contiguous() if sigma != 0 else None)
+            return
         self.model.engine.ddim_step(x_a, x_a, **at(time_range[i]), sqrt_at=sq_at, s1m=s1m, sqrt_aprev=sq_ap, dir_coef=dirc, sigma=sigma,
                                     noise=noise.to(self.device, torch.float32).contiguous() if sigma != 0 else None)
 
@@ -276,8 +333,12 @@ class DPMSolverSampler(_Sampler):
 
     def _step(self, st, x_a, at, i, time_range, index):
         sq_at, s1m, c_x, c_d, w1, w0 = host.dpm_step_coefs(self._sched, index, st["prev"], self.order)
-        self.model.engine.dpmpp_step(x_a, x_a, st["hist"], **at(time_range[i]), sqrt_at=sq_at, s1m=s1m, c_x=c_x, c_d=c_d, w1=w1, w0=w0,
-                                     x0_old=st["hist"] if w0 != 0 else None)
+        if self._guided_eps is not None:
+            ops.dpmpp_update(self._guided_eps(x_a, time_range[i]), x_a, x_a, st["hist"], sqrt_at=sq_at, s1m=s1m, c_x=c_x, c_d=c_d, w1=w1, w0=w0,
+                             x0_old=st["hist"] if w0 != 0 else None)
+        else:
+            self.model.engine.dpmpp_step(x_a, x_a, st["hist"], **at(time_range[i]), sqrt_at=sq_at, s1m=s1m, c_x=c_x, c_d=c_d, w1=w1, w0=w0,
+                                         x0_old=st["hist"] if w0 != 0 else None)
         st["prev"] = index
 
 

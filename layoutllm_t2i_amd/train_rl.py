@@ -26,15 +26,19 @@ from .prompting import build_prompt, center2lefttop, extract_prediction
 
 
 def generate_with(all_models, clip_model=None, clip_processor=None, device=None, sampler=None, steps=None, dpm_order=None,
-                  dpm_discretize=None) -> Callable:
+                  dpm_discretize=None, layout_guidance_scale=None) -> Callable:
     """``generate`` for ``train_batch``: ``interface.generate_batch_images`` on ``all_models`` (train_rl.py:90-91).  ``sampler`` / ``steps`` /
     ``dpm_order`` / ``dpm_discretize``: when any is given, the same call through ``interface.run_batch_images`` with those as ``args`` keys
     (the rollout images only feed the reward: ``sampler="dpmpp_2m", steps=20`` is 20 UNet evaluations per image in place of 51); checked
-    here, before the rollout.  None given: ``generate_batch_images`` exactly."""
+    here, before the rollout.  ``layout_guidance_scale``: the layout's own guidance scale (interface.check_layout_guidance), routed the same
+    way -- how hard the rollout follows the LLM's boxes, without touching prompt adherence.  None given: ``generate_batch_images`` exactly."""
     from . import interface
+    from .family import family_of
     more = {k: v for k, v in dict(sampler=sampler, steps=steps, dpm_order=dpm_order, dpm_discretize=dpm_discretize).items() if v is not None}
     if more:
         interface.resolve_sampler(more)         # every key of the switch that was given, judged the way the rollout's call will judge it
+    if layout_guidance_scale is not None:
+        more[interface.LAYOUT_GUIDANCE_KEY] = interface.check_layout_guidance(layout_guidance_scale, family_of(getattr(all_models[0], "cfg", None)))
 
     def generate(captions, categories, bboxes):
         if not more:

@@ -50,7 +50,7 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
              guidance_scale: float = 7.5, alpha_type: Sequence[float] = (0.3, 0.0, 0.7), is_center: bool = False,
              steps: Optional[int] = None, starting_noise: Optional[torch.Tensor] = None, folder: Optional[str] = None, device=None,
              instruction=None, draw_boxes: bool = False, sampler: str = "plms", ddim_eta: float = 0.0, dpm_order: int = 2,
-             dpm_discretize: str = "logsnr") -> dict:
+             dpm_discretize: str = "logsnr", layout_guidance_scale: Optional[float] = None) -> dict:
     """``all_models``: the 5-tuple of ``interface.load_all_models``; ``policy`` / ``pool``: policy.PolicyNetwork / policy.CandidatePool;
     ``tokenize``: list of strings -> (input_ids, attention_mask) for the CLIP text tower (``pool.towers``, else ``clip_model``);
     ``clip_model`` / ``clip_processor``: the grounding phrases' encoder, as for ``interface.generate_one_image``.
@@ -60,7 +60,9 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
     layout drawn on the saved copies).  ``instruction``: the wording of the LLM prompt (prompting.build_prompt).  ``sampler`` / ``ddim_eta``:
     handed through as ``args["sampler"]`` / ``args["ddim_eta"]`` ("ddim" with eta >= 0; checked before the policy or the LLM runs);
     ``dpm_order`` / ``dpm_discretize``: ``args["dpm_order"]`` / ``args["dpm_discretize"]`` of ``sampler="dpmpp_2m"`` (sampler.resolve_sampler;
-    with ``steps=20`` an image costs 20 UNet evaluations in place of PLMS's 51).
+    with ``steps=20`` an image costs 20 UNet evaluations in place of PLMS's 51).  ``layout_guidance_scale``: None, or how hard the images
+    follow the LLM's boxes, apart from ``guidance_scale``'s prompt adherence -- ``args["layout_guidance_scale"]``
+    (interface.check_layout_guidance; checked before the policy or the LLM runs).
     Returns dict(images, categories, bboxes_ltrb, cids, prompt_text, llm_output)."""
     model = all_models[0]
     if not family_of(model.cfg).boxes:
@@ -74,6 +76,9 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
     spec, values = interface.resolve_sampler(given)
     # handed on: nothing for the default sampler, else the sampler and those of its own keys this entry takes
     sampler_args = {} if spec.name == DEFAULT_SAMPLER else {k: values[k] for k in ("sampler", *(key.name for key in spec.keys)) if k in given}
+    layout = interface.check_layout_guidance(layout_guidance_scale, family_of(model.cfg))
+    if layout is not None:
+        sampler_args[interface.LAYOUT_GUIDANCE_KEY] = layout
     towers = pool.towers if pool.towers is not None else clip_model
     if towers is None:
         raise ValueError("no text tower for the prompt: build the pool with CandidatePool.from_captions, or pass clip_model")
