@@ -413,6 +413,15 @@ int gl_vae_posterior(const float* h, const float* w, const float* bias, const fl
                      int32_t E, int32_t hw, float* z, float* mean, void* stream);
 int gl_latent_blend(float* x, const float* x0, const float* noise, const float* mask, float a, float s, int32_t B, int32_t C,
                     int32_t hw, int32_t x0_batch, int32_t mask_batch, void* stream);
+/* gl_q_sample: the forward process at one timestep (ldm.py:19-22; gl_latent_blend's q_sample without the mask), additive to ABI 15 -- the
+ * start of image-to-image sampling (SDEdit, Meng et al., arXiv 2108.01073): the encoded image noised to the timestep the truncated schedule
+ * starts at.  x0 fp32 [x0_batch, chw] with x0_batch = 1 (one image for every sample) or B, noise / out fp32 [B, chw]:
+ *     out[b] = a * x0[b or 0] + s * noise[b]
+ * two products and their sum, each rounded separately, FP contraction off: bit-identical to the torch fp32 expression.  out may be noise (in
+ * place on the running latent: every thread loads its operands before it stores); out must not overlap x0.  chw % 4 == 0 and 16-byte
+ * pointers take the float4 path (a float4 stays inside one sample), everything else the scalar one; the grid is gl_ddim_update's.
+ * GL_ERR_BAD_ARG, before any device call: NULL x0 / noise / out, B <= 0, chw <= 0, x0_batch neither 1 nor B. */
+int gl_q_sample(const float* x0, const float* noise, float a, float s, int32_t B, int32_t chw, int32_t x0_batch, float* out, void* stream);
 
 /* =====================================================================================================
  * Forward-level API ("what a C-ABI replacement must export underneath"): one handle per device per

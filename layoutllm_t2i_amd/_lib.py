@@ -332,6 +332,7 @@ PROTOTYPES = {
     "gl_conv3x3_pad01": (i32, [C.POINTER(ConvArgs), vp]),
     "gl_vae_posterior": (i32, [fp, fp, fp, fp, f32, i32, i32, i32, i32, fp, fp, vp]),
     "gl_latent_blend": (i32, [fp, fp, fp, fp, f32, f32, i32, i32, i32, i32, i32, vp]),
+    "gl_q_sample": (i32, [fp, fp, f32, f32, i32, i32, i32, fp, vp]),
     "gl_clip_patchify": (i32, [fp, i32, i32, i32, i32, vp, vp]),
     "gl_clip_assemble": (i32, [vp, i32, fp, fp, i32, i32, i32, fp, fp, f32, fp, vp]),
     "gl_clip_embed_tokens": (i32, [vp, fp, fp, i32, i32, i32, i32, fp, vp]),

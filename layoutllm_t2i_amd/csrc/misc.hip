@@ -293,6 +293,24 @@ __global__ __launch_bounds__(256) void latent_blend_kernel(float* x, const float
     }
 }
 
+// The forward process at one timestep (ldm.py:19-22, the blend's q_sample without the mask): out = a * x0 + s * noise on [B, chw], two
+// products and their sum.  x0 has 1 or B (nb0) samples.  No __restrict__ on noise / out: out may be noise (in place on the running latent);
+// every thread loads its operands before it stores.  VEC = 4: chw % 4 == 0, one float4 of one sample per thread.
+template <int VEC>
+__global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x0, const float* noise, float a, float s, size_t chw, size_t n,
+                                                       int nb0, float* out) {
+    const size_t nvec = n / VEC;
+    for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec; v += (size_t)gridDim.x * blockDim.x) {
+        const size_t i = v * VEC;
+        float x0v[VEC], nv[VEC], o[VEC];
+        ew_load<VEC>(x0 + (nb0 == 1 ? i % chw : i), x0v);
+        ew_load<VEC>(noise + i, nv);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) o[j] = a * x0v[j] + s * nv[j];
+        ew_store<VEC>(out + i, o);
+    }
+}
+
 // One DDIM step behind the UNet (ddim.py:115-135) as ONE launch: the CFG combine of the [cond ; uncond] output (reps == 2), pred_x0 and
 // x_prev, in the reference's operation order: e = e_u + g * (e_c - e_u); pred_x0 = (x - s1m * e) / sqrt_at;
 // x_prev = (sqrt_aprev * pred_x0 + dir_coef * e) + sigma * noise.  noise == NULL (the reference's 0 * randn): the last term is SKIPPED, which
@@ -694,6 +712,18 @@ extern "C" int gl_latent_blend(float* x, const float* x0, const float* noise, co
         latent_blend_kernel<4><<<dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream>>>(x, x0, noise, mask, a, s, B, C, hw, x0_batch, mask_batch);
     else
         latent_blend_kernel<1><<<dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream>>>(x, x0, noise, mask, a, s, B, C, hw, x0_batch, mask_batch);
+    GL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gl_q_sample(const float* x0, const float* noise, float a, float s, int32_t B, int32_t chw, int32_t x0_batch, float* out,
+                           void* stream) {
+    if (!x0 || !noise || !out || B <= 0 || chw <= 0 || (x0_batch != 1 && x0_batch != B)) return GL_ERR_BAD_ARG;
+    const size_t n = (size_t)B * chw;
+    if (ew_vec4((size_t)chw, {x0, noise, out}))          // a float4 stays inside one sample
+        q_sample_kernel<4><<<dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream>>>(x0, noise, a, s, (size_t)chw, n, x0_batch, out);
+    else
+        q_sample_kernel<1><<<dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream>>>(x0, noise, a, s, (size_t)chw, n, x0_batch, out);
     GL_CHECK_LAUNCH();
     return 0;
 }

@@ -27,6 +27,11 @@ here and additionally feeds ``cat([z0 * mask, mask])`` to the first conv on ever
 ``meta["input_image"]`` (ValueError otherwise).  A 4-channel text_layout / text_image checkpoint with ``input_image`` keeps running the
 latent-blend inpainting alone, which the reference refuses.
 
+``config["init_image"]`` (a path or a PIL.Image; ``meta["init_image"]`` is read as well) with ``config["strength"]`` in (0, 1] (0.75 when absent):
+image-to-image (SDEdit, arXiv 2108.01073; not in the reference's script).  The image is encoded like ``input_image``, noised to the timestep where
+the last int(strength * n) of the schedule's n nodes begin, and re-rendered from there under the prompt and the boxes; every checkpoint family
+and sampler, with or without ``input_image``.  ``strength`` without an image raises ValueError.
+
 A keypoint checkpoint (``checkpoint_generation_keypoint.pth``, ``keypoint_grounding_net.PositionNet``) takes ``meta["locations"]`` as a
 list of persons, each a list of 17 ``[x, y]`` in [0, 1] with ``[0, 0]`` for a missing keypoint (gligen_inference.py:199-218, :585-633); it
 needs neither ``phrases`` nor a CLIP model, and ``images`` / ``input_image`` raise ValueError.
@@ -84,6 +89,10 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
     for k in ("images", "text_mask", "image_mask", "projection_matrix"):
         if meta.get(k) is not None:
             m[k] = meta[k]
+    init_image = _get(config, interface.INIT_IMAGE_KEY)
+    init_image = meta.get(interface.INIT_IMAGE_KEY) if init_image is None else init_image
+    if init_image is not None:
+        m[interface.INIT_IMAGE_KEY] = init_image
     if starting_noise is None:
         h, w = interface.latent_hw(_get(config, "height"), _get(config, "width"), all_models[1])
         starting_noise = torch.randn(bs, 4, h, w).to(device)
@@ -93,9 +102,9 @@ def run(meta, config, starting_noise=None, clip_model=None, clip_processor=None)
         version = "openai/clip-vit-large-patch14"
         clip_model = CLIPModel.from_pretrained(version).to(device)
         clip_processor = CLIPProcessor.from_pretrained(version)
-    # per-call keys, handed on only when the config carries them: the step count, the sampler switch (sampler.resolve_sampler) and the
-    # layout's guidance scale (interface.check_layout_guidance)
-    for k in ("steps",) + SAMPLER_KEYS + (interface.LAYOUT_GUIDANCE_KEY,):
+    # per-call keys, handed on only when the config carries them: the step count, the sampler switch (sampler.resolve_sampler), the
+    # layout's guidance scale (interface.check_layout_guidance) and image-to-image's strength (interface.check_strength)
+    for k in ("steps",) + SAMPLER_KEYS + (interface.LAYOUT_GUIDANCE_KEY, interface.STRENGTH_KEY):
         if k in (config if isinstance(config, dict) else vars(config)):
             args[k] = _get(config, k)
     images = interface.run_one_image(all_models, args, m, starting_noise, clip_model, clip_processor, device=device)

@@ -192,7 +192,7 @@ def make_dpm_schedule(S: int, acp: np.ndarray, discretize: str = "logsnr") -> Di
 
 
 def dpm_step_coefs(sched: Dict[str, np.ndarray], index: int, prev_index: Optional[int] = None,
-                   order: int = 2) -> Tuple[float, float, float, float, float, float]:
+                   order: int = 2, n_nodes: Optional[int] = None) -> Tuple[float, float, float, float, float, float]:
     """The scalars of one DPM-Solver++(2M) step from node ``index`` (a_t) to its a_prev, in float64, each rounded ONCE to float32:
     (sqrt(a_t), sqrt(1 - a_t), c_x, c_d, w1, w0) of
 
@@ -201,11 +201,12 @@ def dpm_step_coefs(sched: Dict[str, np.ndarray], index: int, prev_index: Optiona
     with h = lambda(a_prev) - lambda(a_t) > 0, c_x = sqrt(1 - a_prev) / sqrt(1 - a_t), c_d = -sqrt(a_prev) * expm1(-h).  ``prev_index``:
     the node of the step before (whose x0 is ``x0_old``), None on the first step.  Second order: r = h_of_that_step / h,
     (w1, w0) = (1 + 1 / (2 r), -1 / (2 r)).  First order, (w1, w0) = (1, 0) -- DDIM with eta 0 in exponential-integrator form: the first step,
-    ``order`` 1, and the last step (index 0) of a schedule with fewer than DPM_LOWER_ORDER_FINAL nodes."""
+    ``order`` 1, and the last step (index 0) of a schedule with fewer than DPM_LOWER_ORDER_FINAL nodes.  ``n_nodes``: the number of nodes that
+    run, where that is not the whole schedule (image-to-image runs its last ``img2img_run_steps`` nodes); None = all of them."""
     if order not in DPM_ORDERS:
         raise ValueError(f"dpm_order = {order!r}: one of {DPM_ORDERS}")
     f = np.float32
-    n = len(sched["ddim_timesteps"])
+    n = len(sched["ddim_timesteps"]) if n_nodes is None else int(n_nodes)
     a_t, a_prev = np.float64(sched["ddim_alphas"][index]), np.float64(sched["ddim_alphas_prev"][index])
     h = np.float64(sched["lambdas_prev"][index]) - np.float64(sched["lambdas"][index])
     c_x = np.sqrt(1.0 - a_prev) / np.sqrt(1.0 - a_t)
@@ -217,6 +218,23 @@ def dpm_step_coefs(sched: Dict[str, np.ndarray], index: int, prev_index: Optiona
         r = (np.float64(sched["lambdas_prev"][prev_index]) - np.float64(sched["lambdas"][prev_index])) / h
         w1, w0 = 1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r)
     return (float(f(np.sqrt(a_t))), float(f(np.sqrt(1.0 - a_t))), float(f(c_x)), float(f(c_d)), float(f(w1)), float(f(w0)))
+
+
+IMG2IMG_DEFAULT_STRENGTH = 0.75       # the default of the Stable Diffusion img2img script
+
+
+def check_strength(v) -> float:
+    """``strength`` of image-to-image sampling (SDEdit, Meng et al., arXiv 2108.01073): the share of the schedule that runs on the noised
+    input image.  A finite real number in (0, 1] that is no bool, else ValueError naming ``strength``."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not 0 < v <= 1:
+        raise ValueError(f"strength = {v!r}: must be a finite number in (0, 1]")
+    return float(v)
+
+
+def img2img_run_steps(n: int, strength: float) -> int:
+    """How many of a schedule's ``n`` nodes image-to-image sampling runs -- its last ones: ``t_enc = int(strength * steps)`` of the Stable
+    Diffusion img2img script, kept within [1, n]."""
+    return max(1, min(int(n), int(check_strength(strength) * int(n))))
 
 
 def draw_masks_from_boxes(boxes, size):

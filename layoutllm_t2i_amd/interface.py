@@ -653,10 +653,38 @@ def check_layout_guidance(value, family=None):
     return float(value)
 
 
+STRENGTH_KEY = "strength"
+INIT_IMAGE_KEY = "init_image"
+
+
+def check_strength(value, has_image):
+    """``args["strength"]`` against ``meta["init_image"]`` (image-to-image, sampler._Sampler.sample_from), checked before any encoder or
+    kernel runs.  Without an image the key must be absent (or None): a number there raises ValueError naming it; returns None.  With one:
+    None = host.IMG2IMG_DEFAULT_STRENGTH (0.75, the Stable Diffusion img2img script's default), else host.check_strength -- a finite real in
+    (0, 1] that is no bool.  Returns None or the float."""
+    if value is not None:
+        value = host.check_strength(value)
+    if not has_image:
+        if value is not None:
+            raise ValueError(f"{STRENGTH_KEY} = {value!r} without meta[{INIT_IMAGE_KEY!r}]: it is the share of the schedule that runs on that image")
+        return None
+    return host.IMG2IMG_DEFAULT_STRENGTH if value is None else value
+
+
+def _load_images(ims, key, bs, side, device) -> torch.Tensor:
+    """``meta[key]``: one image (a path or a PIL.Image) for every sample, or a list with one per sample (another length: ValueError naming
+    the key) -> fp32 [1|bs, 3, H, W] (load_input_image)"""
+    if isinstance(ims, (list, tuple)):
+        if len(ims) != bs:
+            raise ValueError(f"{key}: {len(ims)} images for a batch of {bs}")
+        return torch.cat([load_input_image(im, side, device) for im in ims], 0)
+    return load_input_image(ims, side, device)
+
+
 @torch.no_grad()
 def denoise(all_models, context, uc, relations, grounding_batch, starting_noise, alpha_type=None, guidance_scale=7.5,
             steps=PLMS_STEPS, mask=None, x0=None, inpainting_extra_input=None, grounding_extra_input=None, sampler="plms", ddim_eta=0.0,
-            ddim_discretize="uniform", dpm_order=2, dpm_discretize="logsnr", layout_guidance_scale=None):
+            ddim_discretize="uniform", dpm_order=2, dpm_discretize="logsnr", layout_guidance_scale=None, init_latent=None, strength=None):
     """The denoising hot path proper, from conditioning tensors to the final latent
     (run_batch_images lines interface.py:505-539 without text/VAE stages).  ``mask`` [1|B, 1, h, w] (1 = keep) and ``x0``
     [1|B, 4, h, w] (the encoded input image): inpainting, plms.py:95-99.  The latent's shape [B, 4, h, w] is ``starting_noise``'s
@@ -668,8 +696,15 @@ def denoise(all_models, context, uc, relations, grounding_batch, starting_noise,
     (sampler.DPMSolverSampler, with ``dpm_order`` 2 | 1 and ``dpm_discretize`` "logsnr" | "quad" | "uniform"; there ``steps`` bounds the
     number of UNet evaluations, 20 is the usual choice); all five go through sampler.resolve_sampler first.  ``layout_guidance_scale``:
     None, or the layout's own scale s_l >= 0 -- e = (e_u + s_t (e_t - e_u)) + s_l (e_c - e_t) with s_t = ``guidance_scale`` and e_t the
-    branch that reads the prompt and the null grounding (check_layout_guidance; any sampler; refused on a map family)."""
+    branch that reads the prompt and the null grounding (check_layout_guidance; any sampler; refused on a map family).  ``init_latent``
+    fp32 [1|B, 4, h, w] with ``strength`` in (0, 1] (both or neither): image-to-image -- the last int(strength * n) of the schedule's n nodes
+    run, from ``init_latent`` noised with ``starting_noise`` to where they begin (any sampler; sampler._Sampler.sample_from)."""
     model, autoencoder, text_encoder, diffusion, config = all_models
+    if (init_latent is None) != (strength is None):
+        raise ValueError(f"{STRENGTH_KEY} and init_latent go together: got {STRENGTH_KEY} = {strength!r} and init_latent "
+                         f"{'absent' if init_latent is None else 'given'}")
+    if strength is not None:
+        strength = host.check_strength(strength)
     spec, values = resolve_sampler(dict(sampler=sampler, ddim_eta=ddim_eta, ddim_discretize=ddim_discretize, dpm_order=dpm_order,
                                         dpm_discretize=dpm_discretize))
     layout = check_layout_guidance(layout_guidance_scale, family_of(getattr(model, "cfg", None)))
@@ -680,6 +715,9 @@ def denoise(all_models, context, uc, relations, grounding_batch, starting_noise,
     input = dict(x=starting_noise, timesteps=None, context=context, relations=relations, grounding_input=grounding_input,
                  inpainting_extra_input=inpainting_extra_input, grounding_extra_input=grounding_extra_input)
     shape = tuple(starting_noise.shape)
+    if init_latent is not None:
+        return sampler.sample_from(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, init_latent=init_latent,
+                                   strength=strength, mask=mask, x0=x0, layout_guidance_scale=layout)
     if layout is not None:
         return sampler.sample_layout(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, layout_guidance_scale=layout,
                                      mask=mask, x0=x0)
@@ -735,6 +773,8 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
     fam = family_of(model.cfg)           # the batch builder follows the model, not the checkpoint's file name
     # the layout's guidance scale is read from ``args`` per call, like ``steps``; absent (or None), denoise is called as it always was
     layout = check_layout_guidance(args.get(LAYOUT_GUIDANCE_KEY), fam)
+    # image-to-image: ``strength`` is read from ``args`` per call as well, and never from the cached config
+    strength = check_strength(args.get(STRENGTH_KEY), meta.get(INIT_IMAGE_KEY) is not None)
     _refuse_foreign_meta(model, fam, meta, multiple, tuple(int(v) for v in starting_noise.shape[-2:]) if fam.extra_key else None)
     # the sampler switch is read from ``args`` per call, like ``steps``: not sticky through the cached config
     _, sampler_values = resolve_sampler(args)
@@ -746,6 +786,8 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
         raise NotImplementedError("no_plms = True is the reference's DDIM switch, which is broken there with this UNet (SURVEY App-B#8) and "
                                   "stays refused; DDIM runs under args[\"sampler\"] = \"ddim\" (with args[\"ddim_eta\"], args[\"ddim_discretize\"])")
     bs = cfg.batch_size
+    if isinstance(meta.get(INIT_IMAGE_KEY), (list, tuple)) and len(meta[INIT_IMAGE_KEY]) != bs:      # refused before any encoder runs
+        raise ValueError(f"{INIT_IMAGE_KEY}: {len(meta[INIT_IMAGE_KEY])} images for a batch of {bs}")
     max_rel = cfg.get("max_relations", 10)
     # (a keypoint model: no phrases, no CLIP model, and -- always on the upstream block -- no relation phrases)
     batch = fam.build(globals()[fam.batch[multiple]], meta, model.cfg, clip_model, clip_processor, bs, device)
@@ -765,19 +807,18 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
         # inpainting (gligen_inference.py:393-407): encode the input image, regenerate inside the boxes (mask 0), keep the rest
         L = tuple(int(v) for v in starting_noise.shape[-2:])              # latent (h, w); the image is vae_factor times that per axis
         side = tuple(_vae_factor(autoencoder) * v for v in L)
-        ims = meta["input_image"]
-        if isinstance(ims, (list, tuple)):
-            if len(ims) != bs:
-                raise ValueError(f"input_image: {len(ims)} images for a batch of {bs}")
-            img = torch.cat([load_input_image(im, side, device) for im in ims], 0)
-        else:
-            img = load_input_image(ims, side, device)
-        z0 = autoencoder.encode(img)
+        z0 = autoencoder.encode(_load_images(meta["input_image"], "input_image", bs, side, device))
         mask = host.draw_masks_from_boxes(batch["boxes"], L).to(starting_noise.device)
         if model.cfg.inpaint_mode:
             # an inpaint_mode checkpoint (gligen_inference.py:406-407): the first conv also reads [z0 * mask | mask]; the sampler keeps
             # replacing the known region as well (:430 passes mask and x0 too).  A 4-channel model runs the latent blend alone.
             extra = build_inpainting_extra(z0, mask)
+    if strength is not None:
+        # image-to-image (SDEdit): the encoded image (the posterior sample * scale factor, as above; its one torch.randn draw comes before
+        # anything the sampler draws) is noised to where the truncated schedule starts; independent of the inpainting keys
+        side = tuple(_vae_factor(autoencoder) * int(v) for v in starting_noise.shape[-2:])
+        sampler_values = dict(sampler_values, strength=strength,
+                              init_latent=autoencoder.encode(_load_images(meta[INIT_IMAGE_KEY], INIT_IMAGE_KEY, bs, side, device)))
     # S is a harness parameter: the reference hard-codes 50 (interface.py:507); ``args["steps"]`` overrides it
     samples = denoise(all_models, context, uc, relations, batch, starting_noise, meta.get("alpha_type"), cfg.guidance_scale,
                       steps=int(args.get("steps", PLMS_STEPS)), mask=mask, x0=z0,   # steps per call: not sticky through the cached config
@@ -789,14 +830,17 @@ def _run(all_models, args, meta, starting_noise, clip_model, clip_processor, dev
 
 @torch.no_grad()
 def run_one_image(all_models, args, meta, starting_noise=None, clip_model=None, clip_processor=None, device=None):
-    """interface.py:292-357.  ``meta["input_image"]`` (a path or a PIL.Image): inpaint that image inside the boxes.  On a keypoint checkpoint
+    """interface.py:292-357.  ``meta["input_image"]`` (a path or a PIL.Image): inpaint that image inside the boxes.  ``meta["init_image"]``
+    (a path or a PIL.Image) with ``args["strength"]`` in (0, 1] (0.75 when absent): image-to-image, re-render that image under the prompt
+    and the boxes, the more freely the higher the strength (independent of ``input_image``; every checkpoint family).  On a keypoint checkpoint
     ``meta["locations"]`` is a list of persons, each 17 ``[x, y]`` (prepare_batch_kp); no phrases, no CLIP model, no input image."""
     return _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple=False)
 
 
 @torch.no_grad()
 def run_batch_images(all_models, args, meta, starting_noise=None, clip_model=None, clip_processor=None, device=None):
-    """interface.py:478-549.  ``meta["input_image"]``: a list with one image (path or PIL.Image) per sample, or one for all.  On a keypoint
+    """interface.py:478-549.  ``meta["input_image"]`` / ``meta["init_image"]`` (inpainting / image-to-image with ``args["strength"]``, see
+    run_one_image): a list with one image (path or PIL.Image) per sample, or one for all.  On a keypoint
     checkpoint ``meta["locations"]`` holds one pose layout (a list of persons of 17 ``[x, y]``) per prompt; no phrases, no CLIP model."""
     return _run(all_models, args, meta, starting_noise, clip_model, clip_processor, device, multiple=True)
 

@@ -705,6 +705,25 @@ def latent_blend(x: torch.Tensor, x0: torch.Tensor, noise: torch.Tensor, mask: t
     return x
 
 
+def q_sample(x0: torch.Tensor, noise: torch.Tensor, a: float, s: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = a * x0 + s * noise (gl_q_sample; ldm.py:19-22), bit-identical to that torch fp32 expression.  noise fp32 [B, C, h, w];
+    x0 [1|B, C, h, w] (one image is broadcast over the batch); ``out`` [B, C, h, w]: None = a new tensor, may be ``noise`` (in place),
+    must not overlap ``x0``."""
+    if out is None:
+        out = torch.empty_like(noise)
+    for t, n in ((x0, "x0"), (noise, "noise"), (out, "out")):
+        _req(t, F32, n, 4)
+        if not t.is_contiguous():
+            raise ValueError(f"{n}: need a contiguous tensor")
+    if noise.dim() != 4 or noise.numel() == 0 or x0.shape[1:] != noise.shape[1:] or x0.shape[0] not in (1, noise.shape[0]) or out.shape != noise.shape:
+        raise ValueError(f"q_sample: noise / out [B, C, h, w], x0 [1|B, C, h, w], got x0 {tuple(x0.shape)}, noise {tuple(noise.shape)}, "
+                         f"out {tuple(out.shape)}")
+    B, Cc, hh, ww = noise.shape
+    check(_lib.lib().gl_q_sample(x0.data_ptr(), noise.data_ptr(), float(a), float(s), B, Cc * hh * ww, x0.shape[0], out.data_ptr(), _stream()),
+          "gl_q_sample")
+    return out
+
+
 def softmax_rows(x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
     """in-place softmax(scale * x) over the last dim of a 2-D fp16 tensor"""
     _req(x, F16, "x")

@@ -7,6 +7,8 @@
         .sample(S, shape, input, uc, guidance_scale, mask=None, x0=None) -> latent
     DPMSolverSampler(diffusion, model, alpha_generator_func=..., set_alpha_scale=..., order=2, discretize="logsnr")
         .sample(S, shape, input, uc, guidance_scale, mask=None, x0=None) -> latent
+    every class: .sample_from(S, shape, input, uc, guidance_scale, init_latent, strength, mask=None, x0=None, layout_guidance_scale=None)
+        -> latent: image-to-image (SDEdit), the schedule's tail from the noised ``init_latent`` (not in the reference; see the method)
 
 Same loops, same side effects (per-step fuser scale via set_alpha_scale, permanent SD first-conv switch on every scale-0 step; PLMS: step-0
 double evaluation, Adams-Bashforth history of <= 3 eps), but:
@@ -88,17 +90,39 @@ class _Sampler(object):
         return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0, layout_guidance_scale=layout_guidance_scale)
 
     @torch.no_grad()
-    def _sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, layout_guidance_scale=None):
+    def sample_from(self, S, shape, input, uc, guidance_scale, init_latent, strength, mask=None, x0=None, layout_guidance_scale=None):
+        """Image-to-image (SDEdit, Meng et al., arXiv 2108.01073): ``sample()`` / ``sample_layout()`` started from ``init_latent`` (fp32
+        [1|B, C, h, w], the encoded image) noised to a timestep inside the schedule, instead of from pure noise at its top.  Of the n nodes
+        of the schedule ``S`` gives this sampler, the last ``host.img2img_run_steps(n, strength)`` run; ``strength`` in (0, 1], 1 = all of
+        them (the image then only shifts the starting noise by sqrt(acp[t_top]) * init_latent).  ``input["x"]`` is the noise the image is
+        mixed with (drawn here when None, like ``sample()``'s starting latent); the start itself draws nothing.
+
+        ``alpha_generator_func`` is asked for the number of steps that RUN, so the fuser schedule (``alpha_type``) spans them: taking the tail
+        of the full schedule's scales instead would leave a [0.3, 0, 0.7] run at strength 0.5 with the grounding switched off on every step,
+        and the layout ignored.  PLMS starts its history empty (the first step that runs evaluates twice), DPM-Solver++ starts first order
+        and counts the nodes that run for its lower-order final step; the masked blend and three-branch guidance belong to the loop and
+        compose unchanged."""
+        self.make_schedule(S, *self._sample_schedule)
+        return self._sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0, layout_guidance_scale=layout_guidance_scale,
+                              init_latent=init_latent, strength=strength)
+
+    @torch.no_grad()
+    def _sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, layout_guidance_scale=None, init_latent=None, strength=None):
         """The loop over the schedule in place (``plms_sampling`` / ``ddim_sampling`` / ``dpm_sampling`` by the classes' own names).
         ``layout_guidance_scale``: None = one scale for text and layout, the [cond ; uncond] batch; a number = the layout's own scale s_l
-        next to s_t = ``guidance_scale`` (three-branch guidance, see ``_needs_text_branch``)."""
+        next to s_t = ``guidance_scale`` (three-branch guidance, see ``_needs_text_branch``).  ``init_latent`` + ``strength``: both or
+        neither; the loop runs the schedule's tail from the noised ``init_latent`` (``sample_from``)."""
         layout = layout_guidance_scale
         if layout is not None and uc is None:
             raise ValueError("layout_guidance_scale needs uc, the unconditional context: the text-only and the unconditional branch are "
                              "evaluated whatever guidance_scale is")
-        x_a, reps, time_range, alphas, blend = self._begin(self.tag, shape, input, uc, guidance_scale, mask, x0, layout is not None)
+        if (init_latent is None) != (strength is None):
+            raise ValueError("strength needs init_latent, the latent of the image to start from" if init_latent is None else
+                             "init_latent needs strength, the share of the schedule to run")
+        x_a, reps, time_range, alphas, blend = self._begin(self.tag, shape, input, uc, guidance_scale, mask, x0, layout is not None,
+                                                           init_latent=init_latent, strength=strength)
         model = self.model
-        total_steps = self.ddim_timesteps.shape[0]
+        total_steps = len(time_range)           # the nodes that run: the whole schedule, or its tail under image-to-image
         state = self._alloc(x_a)
 
         def at(t):
@@ -149,12 +173,16 @@ class _Sampler(object):
         self.ddim_sigmas = s["ddim_sigmas"]
         self._sched = s
 
-    def _begin(self, tag, shape, input, uc, guidance_scale, mask, x0, layout=False):
+    def _begin(self, tag, shape, input, uc, guidance_scale, mask, x0, layout=False, init_latent=None, strength=None):
         """Everything before the loop: the starting latent in the engine buffer ``<tag>.x``, the conditioning hoisted once, the fuser scales of
         the steps and the masked blend of one step (None without a mask).  ``layout``: three-branch guidance -- the conditioning takes the form
-        the first step needs.  Returns (x_a, reps, time_range, alphas, blend)."""
+        the first step needs.  ``init_latent`` / ``strength`` (image-to-image): ``time_range`` is the tail of the schedule that runs and the
+        starting latent q_sample(init_latent, time_range[0]) with ``input["x"]`` as its noise, one gl_q_sample launch into ``<tag>.x``.
+        Returns (x_a, reps, time_range, alphas, blend)."""
         if mask is not None and x0 is None:
             raise AssertionError("a mask needs x0, the latent of the image to keep (plms.py:96)")       # before the model is touched
+        if strength is not None:
+            strength = host.check_strength(strength)
         model, eng = self.model, self.model.engine
         dev = self.device
         b = shape[0]
@@ -165,6 +193,15 @@ class _Sampler(object):
         x = img.to(dev, torch.float32).contiguous().clone()
 
         time_range = np.flip(self.ddim_timesteps)
+        init_d = None
+        if init_latent is not None:
+            if not torch.is_tensor(init_latent) or init_latent.dtype != torch.float32 or init_latent.dim() != 4 or \
+                    init_latent.shape[1:] != x.shape[1:] or init_latent.shape[0] not in (1, x.shape[0]):
+                got = f"{init_latent.dtype} {tuple(init_latent.shape)}" if torch.is_tensor(init_latent) else type(init_latent).__name__
+                raise ValueError(f"init_latent must be fp32 [1|{x.shape[0]}, {tuple(x.shape[1:])}], got {got}")
+            init_d = init_latent.to(dev, torch.float32).contiguous()
+            n = len(time_range)
+            time_range = time_range[n - host.img2img_run_steps(n, strength):]       # the last n_run nodes; step i reads table index n_run - i - 1
         alphas = self.alpha_generator_func(len(time_range)) if self.alpha_generator_func is not None else None
 
         # ---- conditioning, once per image: [cond ; uncond] when CFG is active (plms.py:115-124)
@@ -176,7 +213,14 @@ class _Sampler(object):
             reps = model.condition(input, uc if uc is not None and guidance_scale != 1 else None, always_extra=True)
 
         x_a = eng.buf(f"{tag}.x", tuple(x.shape), torch.float32)    # running latent (the engine copies it per forward)
-        x_a.copy_(x)
+        if init_d is None:
+            x_a.copy_(x)
+        else:
+            # q_sample(init_latent, t0) with the caller's noise; the coefficients from the fp32 buffers, as the blend reads them (ldm.py:19-22)
+            t0 = int(time_range[0])
+            sac = self.diffusion.sqrt_alphas_cumprod.detach().cpu().numpy()
+            s1ac = self.diffusion.sqrt_one_minus_alphas_cumprod.detach().cpu().numpy()
+            ops.q_sample(init_d, x, float(sac[t0]), float(s1ac[t0]), out=x_a)
 
         blend = None
         if mask is not None:
@@ -332,7 +376,7 @@ class DPMSolverSampler(_Sampler):
         return dict(hist=self.model.engine.buf("dpmpp.x0", tuple(x_a.shape), torch.float32), prev=None)
 
     def _step(self, st, x_a, at, i, time_range, index):
-        sq_at, s1m, c_x, c_d, w1, w0 = host.dpm_step_coefs(self._sched, index, st["prev"], self.order)
+        sq_at, s1m, c_x, c_d, w1, w0 = host.dpm_step_coefs(self._sched, index, st["prev"], self.order, n_nodes=len(time_range))
         if self._guided_eps is not None:
             ops.dpmpp_update(self._guided_eps(x_a, time_range[i]), x_a, x_a, st["hist"], sqrt_at=sq_at, s1m=s1m, c_x=c_x, c_d=c_d, w1=w1, w0=w0,
                              x0_old=st["hist"] if w0 != 0 else None)

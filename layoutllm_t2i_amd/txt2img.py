@@ -50,7 +50,8 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
              guidance_scale: float = 7.5, alpha_type: Sequence[float] = (0.3, 0.0, 0.7), is_center: bool = False,
              steps: Optional[int] = None, starting_noise: Optional[torch.Tensor] = None, folder: Optional[str] = None, device=None,
              instruction=None, draw_boxes: bool = False, sampler: str = "plms", ddim_eta: float = 0.0, dpm_order: int = 2,
-             dpm_discretize: str = "logsnr", layout_guidance_scale: Optional[float] = None) -> dict:
+             dpm_discretize: str = "logsnr", layout_guidance_scale: Optional[float] = None, init_image=None,
+             strength: Optional[float] = None) -> dict:
     """``all_models``: the 5-tuple of ``interface.load_all_models``; ``policy`` / ``pool``: policy.PolicyNetwork / policy.CandidatePool;
     ``tokenize``: list of strings -> (input_ids, attention_mask) for the CLIP text tower (``pool.towers``, else ``clip_model``);
     ``clip_model`` / ``clip_processor``: the grounding phrases' encoder, as for ``interface.generate_one_image``.
@@ -62,7 +63,9 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
     ``dpm_order`` / ``dpm_discretize``: ``args["dpm_order"]`` / ``args["dpm_discretize"]`` of ``sampler="dpmpp_2m"`` (sampler.resolve_sampler;
     with ``steps=20`` an image costs 20 UNet evaluations in place of PLMS's 51).  ``layout_guidance_scale``: None, or how hard the images
     follow the LLM's boxes, apart from ``guidance_scale``'s prompt adherence -- ``args["layout_guidance_scale"]``
-    (interface.check_layout_guidance; checked before the policy or the LLM runs).
+    (interface.check_layout_guidance; checked before the policy or the LLM runs).  ``init_image`` (a path or a PIL.Image) with ``strength``
+    in (0, 1] (None: 0.75): image-to-image -- every image is that picture re-rendered under the prompt and the LLM's boxes, handed through
+    as ``meta["init_image"]`` / ``args["strength"]`` (interface.check_strength; checked before the policy or the LLM runs).
     Returns dict(images, categories, bboxes_ltrb, cids, prompt_text, llm_output)."""
     model = all_models[0]
     if not family_of(model.cfg).boxes:
@@ -79,6 +82,9 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
     layout = interface.check_layout_guidance(layout_guidance_scale, family_of(model.cfg))
     if layout is not None:
         sampler_args[interface.LAYOUT_GUIDANCE_KEY] = layout
+    strength = interface.check_strength(strength, init_image is not None)
+    if strength is not None:
+        sampler_args[interface.STRENGTH_KEY] = strength
     towers = pool.towers if pool.towers is not None else clip_model
     if towers is None:
         raise ValueError("no text tower for the prompt: build the pool with CandidatePool.from_captions, or pass clip_model")
@@ -97,6 +103,8 @@ def generate(all_models, policy: PolicyNetwork, pool: CandidatePool, prompt: str
     convert = convert_xcycwh_to_ltrb if is_center else convert_xywh_to_ltrb
     locations = [convert(b) for b in bboxes]
     meta = dict(prompt=prompt, phrases=categories, locations=locations, alpha_type=list(alpha_type))
+    if init_image is not None:
+        meta[interface.INIT_IMAGE_KEY] = init_image
 
     images = []
     h, w = interface.latent_hw(None, None, all_models[1]) if starting_noise is None else (0, 0)
